@@ -8,6 +8,13 @@ frames per GPU.  Batches rotate over R distinct device buffer sets (C2: 32, 4 GB
 set exceeds the 256 MB Infinity Cache and the timing is HBM-bound, not MALL-bound; consecutive
 steps share launches of up to 32 batches (fb_parse_classify_seg_batches_dev), split evenly.
 
+A plain run sets up, warms up, times --steps steps and prints the result line (its roofline entry
+comes from the timed steps themselves).  --dump-outputs DIR also writes what the last timed step
+computed (collect_outputs) as DIR/<name>.npy.  Everything else -- the `extra` entries (one batch
+per launch, the queue, the other layout, IMIX C3, C4, the host paths), the CPU baselines and the
+stream-copy reference -- runs only with --full, where the --no-* options select among them.
+(The C5 exchange of an N > 1 run decides that run's `c5_ok` and exit status: it stays part of it.)
+
 Multi-GPU: one process per GPU.  Under torchrun (WORLD_SIZE set) every process is one rank;
 `python3 bench.py --gpus N` with no WORLD_SIZE spawns the N rank processes itself (spawn_ranks,
 before anything touches the GPU) and exits with their status.  Packets are sharded by index (each
@@ -55,8 +62,70 @@ def plan_launches(k, bpl):
     return [q + 1] * r + [q] * (m - r)
 
 
+DUMP_SEED = 0xD0A7  # --dump-outputs: the seed of the row sample of an output past its byte cap
+DUMP_CAPS = {"session_records": 32_000_000, "flow_table": 16_000_000, "dns_records": 8_000_000}  # < 64 MB in all
+
+
+def _columns_f64(a, skip=("padding", "reserved", "reserved0", "reserved1", "reserved2", "slot")):
+    """A structured array as a 2-D float64 array: one column per scalar field (sub-arrays flattened),
+    in the dtype's field order, without the padding / reserved fields and the table placement."""
+    cols = [a[name].reshape(len(a), int(np.prod(a.dtype[name].shape))).astype(np.float64)
+            for name in a.dtype.names if name not in skip]
+    return np.concatenate(cols, axis=1)
+
+
+def _dump_array(a, cap_bytes):
+    """_columns_f64 of the structured array `a`, or of a fixed sample of its rows (DUMP_SEED, rows
+    kept in order) where the whole would exceed cap_bytes."""
+    keep = cap_bytes // (8 * _columns_f64(a[:0]).shape[1])
+    if len(a) > keep:
+        a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(len(a), size=keep, replace=False))]
+    return _columns_f64(a)
+
+
+def collect_outputs(N, lib, ctx, buf, n, mode, flow, records, st, stream):
+    """What a caller of the timed path holds after its last step (--dump-outputs), as float64 arrays:
+    the batch stats, the SESSION and DNS records in packet order (mode "seg": the per-segment counts
+    and the records N.seg_unpack densifies) and, with the session table (flow), every flow record
+    ordered by its key.  Outputs past their DUMP_CAPS share are a fixed sample of their rows."""
+    _, _, d_out, d_dns, _ = buf
+    ns, nd = int(st[0]["n_session"]), int(st[0]["n_dns"])
+    out = {"stats": _columns_f64(st)}
+    if mode == "seg":
+        nseg = (n + N.FB_SEG_FRAMES - 1) // N.FB_SEG_FRAMES
+        seg = d_dns.download(np.zeros(nseg, dtype=np.uint32), stream=stream.ptr)
+        raw = d_out.download(np.zeros(nseg * N.SEG_BYTES, dtype=np.uint8), stream=stream.ptr)
+        out["segment_counts"] = np.stack([seg & 0xFFFF, seg >> 16], axis=1).astype(np.float64)
+        # table-only calls store no SESSION record: only the DNS tails of the segments are output
+        recs, dns = N.seg_unpack(raw, seg if records else seg & np.uint32(0xFFFF0000))
+    else:
+        recs = d_out.download(np.zeros(max(ns, 1), dtype=N.PKT_OUT_DTYPE), stream=stream.ptr)[:ns]
+        dns = d_dns.download(np.zeros(max(nd, 1), dtype=N.DNS_OUT_DTYPE), stream=stream.ptr)[:nd]
+    if records:
+        out["session_records"] = _dump_array(recs, DUMP_CAPS["session_records"])
+    out["dns_records"] = _dump_array(dns, DUMP_CAPS["dns_records"])
+    if flow:
+        cnt = C.c_uint64()
+        N.check(lib.fb_flow_count(ctx, C.byref(cnt), stream.ptr))
+        tab = np.zeros(max(int(cnt.value), 1), dtype=N.FLOW_REC_DTYPE)
+        got = C.c_uint64(0)
+        N.check(lib.fb_flow_export_sessions(ctx, N.FB_FILTER_ALL, N.ptr(tab), int(cnt.value), C.byref(got), stream.ptr))
+        tab = tab[: got.value]
+        key = _columns_f64(tab[["src_ip", "dst_ip", "src_port", "dst_port", "protocol", "family"]])
+        tab = tab[np.lexsort(key[:, ::-1].T)]  # table placement is not content: ordered by key, src_ip major
+        out["flow_table"] = _dump_array(tab, DUMP_CAPS["flow_table"])
+    return out
+
+
+def write_outputs(path, outputs, rank):
+    """--dump-outputs DIR: DIR/<name>.npy per output array (rank r > 0 of a multi-GPU run: <name>.rank<r>.npy)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + (".rank%d" % rank if rank else "") + ".npy"), np.ascontiguousarray(a))
+
+
 def run_config(N, lib, ctx, config_id, n, steps, warmup, rotate, rank, world, dist, flow=False, mode="seg", bpl=1,
-               synth_kw=None, pipelined=False, stage_extras=True, records=True, timed=False):
+               synth_kw=None, pipelined=False, stage_extras=True, records=True, timed=False, dump=False):
     """Time `steps` steps (one step = one batch through the hot path).  mode "seg":
     fb_parse_classify_seg_dev (records compacted per 64-frame wavefront segment, no
     cross-workgroup dependency); mode "dense": fb_parse_classify_dev (the same kernel + the
@@ -206,6 +275,9 @@ def run_config(N, lib, ctx, config_id, n, steps, warmup, rotate, rank, world, di
     algo = algorithmic_bytes(offs, st[0]["n_session"], st[0]["n_dns"])
     # make sure the last step's results are sane too
     st2 = bufs[(steps - 1) % rotate][4].download(np.zeros(1, dtype=N.STATS_DTYPE), stream=stream.ptr)
+    # --dump-outputs: the last timed step's results, before anything else runs on the context
+    outputs = collect_outputs(N, lib, ctx, bufs[(steps - 1) % rotate], n, mode, flow, records, st2, stream) \
+        if dump else None
     stage = None
     if flow:
         # after warmup every session exists: the timed steps are all updates
@@ -250,7 +322,7 @@ def run_config(N, lib, ctx, config_id, n, steps, warmup, rotate, rank, world, di
         for x in (b if isinstance(b, tuple) else (b,)):
             x.free()
     return dict(frames=frames, offs=offs, elapsed=elapsed, local_elapsed=local_elapsed, ev_ms=ev_ms,
-                algo_bytes=algo, stage=stage,
+                algo_bytes=algo, stage=stage, outputs=outputs,
                 host_us=round((t1 - t0) * 1e6 - ev_ms * 1e3, 1),
                 launches=n_launch, stats={k: int(st[0][k]) for k in ("n_session", "n_dns", "n_drop", "n_filtered")})
 
@@ -1123,7 +1195,14 @@ def main():
                     help="profiling: the main run with Zipf(s) flow popularity instead of uniform")
     ap.add_argument("--world-check", action="store_true",
                     help="launch plumbing only: the ranks join the group and rank 0 reports it (no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement (the `extra` entries, the CPU "
+                         "baselines, the stream-copy reference); the --no-* options select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: this process only starts the N ranks (before any HIP call) and waits
@@ -1174,7 +1253,10 @@ def main():
     main_kw = dict(zipf=1, zipf_s=args.zipf) if args.zipf else None
     main_r = run_config(N, lib, ctx, args.config, n, args.steps, args.warmup, rotate, rank, world, dist,
                         flow=args.config == 4, mode=args.mode, bpl=bpl,
-                        synth_kw=main_kw, pipelined=pipe, records=not args.table_only)
+                        synth_kw=main_kw, pipelined=pipe, records=not args.table_only,
+                        stage_extras=args.full, dump=args.dump_outputs is not None)
+    if args.dump_outputs is not None:
+        write_outputs(args.dump_outputs, main_r.pop("outputs"), rank)
     # the dominant kernel's launches: algorithmic bytes per launch / average launch duration
     per_launch_s = main_r["ev_ms"] / 1e3 / main_r["launches"]
     algo_per_launch = main_r["algo_bytes"] * args.steps / main_r["launches"]
@@ -1189,11 +1271,12 @@ def main():
         per_rank = [dict(rank=r, Mpackets_s=round(float(t[1]), 2), roofline_frac=round(float(t[0]) / HBM_PEAK_GBS, 4))
                     for r, t in enumerate(allr)]
 
+    # everything below times or checks something beside the headline: only with --full
     extra = {}
-    if main_r["stage"]:
+    if main_r["stage"] and args.full:
         extra.update(c4_split(N, lib, ctx, main_r, n, args.steps, args.warmup, rank, world, dist, args.mode, pipe,
                               main_kw, records=not args.table_only))
-    if args.config == 4 and not args.no_other_mode:  # C4 also with Zipf(1.1) flow popularity
+    if args.full and args.config == 4 and not args.no_other_mode:  # C4 also with Zipf(1.1) flow popularity
         rz = run_config(N, lib, ctx, 4, n, max(args.steps // 2, 5), max(args.warmup // 2, 2), rotate, rank, world,
                         dist, flow=True, mode=args.mode, synth_kw=dict(zipf=1, zipf_s=1.1))
         sz = rz["stage"]
@@ -1201,7 +1284,7 @@ def main():
                                 unit="Mpackets/s", parse_ms=round(sz["parse_ms"], 4),
                                 flow_update_ms=round(sz["flow_ms"], 4), flows_in_table=sz["flows"],
                                 history_ms=round(sz["history_ms"], 4))
-    if bpl > 1 and not args.no_single_launch:  # the same workload with one batch per launch
+    if args.full and bpl > 1 and not args.no_single_launch:  # the same workload with one batch per launch
         st_1 = max(args.steps // 2, 10)
         r1 = run_config(N, lib, ctx, args.config, n, st_1, max(args.warmup // 2, 2), rotate, rank, world, dist,
                         mode=args.mode, bpl=1)
@@ -1223,7 +1306,7 @@ def main():
                 except Exception as e:
                     extra["single_batch_queue_table"] = {"error": repr(e)[:300]}
     # N > 1: the scaling line needs only the headline path (the other layout is timed at N = 1)
-    if not args.no_other_mode and world == 1:
+    if args.full and not args.no_other_mode and world == 1:
         other = "dense" if args.mode == "seg" else "seg"
         st_o = max(args.steps // 2, 10)
         ro = run_config(N, lib, ctx, args.config, n, st_o, max(args.warmup // 2, 2), rotate, rank, world, dist,
@@ -1233,7 +1316,7 @@ def main():
                                       ms_per_step=round(ro["elapsed"] * 1e3 / st_o, 4),
                                       roofline_achieved_GBs=round(ro["algo_bytes"] / plo / 1e9, 1),
                                       roofline_frac=round(ro["algo_bytes"] / plo / 1e9 / HBM_PEAK_GBS, 4))
-    if not args.no_imix and args.config == 2:
+    if args.full and not args.no_imix and args.config == 2:
         steps3 = max(args.steps // 2, 10)
         bpl3 = 32 if args.mode == "seg" and bpl > 1 else 1
         r3 = run_config(N, lib, ctx, 3, 1 << 20, steps3, max(args.warmup // 2, 2), 32, rank, world, dist,
@@ -1246,10 +1329,10 @@ def main():
                                 roofline_frac=round(algo3 / pl3 / 1e9 / HBM_PEAK_GBS, 4),
                                 batches_per_launch=bpl3, algo_bytes_per_batch=r3["algo_bytes"])
 
-    if args.config == 2 and not args.no_c4:  # BASELINE configs[3] in the default (driver-timed) run
+    if args.full and args.config == 2 and not args.no_c4:  # BASELINE configs[3] in the default (driver-timed) run
         extra["c4"] = c4_line(N, lib, ctx, max(args.steps // 10, 20), 5, rank, world, dist,
                               0 if args.no_cpu_baseline else args.cpu_seconds / 2)
-    if not args.no_host and rank == 0 and args.config == 2:
+    if args.full and not args.no_host and rank == 0 and args.config == 2:
         extra["host_inclusive_c2"] = host_inclusive(N, lib, ctx, main_r["frames"], main_r["offs"])
         try:
             extra["host_ring_c2"] = host_ring(N, lib, ctx, main_r["frames"], main_r["offs"])
@@ -1281,13 +1364,13 @@ def main():
         extra["c5_flow_reduce"], c5_ok = c5_checked(run, world, args.gpus, dist)
 
     copy_gbs = None
-    if rank == 0 and not args.no_copy_ref:  # (after the timed region)
+    if args.full and rank == 0 and not args.no_copy_ref:  # (after the timed region)
         try:
             copy_gbs = stream_copy(device)
         except Exception as e:  # a reference point: reported, never allowed to break the bench line
             print("stream copy reference failed: %r" % (e,), file=sys.stderr)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(main_r["frames"], main_r["offs"], args.cpu_seconds)
 
     lib.fb_destroy(ctx)

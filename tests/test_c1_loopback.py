@@ -6,7 +6,9 @@ SessionFilter.All (100 flows, both directions of each 127.0.0.1 <-> 127.0.0.1:80
 into one canonical key), and under the reference's default GlobalOnly every one of them is
 filtered -- the reason the reference example prints 0 sessions for loopback (src/capture.rs:108,
 src/packets.rs:323-324).  On the GPU: the same batch through FlodbaddGpuCapture, bit-exact."""
+import collections
 import os
+import socket
 import sys
 
 import numpy as np
@@ -45,17 +47,66 @@ def test_c1_fixture_oracles():
     assert len(g_out) == 0 and (g_cls == 3).all() and int(g_st[0]["n_filtered"]) == n
 
 
-def test_loopback_capture_tool():
-    """The capture harness itself (AF_PACKET on lo); skipped without CAP_NET_RAW."""
+class _LoopbackModel:
+    """What a pair of AF_PACKET sockets bound to `lo` shows the capture harness, without the
+    privilege: every frame sent comes back twice (the PACKET_OUTGOING copy, then the received one),
+    between other hosts' traffic (a short frame, and a 64-B frame without the harness's mark)."""
+    queue = None
+
+    def __init__(self, family, kind, proto):
+        assert (family, kind) == (socket.AF_PACKET, socket.SOCK_RAW)
+        self.bound = None
+
+    def setsockopt(self, *a):
+        pass
+
+    def settimeout(self, t):
+        pass
+
+    def bind(self, addr):
+        assert addr == ("lo", 0)
+        self.bound = addr
+
+    def send(self, data):
+        assert self.bound
+        q = _LoopbackModel.queue
+        q.append((bytes(data), ("lo", 0x0800, 4, 772, b"")))  # PACKET_OUTGOING
+        if len(q) % 7 == 0:
+            q.append((b"\xff" * 42, ("lo", 0x0806, 0, 772, b"")))
+            q.append((b"\0" * 12 + b"\x08\x00" + b"\x45" + b"\0" * 49, ("lo", 0x0800, 0, 772, b"")))
+        q.append((bytes(data), ("lo", 0x0800, 0, 772, b"")))  # PACKET_HOST
+        return len(data)
+
+    def recvfrom(self, n):
+        assert self.bound
+        if not _LoopbackModel.queue:
+            raise socket.timeout()
+        return _LoopbackModel.queue.popleft()
+
+    def close(self):
+        pass
+
+
+def test_loopback_capture_tool(monkeypatch):
+    """The capture harness itself: always against a model of AF_PACKET sockets on lo, and where
+    the process may open raw sockets (CAP_NET_RAW) also against the real interface."""
     sys.path.insert(0, os.path.join(ROOT, "examples"))
     import capture_sessions
-    try:
-        frames, offs, _ = capture_sessions.capture_loopback(300, 10, timeout=5.0)
-    except (PermissionError, OSError) as e:
-        pytest.skip("no raw capture on lo here: %s" % e)
-    assert len(offs) - 1 == 300
     expect = b"".join(capture_sessions.frame(k, 10) for k in range(300))
+    with monkeypatch.context() as m:
+        _LoopbackModel.queue = collections.deque()
+        m.setattr(socket, "socket", _LoopbackModel)
+        frames, offs, _ = capture_sessions.capture_loopback(300, 10, timeout=5.0)
+    assert len(offs) - 1 == 300
     assert frames.tobytes() == expect  # each injected frame captured once, in order
+    assert np.array_equal(np.diff(offs.astype(np.int64)), np.full(300, 64))
+    try:
+        socket.socket(socket.AF_PACKET, socket.SOCK_RAW, socket.htons(capture_sessions.ETH_P_ALL)).close()
+    except OSError:
+        return  # no raw sockets for this user: the real interface is out of reach
+    frames, offs, _ = capture_sessions.capture_loopback(300, 10, timeout=5.0)
+    assert len(offs) - 1 == 300
+    assert frames.tobytes() == expect
 
 
 @pytest.mark.gpu

@@ -4,12 +4,12 @@ set -e
 R=$(pwd); export TMPDIR=/tmp
 for v in ${VARS:-product}; do
   L=""; [ "$v" != product ] && L=$R/flodbadd_amd/build/var_$v.so
-  mkdir -p $R/gpurun_out/profz_$v
+  mkdir -p $R/bench_out/profz_$v
   cd /tmp
-  FB_BENCH_ABLATION=1 FLODBADD_GPU_LIB=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/profz_$v -o run -- python3 $R/bench.py --config 4 --zipf ${ZIPF:-1.1} --c4-sync --steps 10 --warmup 2 --no-cpu-baseline --no-host --no-imix --no-other-mode > $R/gpurun_out/profz_$v/bench.log 2>&1
+  FB_BENCH_ABLATION=1 FLODBADD_GPU_LIB=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/bench_out/profz_$v -o run -- python3 $R/bench.py --full --config 4 --zipf ${ZIPF:-1.1} --c4-sync --steps 10 --warmup 2 --no-cpu-baseline --no-host --no-imix --no-other-mode > $R/bench_out/profz_$v/bench.log 2>&1
   cd $R
   echo "== $v"
-  python3 - $R/gpurun_out/profz_$v <<'PY'
+  python3 - $R/bench_out/profz_$v <<'PY'
 import sqlite3, glob, collections, sys
 db = glob.glob(sys.argv[1] + "/**/*.db", recursive=True)[0]
 acc = collections.defaultdict(list)

@@ -8,6 +8,6 @@ bash tools/experiments/r2_profile.sh || exit 1
 bash tools/prof_driver.sh || exit 1
 OUT=$R/gpurun_out/profdense; rm -rf "$OUT"; mkdir -p "$OUT"; export TMPDIR=/tmp
 cd /tmp
-timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -- python3 "$R/bench.py" --mode dense --steps 100 --warmup 10 \
+timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -- python3 "$R/bench.py" --full --mode dense --steps 100 --warmup 10 \
   --no-cpu-baseline --no-imix --no-other-mode --no-host --no-single-launch > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail "$OUT/bench.err"; exit 1; }
 tail -c 300 "$OUT/bench.json"

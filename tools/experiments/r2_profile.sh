@@ -14,11 +14,11 @@ for CFG in ${CFGS:-2 3 4}; do
     4) W=2; ST=10; SP=6;;
   esac
   NO="--no-cpu-baseline --no-imix --no-other-mode --no-host --no-single-launch"
-  step timeout -k 10 300 python3 bench.py --config $CFG --steps 200 --warmup 20 > "$OUT/bench_c$CFG.json" 2> "$OUT/bench_c$CFG.err"
+  step timeout -k 10 300 python3 bench.py --full --config $CFG --steps 200 --warmup 20 > "$OUT/bench_c$CFG.json" 2> "$OUT/bench_c$CFG.err"
   cd /tmp
-  step timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/trace_c$CFG" -o run -- python3 "$R/bench.py" --config $CFG --steps $ST --warmup $W $NO > "$OUT/trace_c$CFG.log" 2>&1
-  step timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch_c$CFG" -o run -- python3 "$R/bench.py" --config $CFG --steps $SP --warmup $W $NO > "$OUT/pmc_fetch_c$CFG.log" 2>&1
-  step timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write_c$CFG" -o run -- python3 "$R/bench.py" --config $CFG --steps $SP --warmup $W $NO > "$OUT/pmc_write_c$CFG.log" 2>&1
+  step timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/trace_c$CFG" -o run -- python3 "$R/bench.py" --full --config $CFG --steps $ST --warmup $W $NO > "$OUT/trace_c$CFG.log" 2>&1
+  step timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch_c$CFG" -o run -- python3 "$R/bench.py" --full --config $CFG --steps $SP --warmup $W $NO > "$OUT/pmc_fetch_c$CFG.log" 2>&1
+  step timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write_c$CFG" -o run -- python3 "$R/bench.py" --full --config $CFG --steps $SP --warmup $W $NO > "$OUT/pmc_write_c$CFG.log" 2>&1
   cd "$R"
   echo "c$CFG done: $(head -c 300 $OUT/bench_c$CFG.json)"
 done

@@ -8,12 +8,12 @@ T="--table-only"; [ -n "${C4REC:-}" ] && T=""
 A="--config 4 --c4-sync --no-cpu-baseline --no-host --no-imix --no-other-mode $T"
 D=$R/gpurun_out/c4prof; rm -rf $D; mkdir -p $D
 cd /tmp
-FLODBADD_GPU_LIB=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $D/trace -o run -- python3 $R/bench.py $A --steps 20 --warmup 3 > $D/bench.json 2> $D/bench.err || { grep -v "^[WIE]20" $D/bench.err | tail -5; exit 1; }
+FLODBADD_GPU_LIB=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $D/trace -o run -- python3 $R/bench.py --full $A --steps 20 --warmup 3 > $D/bench.json 2> $D/bench.err || { grep -v "^[WIE]20" $D/bench.err | tail -5; exit 1; }
 cd $R; python3 tools/timeline.py $D/trace 40 8
 [ -n "${NOPMC:-}" ] && exit 0
 cd /tmp
 for P in FETCH_SIZE WRITE_SIZE; do
-  FLODBADD_GPU_LIB=$L timeout -s KILL 120 rocprofv3 --pmc $P -d $D/pmc_$P -o run -- python3 $R/bench.py $A --steps 6 --warmup 2 > $D/pmc_$P.log 2>&1 || { echo "pmc $P failed"; tail -3 $D/pmc_$P.log; exit 1; }
+  FLODBADD_GPU_LIB=$L timeout -s KILL 120 rocprofv3 --pmc $P -d $D/pmc_$P -o run -- python3 $R/bench.py --full $A --steps 6 --warmup 2 > $D/pmc_$P.log 2>&1 || { echo "pmc $P failed"; tail -3 $D/pmc_$P.log; exit 1; }
 done
 cd $R
 python3 - $D <<'PY'

@@ -5,7 +5,7 @@ set -u
 cd "${GRAFT_REPO_ROOT}"; R=$(pwd); export TMPDIR=/tmp; O=$R/gpurun_out/r3; rm -rf $O; mkdir -p $O
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -p no:cacheprovider > $O/tests.log 2>&1
 rc=$?; tail -2 $O/tests.log; [ $rc -eq 0 ] || { grep -E "FAIL|Error" $O/tests.log | head; exit $rc; }
-timeout -k 10 600 python3 bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python3 -c "
 import json; d=json.load(open('$O/bench.json')); e=d['extra']
 print('C2', d['value'], d['roofline']['frac'], 'cpu', d['cpu_baseline']['value'])
@@ -18,6 +18,6 @@ cp -r gpurun_out/profdrv $O/profdrv
 NOSQ=1 bash tools/experiments/r3_c4prof.sh || exit 1
 cp -r gpurun_out/c4prof $O/c4prof
 cd /tmp
-timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/dense -o run -- python3 $R/bench.py --mode dense --steps 100 --warmup 10 \
+timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/dense -o run -- python3 $R/bench.py --full --mode dense --steps 100 --warmup 10 \
   --no-cpu-baseline --no-imix --no-other-mode --no-host --no-single-launch > $O/dense.json 2> $O/dense.err || { tail $O/dense.err; exit 1; }
 cd $R; python3 tools/timeline.py $O/dense 0 0 | head -4

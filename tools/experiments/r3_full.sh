@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT}"; R=$(pwd); export TMPDIR=/tmp; mkdir -p gpurun_out
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -p no:cacheprovider > gpurun_out/full_tests.log 2>&1
 rc=$?; tail -3 gpurun_out/full_tests.log; [ $rc -eq 0 ] || { grep -E "FAIL|Error" gpurun_out/full_tests.log | head; exit $rc; }
 D=$R/gpurun_out/fullbench; rm -rf $D; mkdir -p $D
-timeout -k 10 600 python3 bench.py > $D/bench.json 2> $D/bench.err || { tail -5 $D/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $D/bench.json 2> $D/bench.err || { tail -5 $D/bench.err; exit 1; }
 python3 -c "
 import json; d=json.load(open('$D/bench.json')); e=d['extra']
 print(d['value'], d['roofline']['frac'], d['cpu_baseline']['value'])

@@ -8,7 +8,7 @@ for mode in sync pipe; do
   D=$R/gpurun_out/k2c_$mode; rm -rf $D; mkdir -p $D
   X=""; [ $mode = sync ] && X="--c4-sync"
   cd /tmp
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $D -o run -- python3 $R/bench.py --config 4 $X --steps 20 --warmup 3 --no-cpu-baseline --no-host --no-imix --no-other-mode > $D/bench.json 2> $D/bench.err || { tail -5 $D/bench.err; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $D -o run -- python3 $R/bench.py --full --config 4 $X --steps 20 --warmup 3 --no-cpu-baseline --no-host --no-imix --no-other-mode > $D/bench.json 2> $D/bench.err || { tail -5 $D/bench.err; exit 1; }
   cd $R
   echo "== $mode"; python3 tools/timeline.py $D 0 0 | head -8
   python3 -c "import json;d=json.load(open('$D/bench.json'));print(d['value'], d['extra']['c4_stages']['flow_update_ms'], d['extra']['c4_stages']['history_ms'])"

@@ -15,12 +15,12 @@ for k, v in sorted(acc.items(), key=lambda kv: -sum(kv[1]))[:6]:
 PY
 }
 for o in partition original; do
-  rm -rf $R/gpurun_out/k2l_$o; mkdir -p $R/gpurun_out/k2l_$o
+  rm -rf $R/bench_out/k2l_$o; mkdir -p $R/bench_out/k2l_$o
   cd /tmp
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/k2l_$o -o run -- python3 $R/tools/experiments/k2_local.py --order $o -- --config 4 --c4-sync --steps 10 --warmup 2 --no-cpu-baseline --no-host --no-imix --no-other-mode > $R/gpurun_out/k2l_$o/bench.json 2> $R/gpurun_out/k2l_$o/bench.err || { grep -v "^[WIE]20" $R/gpurun_out/k2l_$o/bench.err | tail -5; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/bench_out/k2l_$o -o run -- python3 $R/tools/experiments/k2_local.py --order $o -- --full --config 4 --c4-sync --steps 10 --warmup 2 --no-cpu-baseline --no-host --no-imix --no-other-mode > $R/bench_out/k2l_$o/bench.json 2> $R/bench_out/k2l_$o/bench.err || { grep -v "^[WIE]20" $R/bench_out/k2l_$o/bench.err | tail -5; exit 1; }
   cd $R
-  echo "== $o"; summ $R/gpurun_out/k2l_$o
-  python3 -c "import json;d=json.load(open('$R/gpurun_out/k2l_$o/bench.json'));print(d['value'],d['extra']['c4_stages']['parse_ms'],d['extra']['c4_stages']['flow_update_ms'])"
+  echo "== $o"; summ $R/bench_out/k2l_$o
+  python3 -c "import json;d=json.load(open('$R/bench_out/k2l_$o/bench.json'));print(d['value'],d['extra']['c4_stages']['parse_ms'],d['extra']['c4_stages']['flow_update_ms'])"
 done
-timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > gpurun_out/r3_default.json 2> gpurun_out/r3_default.err || { tail -5 gpurun_out/r3_default.err; exit 1; }
-python3 -c "import json;d=json.load(open('gpurun_out/r3_default.json'));print(d['value'],d['roofline']['frac']);print(json.dumps(d['extra']['c4'])[:1500]);print(d['cpu_baseline'])"
+timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > bench_out/r3_default.json 2> bench_out/r3_default.err || { tail -5 bench_out/r3_default.err; exit 1; }
+python3 -c "import json;d=json.load(open('bench_out/r3_default.json'));print(d['value'],d['roofline']['frac']);print(json.dumps(d['extra']['c4'])[:1500]);print(d['cpu_baseline'])"

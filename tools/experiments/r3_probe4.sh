@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT}"; R=$(pwd); export TMPDIR=/tmp
 timeout -k 10 120 ./tools/ubench_gather 10485760 10 || exit 1
 D=$R/gpurun_out/c4pipe; rm -rf $D; mkdir -p $D
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $D -o run -- python3 $R/bench.py --config 4 --steps 20 --warmup 3 --no-cpu-baseline --no-host --no-imix --no-other-mode > $D/bench.json 2> $D/bench.err || { grep -v "^[WIE]20" $D/bench.err | tail -5; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $D -o run -- python3 $R/bench.py --full --config 4 --steps 20 --warmup 3 --no-cpu-baseline --no-host --no-imix --no-other-mode > $D/bench.json 2> $D/bench.err || { grep -v "^[WIE]20" $D/bench.err | tail -5; exit 1; }
 cd $R
 python3 - $D <<'PY'
 import sqlite3, glob, collections, sys, statistics

@@ -8,6 +8,6 @@ X="--no-cpu-baseline --no-host --no-imix --no-other-mode --no-single-launch --ta
 cd /tmp
 for v in unif zipf; do
   Z=""; [ $v = zipf ] && Z="--zipf 1.1"
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/$v" -o run -- python3 "$R/bench.py" --config 4 $Z --steps 20 --warmup 3 $X > "$OUT/$v.json" 2> "$OUT/$v.err" || { echo "$v failed"; tail -5 "$OUT/$v.err"; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/$v" -o run -- python3 "$R/bench.py" --full --config 4 $Z --steps 20 --warmup 3 $X > "$OUT/$v.json" 2> "$OUT/$v.err" || { echo "$v failed"; tail -5 "$OUT/$v.err"; exit 1; }
   echo "== $v done"
 done

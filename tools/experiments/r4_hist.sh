@@ -9,5 +9,5 @@ step tests timeout -k 10 900 python3 -u -m pytest tests/test_gpu_history.py test
 tail -3 "$OUT/tests.log"
 X="--no-cpu-baseline --no-host --no-imix --no-other-mode --no-single-launch"
 cd /tmp
-step zipf timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/zipf" -o run -- python3 "$R/bench.py" --config 4 --zipf 1.1 --c4-sync --table-only --steps 10 --warmup 2 $X > "$OUT/zipf.json" 2> "$OUT/zipf.err"
-step unif timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/unif" -o run -- python3 "$R/bench.py" --config 4 --c4-sync --table-only --steps 10 --warmup 2 $X > "$OUT/unif.json" 2> "$OUT/unif.err"
+step zipf timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/zipf" -o run -- python3 "$R/bench.py" --full --config 4 --zipf 1.1 --c4-sync --table-only --steps 10 --warmup 2 $X > "$OUT/zipf.json" 2> "$OUT/zipf.err"
+step unif timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/unif" -o run -- python3 "$R/bench.py" --full --config 4 --c4-sync --table-only --steps 10 --warmup 2 $X > "$OUT/unif.json" 2> "$OUT/unif.err"

@@ -8,7 +8,7 @@ X="--no-cpu-baseline --no-host --no-imix --no-other-mode --no-single-launch --ta
 cd /tmp
 for v in product ${VARS}; do
   L=""; [ "$v" != product ] && L=$R/flodbadd_amd/build/var_$v.so
-  FB_BENCH_ABLATION=1 FLODBADD_GPU_LIB=$L timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$OUT/$v" -o run -- python3 "$R/bench.py" $X > "$OUT/$v.json" 2> "$OUT/$v.err" || { echo "$v failed"; tail -3 "$OUT/$v.err"; exit 1; }
+  FB_BENCH_ABLATION=1 FLODBADD_GPU_LIB=$L timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$OUT/$v" -o run -- python3 "$R/bench.py" --full $X > "$OUT/$v.json" 2> "$OUT/$v.err" || { echo "$v failed"; tail -3 "$OUT/$v.err"; exit 1; }
   echo "== $v done"
 done
 cd "$R"

@@ -14,7 +14,7 @@ for rep in 1 2; do
   for v in ${VARS:-h0 g768h256 g512h512 g1024h512}; do
     for z in "--zipf 1.1" ""; do
       f=$OUT/pipe_${v}_${rep}${z:+z}.json
-      step pipe env FLODBADD_GPU_LIB=$R/flodbadd_amd/build/var_$v.so timeout -k 10 300 python3 bench.py --config 4 $z --steps 20 --warmup 3 $X > "$f" 2> "$f.err"
+      step pipe env FLODBADD_GPU_LIB=$R/flodbadd_amd/build/var_$v.so timeout -k 10 300 python3 bench.py --full --config 4 $z --steps 20 --warmup 3 $X > "$f" 2> "$f.err"
       python3 -c "import json; d=json.loads(open('$f').readline()); print('$v rep $rep zipf=${z:+1}', d['value'], d['ms_per_step'])"
     done
   done

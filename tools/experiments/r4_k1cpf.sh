@@ -13,7 +13,7 @@ X="--no-cpu-baseline --no-host --no-imix --no-other-mode --no-single-launch --ta
 for v in base new; do
   L=$R/flodbadd_amd/libflodbadd_gpu.so; [ $v = base ] && L=$R/flodbadd_amd/build/var_base.so
   cd /tmp
-  step tr_$v env FB_BENCH_ABLATION=1 FLODBADD_GPU_LIB=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/tr_$v" -o run -- python3 "$R/bench.py" --config 4 --zipf 1.1 --c4-sync --steps 10 --warmup 2 $X > "$OUT/tr_$v.json" 2> "$OUT/tr_$v.err"
+  step tr_$v env FB_BENCH_ABLATION=1 FLODBADD_GPU_LIB=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/tr_$v" -o run -- python3 "$R/bench.py" --full --config 4 --zipf 1.1 --c4-sync --steps 10 --warmup 2 $X > "$OUT/tr_$v.json" 2> "$OUT/tr_$v.err"
   cd "$R"
 done
 for rep in 1 2; do
@@ -21,7 +21,7 @@ for rep in 1 2; do
     L=$R/flodbadd_amd/libflodbadd_gpu.so; [ $v = base ] && L=$R/flodbadd_amd/build/var_base.so
     for z in "--zipf 1.1" ""; do
       f=$OUT/pipe_${v}_${rep}${z:+z}.json
-      step pipe env FB_BENCH_ABLATION=1 FLODBADD_GPU_LIB=$L timeout -k 10 300 python3 bench.py --config 4 $z --steps 20 --warmup 3 $X > "$f" 2> "$f.err"
+      step pipe env FB_BENCH_ABLATION=1 FLODBADD_GPU_LIB=$L timeout -k 10 300 python3 bench.py --full --config 4 $z --steps 20 --warmup 3 $X > "$f" 2> "$f.err"
       python3 -c "import json; d=json.loads(open('$f').readline()); print('$v rep $rep zipf=${z:+1}', d['value'], d['ms_per_step'])"
     done
   done

@@ -9,7 +9,7 @@ for rep in 1 2; do
   for v in product ${VARS:-k1cpar}; do
     L=""; [ "$v" != product ] && L=$R/flodbadd_amd/build/var_$v.so
     for z in "" "--zipf 1.1"; do
-      FLODBADD_GPU_LIB=$L timeout -k 10 200 python3 bench.py $z $X > "$OUT/$v$rep${z:+z}.json" 2> "$OUT/$v$rep${z:+z}.err" || { tail -3 "$OUT/$v$rep${z:+z}.err"; exit 1; }
+      FLODBADD_GPU_LIB=$L timeout -k 10 200 python3 bench.py --full $z $X > "$OUT/$v$rep${z:+z}.json" 2> "$OUT/$v$rep${z:+z}.err" || { tail -3 "$OUT/$v$rep${z:+z}.err"; exit 1; }
       python3 -c "import json; d=json.loads(open('$OUT/$v$rep${z:+z}.json').readline()); print('$v rep $rep zipf=${z:+1}', d['value'], d['ms_per_step'])"
     done
   done

@@ -12,14 +12,14 @@ for rep in 1 2 3; do
   for v in 0 1; do
     for z in "" "--zipf 1.1"; do
       f=$OUT/pipe_k${v}_${rep}${z:+z}.json
-      step pipe env FB_K1_ON_UPD=$v timeout -k 10 300 python3 bench.py --config 4 $z --steps 20 --warmup 3 $X > "$f" 2> "$f.err"
+      step pipe env FB_K1_ON_UPD=$v timeout -k 10 300 python3 bench.py --full --config 4 $z --steps 20 --warmup 3 $X > "$f" 2> "$f.err"
       python3 -c "import json; d=json.loads(open('$f').readline()); print('k1_on_upd=$v rep $rep zipf=${z:+1}', d['value'], d['ms_per_step'])"
     done
   done
 done
 cd /tmp
 for v in 0 1; do
-  step tr_$v env FB_K1_ON_UPD=$v timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/tr_$v" -o run -- python3 "$R/bench.py" --config 4 --steps 10 --warmup 2 $X > "$OUT/tr_$v.json" 2> "$OUT/tr_$v.err"
+  step tr_$v env FB_K1_ON_UPD=$v timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/tr_$v" -o run -- python3 "$R/bench.py" --full --config 4 --steps 10 --warmup 2 $X > "$OUT/tr_$v.json" 2> "$OUT/tr_$v.err"
 done
 cd "$R"
 step tests env FB_K1_ON_UPD=1 timeout -k 10 600 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "async or zipf or hot or history or grow or c4 or combine or pipelined" > "$OUT/tests.log" 2>&1

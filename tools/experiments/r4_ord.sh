@@ -9,10 +9,10 @@ step tests timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -v --timeout 3
 tail -1 "$OUT/gputests.log"
 X="--no-cpu-baseline --no-host --no-imix --no-other-mode --no-single-launch --table-only"
 cd /tmp
-step zipf timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/zipf" -o run -- python3 "$R/bench.py" --config 4 --zipf 1.1 --c4-sync --steps 10 --warmup 2 $X > "$OUT/zipf.json" 2> "$OUT/zipf.err"
-step unif timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/unif" -o run -- python3 "$R/bench.py" --config 4 --c4-sync --steps 10 --warmup 2 $X > "$OUT/unif.json" 2> "$OUT/unif.err"
+step zipf timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/zipf" -o run -- python3 "$R/bench.py" --full --config 4 --zipf 1.1 --c4-sync --steps 10 --warmup 2 $X > "$OUT/zipf.json" 2> "$OUT/zipf.err"
+step unif timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/unif" -o run -- python3 "$R/bench.py" --full --config 4 --c4-sync --steps 10 --warmup 2 $X > "$OUT/unif.json" 2> "$OUT/unif.err"
 cd "$R"
 for z in "" "--zipf 1.1"; do
-  step pipe timeout -k 10 300 python3 bench.py --config 4 $z --steps 20 --warmup 3 $X > "$OUT/pipe${z:+z}.json" 2> "$OUT/pipe${z:+z}.err"
+  step pipe timeout -k 10 300 python3 bench.py --full --config 4 $z --steps 20 --warmup 3 $X > "$OUT/pipe${z:+z}.json" 2> "$OUT/pipe${z:+z}.err"
   python3 -c "import json; d=json.loads(open('$OUT/pipe${z:+z}.json').readline()); print('pipelined zipf=${z:+1}', d['value'], d['ms_per_step'])"
 done

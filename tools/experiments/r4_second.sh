@@ -10,7 +10,7 @@ X="--no-cpu-baseline --no-host --no-imix --no-other-mode --no-single-launch"
 step merge timeout -k 10 300 python3 tools/c5_merge_time.py > "$OUT/c5_merge_time.log" 2>&1
 cat "$OUT/c5_merge_time.log"
 cd /tmp
-step zipf timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/zipf" -o run -- python3 "$R/bench.py" --config 4 --zipf 1.1 --c4-sync --table-only --steps 10 --warmup 2 $X > "$OUT/zipf.json" 2> "$OUT/zipf.err"
-step c4pipe timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/c4pipe" -o run -- python3 "$R/bench.py" --config 4 --table-only --steps 20 --warmup 5 $X > "$OUT/c4pipe.json" 2> "$OUT/c4pipe.err"
-step c4sync timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/c4sync" -o run -- python3 "$R/bench.py" --config 4 --c4-sync --table-only --steps 10 --warmup 2 $X > "$OUT/c4sync.json" 2> "$OUT/c4sync.err"
+step zipf timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/zipf" -o run -- python3 "$R/bench.py" --full --config 4 --zipf 1.1 --c4-sync --table-only --steps 10 --warmup 2 $X > "$OUT/zipf.json" 2> "$OUT/zipf.err"
+step c4pipe timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/c4pipe" -o run -- python3 "$R/bench.py" --full --config 4 --table-only --steps 20 --warmup 5 $X > "$OUT/c4pipe.json" 2> "$OUT/c4pipe.err"
+step c4sync timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/c4sync" -o run -- python3 "$R/bench.py" --full --config 4 --c4-sync --table-only --steps 10 --warmup 2 $X > "$OUT/c4sync.json" 2> "$OUT/c4sync.err"
 du -sh "$OUT"/* >&2

@@ -10,7 +10,7 @@ X="--no-cpu-baseline --no-host --no-imix --no-other-mode --no-single-launch --ta
 for rep in 1 2; do
   for u in 0 1; do
     for z in "" "--zipf 1.1"; do
-      FB_K1_UNITS=$u timeout -k 10 200 python3 bench.py --config 4 $z $X > "$OUT/u$u$rep${z:+z}.json" 2> "$OUT/u$u$rep${z:+z}.err" || { tail -3 "$OUT/u$u$rep${z:+z}.err"; exit 1; }
+      FB_K1_UNITS=$u timeout -k 10 200 python3 bench.py --full --config 4 $z $X > "$OUT/u$u$rep${z:+z}.json" 2> "$OUT/u$u$rep${z:+z}.err" || { tail -3 "$OUT/u$u$rep${z:+z}.err"; exit 1; }
       python3 -c "import json; d=json.loads(open('$OUT/u$u$rep${z:+z}.json').readline()); e=d['extra']; print('units=$u rep=$rep zipf=${z:+1}', d['value'], d['ms_per_step'], 'sync', e['c4_sync']['value'], 'parse', e['c4_stages']['parse_ms'], 'upd', e['c4_stages']['flow_update_ms'])"
     done
   done

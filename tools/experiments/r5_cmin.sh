@@ -26,7 +26,7 @@ for r in 1 2; do
   for v in product ${ABVARS:-cm64 cm96 cm128}; do
     if [ $v = product ]; then L=""; else L="$(pwd)/flodbadd_amd/build/var_$v.so"; fi
     for z in "" "--zipf 1.1"; do
-      FLODBADD_GPU_LIB=$L timeout -k 10 200 python bench.py --config 4 $z --table-only --steps 20 --warmup 4 \
+      FLODBADD_GPU_LIB=$L timeout -k 10 200 python bench.py --full --config 4 $z --table-only --steps 20 --warmup 4 \
         --no-other-mode --no-cpu-baseline --no-host --no-imix --no-queue --no-copy-ref > gpurun_out/cmn.json 2> gpurun_out/cmn.err || { tail gpurun_out/cmn.err; exit 1; }
       python -c "import json;d=json.load(open('gpurun_out/cmn.json'));e=d['extra'];print('$v', '${z:-uniform}', d['value'], e['c4_sync']['value'], e['c4_stages']['flow_update_ms'])"
     done

@@ -13,7 +13,7 @@ X="--no-cpu-baseline --no-imix --no-other-mode --no-host --no-c4 --no-copy-ref -
 for rep in 1 2; do
   for v in product static; do
     L=""; [ "$v" != product ] && L=$R/flodbadd_amd/build/var_$v.so
-    FLODBADD_GPU_LIB=$L timeout -k 10 200 python3 bench.py $X > "$OUT/$v.$rep.json" 2> "$OUT/$v.$rep.err" || { tail -3 "$OUT/$v.$rep.err"; exit 1; }
+    FLODBADD_GPU_LIB=$L timeout -k 10 200 python3 bench.py --full $X > "$OUT/$v.$rep.json" 2> "$OUT/$v.$rep.err" || { tail -3 "$OUT/$v.$rep.err"; exit 1; }
     python3 -c "import json; d=json.loads(open('$OUT/$v.$rep.json').readline()); print('$v', d['value'], d['roofline']['frac'], 'single', d['extra']['single_batch_launch']['value'])"
   done
 done

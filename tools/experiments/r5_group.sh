@@ -11,11 +11,11 @@ fi
 X="--no-cpu-baseline --no-imix --no-other-mode --no-host --no-single-launch --no-queue --no-copy-ref"
 for rep in 1 2; do
   for g in 1 0; do
-    FB_UNIT_GROUP=$g timeout -k 10 300 python3 bench.py $X > "$OUT/c4_g$g.$rep.json" 2> "$OUT/c4_g$g.$rep.err" || { tail -3 "$OUT/c4_g$g.$rep.err"; exit 1; }
+    FB_UNIT_GROUP=$g timeout -k 10 300 python3 bench.py --full $X > "$OUT/c4_g$g.$rep.json" 2> "$OUT/c4_g$g.$rep.err" || { tail -3 "$OUT/c4_g$g.$rep.err"; exit 1; }
     python3 -c "import json; d=json.loads(open('$OUT/c4_g$g.$rep.json').readline()); c=d['extra']['c4']; print('group=$g', 'c4', c['value'], 'sync', c.get('c4_sync',{}).get('value'), 'stages', c.get('stages', c.get('c4_stages')))"
   done
 done
 for g in 1 0; do
-  FB_UNIT_GROUP=$g timeout -k 10 300 python3 bench.py --config 4 --zipf 1.1 --steps 20 --warmup 4 --no-other-mode --no-cpu-baseline > "$OUT/z_g$g.json" 2> "$OUT/z_g$g.err" || { tail -3 "$OUT/z_g$g.err"; exit 1; }
+  FB_UNIT_GROUP=$g timeout -k 10 300 python3 bench.py --full --config 4 --zipf 1.1 --steps 20 --warmup 4 --no-other-mode --no-cpu-baseline > "$OUT/z_g$g.json" 2> "$OUT/z_g$g.err" || { tail -3 "$OUT/z_g$g.err"; exit 1; }
   python3 -c "import json; d=json.loads(open('$OUT/z_g$g.json').readline()); print('zipf group=$g', d['value'], d['extra'].get('c4_sync',{}).get('value'))"
 done

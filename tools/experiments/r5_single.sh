@@ -5,7 +5,7 @@ set -u
 cd "${GRAFT_REPO_ROOT}"
 R=$(pwd); OUT=$R/gpurun_out/r5single; rm -rf "$OUT"; mkdir -p "$OUT"; export TMPDIR=/tmp
 cd /tmp
-timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -- python3 "$R/bench.py" --steps 64 --warmup 16 \
+timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -- python3 "$R/bench.py" --full --steps 64 --warmup 16 \
   --batches-per-launch 1 --no-cpu-baseline --no-imix --no-other-mode --no-host --no-single-launch --no-c4 --no-copy-ref \
   > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail "$OUT/bench.err"; exit 1; }
 tail -c 300 "$OUT/bench.json"

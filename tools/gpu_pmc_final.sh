@@ -6,7 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT}"
 R=$(pwd); OUT=$R/gpurun_out/pmcz; rm -rf "$OUT"; mkdir -p "$OUT"; export TMPDIR=/tmp
 cd /tmp
-B="$R/bench.py --steps 20 --warmup 20 --no-cpu-baseline --no-imix --no-other-mode --no-host --no-single-launch --no-c4 --no-copy-ref"
+B="$R/bench.py --full --steps 20 --warmup 20 --no-cpu-baseline --no-imix --no-other-mode --no-host --no-single-launch --no-c4 --no-copy-ref"
 step() { echo "== $1" >&2; shift; "$@" || { echo "FAILED rc=$?" >&2; exit 1; }; }
 step trace_c2 timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/trace_c2" -o run -- python3 $B > "$OUT/trace_c2.json" 2> "$OUT/trace_c2.err"
 step fetch_c2 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch_c2" -o run -- python3 $B > "$OUT/fetch_c2.json" 2> "$OUT/fetch_c2.err"

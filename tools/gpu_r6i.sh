@@ -7,5 +7,5 @@ timeout -k 10 700 python -u -m pytest tests -m gpu -v --timeout 180 --timeout-me
 tail -3 $OUT/gpu_tests.txt
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 || { tail -20 $OUT/smoke.txt; exit 1; }
 tail -3 $OUT/smoke.txt
-timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 tail -c 300 $OUT/bench.json

@@ -7,5 +7,5 @@ tail -2 "$OUT/tests.log"
 cd /tmp
 timeout -k 10 180 rocprofv3 --kernel-trace --stats -d "$OUT/qt" -o run -- python3 "$R/tools/queue_table_prof.py" 40 > "$OUT/qt.log" 2>&1 || { tail "$OUT/qt.log"; exit 1; }
 grep Mpackets "$OUT/qt.log"
-cd "$R" && timeout -k 10 200 python bench.py --steps 50 --no-cpu-baseline --no-imix --no-other-mode --no-host > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail "$OUT/bench.err"; exit 1; }
+cd "$R" && timeout -k 10 200 python bench.py --full --steps 50 --no-cpu-baseline --no-imix --no-other-mode --no-host > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail "$OUT/bench.err"; exit 1; }
 python -c "import json;d=json.loads(open('$OUT/bench.json').read().splitlines()[-1]);print(d['value'],{k:v.get('value') for k,v in d['extra'].items() if isinstance(v,dict)})"

@@ -7,7 +7,7 @@ timeout -k 10 700 python -u -m pytest tests -m gpu -v --timeout 180 --timeout-me
 tail -3 $OUT/gpu_tests.txt
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 || { tail -20 $OUT/smoke.txt; exit 1; }
 tail -3 $OUT/smoke.txt
-timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 tail -c 300 $OUT/bench.json
 cd /tmp
 timeout -k 10 180 rocprofv3 --kernel-trace -d "$OUT/tasync" -o run -- python3 "$R/tools/c4_small_calls.py" --frames 10485760 --calls 10 --warmup 2 --timed > "$OUT/tasync.log" 2>&1 || exit 1

@@ -6,6 +6,6 @@ set -u
 cd "${GRAFT_REPO_ROOT}"
 R=$(pwd); OUT=$R/gpurun_out/profdrv; rm -rf "$OUT"; mkdir -p "$OUT"; export TMPDIR=/tmp
 cd /tmp
-timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -- python3 "$R/bench.py" --steps 20 --warmup 20 \
+timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -- python3 "$R/bench.py" --full --steps 20 --warmup 20 \
   --no-cpu-baseline --no-imix --no-other-mode --no-host --no-single-launch > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail "$OUT/bench.err"; exit 1; }
 tail -c 400 "$OUT/bench.json"
