@@ -58,6 +58,16 @@ FLOW_TIME_DTYPE = np.dtype([
     ("total_segment_interarrival_ms", "<i8"), ("segment_interarrival_div", "<u4"), ("segment_count", "<u4"),
     ("in_segment", "u1"), ("reserved", "u1", (3,)), ("slot", "<u4")])
 assert FLOW_TIME_DTYPE.itemsize == 64
+# fb_age_params / fb_age_stats (fb_flow_age: update_sessions_status, src/capture.rs:1497-1551) and the
+# per-slot status byte of fb_flow_status_dev (0: never aged since insert = the insert status)
+AGE_PARAMS_DTYPE = np.dtype([("activity_ns", "<u8"), ("current_ns", "<u8"), ("retention_ns", "<u8"),
+                             ("reserved", "<u8")])
+AGE_STATS_FIELDS = ["flows", "active", "added", "activated", "deactivated", "current", "purged", "remaining",
+                    "max_partition"]
+AGE_STATS_DTYPE = np.dtype([(f, "<u8") for f in AGE_STATS_FIELDS] + [("reserved", "<u8", (7,))])
+assert AGE_PARAMS_DTYPE.itemsize == 32 and AGE_STATS_DTYPE.itemsize == 128
+FB_AGE_PURGE = 1
+STATUS_ACTIVE, STATUS_ADDED, STATUS_ACTIVATED, STATUS_DEACTIVATED, STATUS_CURRENT, STATUS_AGED = 1, 2, 4, 8, 16, 128
 FB_SEGMENT_TIMEOUT_MS = 5000
 FB_CFG_TIMED = 2
 FB_QUEUE_SHARED = 1
@@ -254,6 +264,8 @@ GPU_SYMBOLS = [
     ("fb_set_frame_times", _I, [_P, _P]),
     ("fb_flow_export_times_dev", _I, [_P, _P, _U64, _P, _P]),
     ("fb_flow_export_times", _I, [_P, _P, _U64, _PU64, _P]),
+    ("fb_flow_age", _I, [_P, _U64, _P, _U32, _P, _P]),
+    ("fb_flow_status_dev", _I, [_P, _P, _U64, _P]),
 ]
 
 _gpu = None

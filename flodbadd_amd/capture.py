@@ -251,8 +251,9 @@ class FlodbaddGpuCapture:
                     max_partition=t.max_partition)
 
     def _follow_growth(self):
-        """The table grew since the histories were last keyed: move them to the new slots
-        (fb_flow_slot_remap; only the last growth's map is kept, and this runs after every batch)."""
+        """The table grew, or a purge re-packed it, since the histories were last keyed: move them to
+        the new slots (fb_flow_slot_remap; only the last move's map is kept, and this runs after every
+        batch and every purge)."""
         gen = self.table_info()["generation"]
         if gen == self._generation:
             return
@@ -266,7 +267,9 @@ class FlodbaddGpuCapture:
         m = np.zeros(max(old_cap, 1), dtype=np.uint32)
         n = C.c_uint64(0)
         N.check(N.gpu_lib().fb_flow_slot_remap(self.ctx, N.ptr(m), old_cap, C.byref(n)))
-        self.histories = {int(m[k]): v for k, v in self.histories.items()}
+        # a purge (update_sessions_status) maps the flows it removed to 0xFFFFFFFF: their histories go
+        # with them (a growth maps every occupied slot, so nothing is dropped then)
+        self.histories = {int(m[k]): v for k, v in self.histories.items() if int(m[k]) != 0xFFFFFFFF}
 
     def _pull_history(self, n_slots):
         if not self.track_history:
@@ -296,12 +299,58 @@ class FlodbaddGpuCapture:
         N.check(N.gpu_lib().fb_flow_export_times(self.ctx, N.ptr(out), cnt, C.byref(n), None))
         return out[: n.value]
 
-    def get_sessions(self):
+    def status_bytes(self):
+        """fb_flow_status_dev: the status byte of every table slot (index = fb_flow_rec.slot); all
+        zero before the first update_sessions_status."""
+        cap = int(self.table_info()["capacity"])
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        if cap:
+            d = N.DeviceBuffer(cap)
+            N.check(N.gpu_lib().fb_flow_status_dev(self.ctx, d.ptr, cap, None))
+            d.download(out, cap)
+        return out[:cap]
+
+    def update_sessions_status(self, now_ns, purge=True, activity_s=60, current_s=180, retention_s=86400):
+        """update_sessions_status (src/capture.rs:1497-1551) at `now_ns` on the capture timestamps'
+        clock (timed captures): every session's status and current_sessions membership recomputed, and
+        with `purge` the sessions idle for longer than retention_s removed.  Returns the call's
+        counters (fb_age_stats).  A purge that removed sessions moves others to new table slots; the
+        history strings follow (fb_flow_slot_remap), those of removed sessions are dropped."""
+        prm = np.zeros(1, dtype=N.AGE_PARAMS_DTYPE)
+        prm[0]["activity_ns"] = int(round(activity_s * 1e9))
+        prm[0]["current_ns"] = int(round(current_s * 1e9))
+        prm[0]["retention_ns"] = int(round(retention_s * 1e9))
+        st = np.zeros(1, dtype=N.AGE_STATS_DTYPE)
+        N.check(N.gpu_lib().fb_flow_age(self.ctx, int(now_ns), N.ptr(prm), N.FB_AGE_PURGE if purge else 0, N.ptr(st),
+                                        None))
+        if self.track_history:
+            self._follow_growth()
+        return {k: int(st[0][k]) for k in N.AGE_STATS_FIELDS}
+
+    def get_sessions(self, now_ns=None):
         """get_sessions (src/capture.rs:1578-1612): the sessions that pass the CURRENT filter,
         is_local_session! evaluated at query time on the GPU (capture.rs:1603-1608), sorted by the
-        derived Ord of Session (integer counters + derived f64s)."""
+        derived Ord of Session (integer counters + derived f64s).  With now_ns (timed captures) the
+        table is aged first, as the reference does on every query (capture.rs:1581)."""
+        if now_ns is not None:
+            self.update_sessions_status(now_ns)
         return flows_to_sessions(self.export_flows(self.filter), self.histories if self.track_history else None,
-                                 times=self.export_times() if self.timed else None)
+                                 times=self.export_times() if self.timed else None,
+                                 status=self.status_bytes() if self.timed else None)
+
+    def get_current_sessions(self, now_ns=None):
+        """get_current_sessions (src/capture.rs:1624-1670): the members of current_sessions -- activity
+        within the current span at the last aging, or inserted since (src/packets.rs:532) -- that pass
+        the current filter.  With now_ns the table is aged first."""
+        if not self.timed:
+            raise ValueError("current sessions need a timed capture (timed=True)")
+        if now_ns is not None:
+            self.update_sessions_status(now_ns)
+        flows, status = self.export_flows(self.filter), self.status_bytes()
+        b = status[flows["slot"]] if len(flows) else np.zeros(0, dtype=np.uint8)
+        flows = flows[(b == 0) | ((b & N.STATUS_CURRENT) != 0)]
+        return flows_to_sessions(flows, self.histories if self.track_history else None, times=self.export_times(),
+                                 status=status)
 
     # ---- new-session enrichment (src/packets.rs:429-485) -------------------------------------
     def set_asn_tables(self, v4, v6):

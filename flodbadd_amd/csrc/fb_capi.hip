@@ -99,7 +99,7 @@ struct fb_ctx {
     uint64_t upd_seq = 0;           // table updates issued (the mailbox's seq counts them from 1)
     uint64_t grown_seq = 0;         // upd_seq at the last growth (older reports describe the old geometry)
     uint64_t clear_seq = 0;         // upd_seq at the last fb_flow_clear (older reports are void)
-    uint64_t generation = 0;        // growths so far
+    uint64_t generation = 0;        // slot moves: growths and purges
     bool grow = true;               // FB_CFG_FIXED_TABLE clears it
     uint32_t* d_remap = nullptr;    // the last growth's old -> new slot map
     uint4* d_char_call = nullptr;   // [table_cap] first update call of S s H h per slot (the merge's)
@@ -111,7 +111,14 @@ struct fb_ctx {
     void* d_tscratch = nullptr;
     uint64_t tscratch_bytes = 0;
     hipEvent_t ev_tscratch = nullptr;
-    void* d_mscratch = nullptr;     // multi-GPU merge scratch (export owner counts / merge tables)
+    // session aging (fb_flow_age, fb_age.hip): the status plane (allocated by the first aging call), the
+    // call's counters, and the buffer the next purge writes its slot map into (swapped with d_remap
+    // when the purge removed something)
+    uint8_t* d_status = nullptr;               // [table_cap]
+    unsigned long long* d_age_stats = nullptr; // [kAgeStatWords]
+    uint32_t* d_age_remap = nullptr;
+    uint64_t age_remap_n = 0;
+    void* d_mscratch = nullptr;    // multi-GPU merge scratch (export owner counts / merge tables)
     hipEvent_t ev_mscratch = nullptr;  // after the last export / merge that used d_mscratch (either may
                                        // run on any stream: the next use waits for it)
     uint64_t mscratch_bytes = 0;
@@ -536,6 +543,9 @@ int fb_destroy(fb_ctx* c) {
     hipFree(c->d_time);
     hipFree(c->d_tscratch);
     if (c->ev_tscratch) hipEventDestroy(c->ev_tscratch);
+    hipFree(c->d_status);
+    hipFree(c->d_age_stats);
+    hipFree(c->d_age_remap);
     hipFree(c->d_mscratch);
     if (c->ev_mscratch) hipEventDestroy(c->ev_mscratch);
     if (c->h_mbox) hipHostFree(c->h_mbox);
@@ -1373,10 +1383,26 @@ static int grow_table(fb_ctx* c, hipStream_t s, uint32_t k) {
         HIP_TRY(hipMemsetAsync(nw_time, 0, cap * sizeof(FlowTime), s));
         HIP_TRY(launch_time_remap(c->d_time, c->d_remap, c->table_cap, nw_time, s));
     }
+    uint8_t* nw_status = nullptr;
+    if (c->d_status) {  // ... and so do the status bytes of the aging calls so far (fb_age.hip)
+        if (hipMalloc(&nw_status, cap) != hipSuccess) {
+            hipFree(nw);
+            hipFree(nw_cc);
+            hipFree(nw_time);
+            free_new();
+            return set_err(FB_ERR_NOMEM, "grown status plane");
+        }
+        HIP_TRY(hipMemsetAsync(nw_status, 0, cap, s));
+        HIP_TRY(launch_age_remap(c->d_status, c->d_remap, c->table_cap, nw_status, s));
+    }
     HIP_TRY(hipStreamSynchronize(s));
     if (c->timed) {
         hipFree(c->d_time);
         c->d_time = nw_time;
+    }
+    if (nw_status) {
+        hipFree(c->d_status);
+        c->d_status = nw_status;
     }
     hipFree(c->d_table);
     hipFree(c->d_partials);
@@ -1876,6 +1902,102 @@ int fb_flow_export_dev(fb_ctx* c, fb_flow_rec* d_out, uint64_t cap, uint64_t* d_
     return fb_flow_export_sessions_dev(c, FB_FILTER_ALL, d_out, cap, d_n, stream);
 }
 
+// ---- session aging (fb_age.hip) ---------------------------------------------------------------------
+// Synchronous, like a growth: drains the updates in flight, runs k_flow_age over every partition and
+// reads the call's counters back.  A purge that removed flows moved others inside their partitions:
+// its slot map replaces the last growth's, the generation rises, the last update's history is gone,
+// and -- everything being drained -- the host writes the purged table's occupancy into the mailbox, so
+// fb_flow_table_info_get and maybe_grow's projection see the table as it is now.
+int fb_flow_age(fb_ctx* c, uint64_t now_ns, const fb_age_params* params, uint32_t flags, fb_age_stats* out,
+                void* stream) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->timed) return set_err(FB_ERR_INVAL, "the context was created without FB_CFG_TIMED (aging needs the clock)");
+    if (flags & ~FB_AGE_PURGE) return set_err(FB_ERR_INVAL, "unknown flags %u", flags);
+    static const fb_age_params kReference = {60ull * 1000000000ull, 180ull * 1000000000ull, 86400ull * 1000000000ull, 0};
+    const fb_age_params& ap = params ? *params : kReference;  // src/sessions.rs:10-15
+    const bool purge = (flags & FB_AGE_PURGE) != 0u;
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = drain_updates(c);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!c->d_status) {
+        if (hipMalloc(&c->d_status, c->table_cap) != hipSuccess) {
+            c->d_status = nullptr;
+            return set_err(FB_ERR_NOMEM, "status plane");
+        }
+        HIP_TRY(hipMemsetAsync(c->d_status, 0, c->table_cap, s));
+    }
+    if (!c->d_age_stats && hipMalloc(&c->d_age_stats, kAgeStatWords * 8ull) != hipSuccess) {
+        c->d_age_stats = nullptr;
+        return set_err(FB_ERR_NOMEM, "aging counters");
+    }
+    if (purge && c->age_remap_n != c->table_cap) {
+        hipFree(c->d_age_remap);
+        c->d_age_remap = nullptr;
+        c->age_remap_n = 0;
+        if (hipMalloc(&c->d_age_remap, c->table_cap * 4ull) != hipSuccess) {
+            c->d_age_remap = nullptr;
+            return set_err(FB_ERR_NOMEM, "slot remap");
+        }
+        c->age_remap_n = c->table_cap;
+    }
+    HIP_TRY(hipMemsetAsync(c->d_age_stats, 0, kAgeStatWords * 8ull, s));
+    AgeArgs a;
+    a.table = c->d_table;
+    a.plane = c->d_time;
+    a.char_call = c->d_char_call;
+    a.status = c->d_status;
+    a.remap = purge ? c->d_age_remap : nullptr;
+    a.stats = c->d_age_stats;
+    a.now = now_ns;
+    a.activity = ap.activity_ns;
+    a.current = ap.current_ns;
+    a.retention = ap.retention_ns;
+    a.purge = purge ? 1u : 0u;
+    HIP_TRY(launch_flow_age(a, c->flow_parts, s));
+    unsigned long long h[kAgeStatWords] = {};
+    HIP_TRY(hipMemcpyAsync(h, c->d_age_stats, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h[6]) {  // flows were removed: survivors of their partitions may have moved
+        std::swap(c->d_remap, c->d_age_remap);
+        c->age_remap_n = c->d_age_remap ? c->remap_n : 0;  // (the old map's size; reallocated if it differs)
+        c->remap_n = c->table_cap;
+        ++c->generation;
+        c->last_recs = nullptr;  // the last update's slots moved: its history is no longer available
+        c->last_part = nullptr;
+        c->h_mbox->flows = h[7];
+        c->h_mbox->max_part = h[8];
+    }
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        out->flows = h[0];
+        out->active = h[1];
+        out->added = h[2];
+        out->activated = h[3];
+        out->deactivated = h[4];
+        out->current = h[5];
+        out->purged = h[6];
+        out->remaining = h[7];
+        out->max_partition = h[8];
+    }
+    return FB_OK;
+}
+
+int fb_flow_status_dev(fb_ctx* c, uint8_t* d_out, uint64_t cap, void* stream) {
+    if (!c || (cap && !d_out)) return set_err(FB_ERR_INVAL, "bad arguments");
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t m = std::min<uint64_t>(cap, c->table_cap);
+    if (m == 0) return FB_OK;
+    if (c->d_status)
+        HIP_TRY(hipMemcpyAsync(d_out, c->d_status, m, hipMemcpyDeviceToDevice, s));
+    else
+        HIP_TRY(hipMemsetAsync(d_out, 0, m, s));
+    return FB_OK;
+}
+
 // ---- multi-GPU merge (fb_merge.hip) ---------------------------------------------------------------
 // The export and the merge share d_mscratch and may be called on different streams: each use waits
 // on the event the previous use recorded (mscratch_use / mscratch_done), and a reallocation waits for
@@ -2046,6 +2168,7 @@ int fb_flow_clear(fb_ctx* c, void* stream) {
     const int rc = join_updates(c, (hipStream_t)stream);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->d_table, 0, c->table_cap * sizeof(FlowSlot), (hipStream_t)stream));
+    if (c->d_status) HIP_TRY(hipMemsetAsync(c->d_status, 0, c->table_cap, (hipStream_t)stream));
     c->flow_batch = 0;
     c->clear_seq = c->upd_seq;
     c->last_recs = nullptr;

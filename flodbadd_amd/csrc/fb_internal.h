@@ -593,6 +593,28 @@ hipError_t launch_time_remap(const FlowTime* old, const uint32_t* remap, unsigne
 hipError_t launch_time_export(const FlowSlot* table, const FlowTime* plane, unsigned long long cap, fb_flow_time* out,
                               unsigned long long out_cap, unsigned long long* d_n, hipStream_t s);
 
+// Session aging (fb_age.hip, fb_flow_age): the status plane holds one byte per table slot -- the
+// reference's SessionStatus (src/sessions.rs) in bits 0-3, membership of current_sessions in bit 4, and
+// kAgeAged once an aging call has seen the flow (a zero byte: never aged since its insert).
+constexpr uint32_t kAgeActive = 1u, kAgeAdded = 2u, kAgeActivated = 4u, kAgeDeactivated = 8u, kAgeCurrent = 16u,
+                   kAgeAged = 128u;
+// the call's device counters: fb_age_stats' first nine fields, in order (7 summed per workgroup from
+// wave counts, then remaining and max_partition)
+constexpr uint32_t kAgeCounters = 7, kAgeStatWords = 9;
+struct AgeArgs {
+    FlowSlot* table;
+    FlowTime* plane;
+    uint4* char_call;            // moved with the slots of a rebuilt partition
+    uint8_t* status;             // [capacity]
+    uint32_t* remap;             // [capacity] with purge: old slot -> new slot, ~0u empty or removed
+    unsigned long long* stats;   // [kAgeStatWords], zeroed before the launch
+    unsigned long long now, activity, current, retention;  // ns
+    uint32_t purge;
+};
+hipError_t launch_flow_age(const AgeArgs& a, uint32_t parts, hipStream_t s);
+hipError_t launch_age_remap(const uint8_t* old, const uint32_t* remap, unsigned long long old_cap, uint8_t* nw,
+                            hipStream_t s);
+
 // Per-flow history characters of the last update (fb_hist.hip): the update's FlowParams (its
 // entries, transposed original rows, combined-group maps, per-slot counts) and the outputs.
 // cnt: flow_history_cnt_bytes(chunks) of scratch (hot partitions split over chunk blocks), or null

@@ -16,7 +16,7 @@ from typing import List, Optional
 
 from ._native import (CONN_STATES, FB_FILTER_ALL, FB_FILTER_GLOBAL_ONLY, FB_FILTER_LOCAL_ONLY, FB_SEEN_NONE,
                       FLOW_REC_DTYPE, SESSION_DST_SERVICE, SESSION_LOCAL_DST, SESSION_LOCAL_SRC, SESSION_SELF_DST,
-                      SESSION_SELF_SRC,
+                      SESSION_SELF_SRC, STATUS_ACTIVATED, STATUS_ACTIVE, STATUS_ADDED, STATUS_DEACTIVATED,
                       META_DST_SERVICE, META_HAS_FLAGS, META_LOCAL_DST, META_LOCAL_SRC, META_ORIGINATOR,
                       META_SELF_DST, META_SELF_SRC, META_SWAP, PARSED_DTYPE, PKT_OUT_DTYPE)
 
@@ -156,10 +156,29 @@ class SessionStats:
 
 
 @dataclass
+class SessionStatus:
+    """SessionStatus (src/sessions.rs), as update_sessions_status leaves it (src/capture.rs:1514-1528);
+    the defaults are the status a session is inserted with (src/packets.rs:497-502)."""
+    active: bool = True
+    added: bool = True
+    activated: bool = True
+    deactivated: bool = False
+
+    @staticmethod
+    def from_byte(b):
+        """A status byte of fb_flow_status_dev; 0 (never aged since insert) is the insert status."""
+        b = int(b)
+        if b == 0:
+            return SessionStatus()
+        return SessionStatus(bool(b & STATUS_ACTIVE), bool(b & STATUS_ADDED), bool(b & STATUS_ACTIVATED),
+                             bool(b & STATUS_DEACTIVATED))
+
+
+@dataclass
 class SessionInfo:
     """Subset of src/sessions.rs:40-61 that the GPU path owns.  is_local_* / is_self_* and
     dst_service are the values stored when the session was inserted (src/packets.rs:429-466,
-    fb_flow_rec.session_flags)."""
+    fb_flow_rec.session_flags); status is None on an untimed capture (no clock to age by)."""
     session: Session
     stats: SessionStats = field(default_factory=SessionStats)
     is_local_src: bool = False
@@ -167,6 +186,7 @@ class SessionInfo:
     is_self_src: bool = False
     is_self_dst: bool = False
     dst_service: Optional[str] = None
+    status: Optional[SessionStatus] = None
 
 
 _SERVICE_NAMES = None
@@ -271,13 +291,15 @@ def histories_from_records(recs):
     return {k: (h, state.get(k)) for k, h in hist.items()}
 
 
-def flows_to_sessions(flows, histories=None, times=None):
+def flows_to_sessions(flows, histories=None, times=None, status=None):
     """fb_flow_rec records -> SessionInfo list sorted by the derived Ord of Session.  `histories`
     ({table slot: str}, FlodbaddGpuCapture.histories) supplies the history strings; the locality
     flags and dst_service come from fb_flow_rec.session_flags (stored at insert, src/packets.rs:
     429-466; dst_service = the key's dst port name, or its number for a port only a service table
     set at run time names).  `times` (timed contexts): FLOW_TIME_DTYPE records, either joined by
-    table slot (fb_flow_export_times) or, when every slot field is 0, one per flow in `flows` order."""
+    table slot (fb_flow_export_times) or, when every slot field is 0, one per flow in `flows` order.
+    `status` (timed contexts): the status byte of every table slot (fb_flow_status_dev), indexed by
+    fb_flow_rec.slot, decoded into SessionInfo.status; a zero byte gives the insert status."""
     if flows.dtype != FLOW_REC_DTYPE:
         raise TypeError("expected fb_flow_rec records (FLOW_REC_DTYPE), got %s" % flows.dtype)
     tmap = None
@@ -309,6 +331,8 @@ def flows_to_sessions(flows, histories=None, times=None):
         svc = (service_name(s.dst_port) or str(s.dst_port)) if f & SESSION_DST_SERVICE else None
         info = SessionInfo(s, st, bool(f & SESSION_LOCAL_SRC), bool(f & SESSION_LOCAL_DST),
                            bool(f & SESSION_SELF_SRC), bool(f & SESSION_SELF_DST), svc)
+        if status is not None:
+            info.status = SessionStatus.from_byte(status[int(r["slot"])])
         out.append(info)
     out.sort(key=lambda i: i.session.sort_key())
     return out
@@ -324,7 +348,7 @@ def filter_sessions(sessions: List[SessionInfo], flt: SessionFilter, lan_v6=()) 
     return list(sessions)
 
 
-__all__ = ["Protocol", "SessionFilter", "Session", "SessionPacketData", "SessionStats", "SessionInfo",
+__all__ = ["Protocol", "SessionFilter", "Session", "SessionPacketData", "SessionStats", "SessionStatus", "SessionInfo",
            "ip_to_words", "words_to_ip", "service_name", "records_to_packets", "flows_to_sessions", "filter_sessions",
            "packets_to_parsed", "determine_conn_state", "histories_from_records", "is_lan_ip", "is_local_session",
            "META_HAS_FLAGS", "META_SWAP", "META_ORIGINATOR", "META_LOCAL_SRC", "META_LOCAL_DST",

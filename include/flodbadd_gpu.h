@@ -666,15 +666,15 @@ int fb_flow_export_sessions(fb_ctx* ctx, uint32_t filter, fb_flow_rec* out, uint
 int fb_flow_export_sessions_dev(fb_ctx* ctx, uint32_t filter, fb_flow_rec* d_out, uint64_t cap, uint64_t* d_n,
                                 void* stream);
 int fb_flow_clear(fb_ctx* ctx, void* stream); /* clear_all_sessions, src/capture.rs:396 */
-/* Flow-table geometry and growth.  `generation` counts the growths since fb_create: each moves
- * flows to new slots (fb_flow_rec.slot, the history's flow ids), and fb_flow_slot_remap gives the
- * last growth's old -> new slot map (old capacity entries, 0xFFFFFFFF = empty) so a host that keys
- * per-flow state by slot can follow.  flows / max_partition are those the last completed update
- * reported (no device wait).  Synchronous. */
+/* Flow-table geometry and growth.  `generation` counts the slot moves since fb_create -- growths and
+ * purges (fb_flow_age) --: each moves flows to new slots (fb_flow_rec.slot, the history's flow ids),
+ * and fb_flow_slot_remap gives the last move's old -> new slot map (old capacity entries, 0xFFFFFFFF =
+ * empty, or removed by a purge) so a host that keys per-flow state by slot can follow.  flows /
+ * max_partition are those the last completed update (or purge) reported (no device wait).  Synchronous. */
 typedef struct fb_flow_table_info {
     uint64_t capacity;      /* slots */
     uint64_t partitions;    /* of 512 slots */
-    uint64_t generation;    /* growths so far */
+    uint64_t generation;    /* slot moves: growths and purges */
     uint64_t flows;         /* occupied slots after the last completed update */
     uint64_t max_partition; /* fullest partition then */
     uint64_t reserved[3];
@@ -689,6 +689,61 @@ uint64_t fb_flow_hash(const fb_session_key* key);
  * export: the orders differ).  Device form: asynchronous, *d_n = records; host form: synchronous. */
 int fb_flow_export_times_dev(fb_ctx* ctx, fb_flow_time* d_out, uint64_t cap, uint64_t* d_n, void* stream);
 int fb_flow_export_times(fb_ctx* ctx, fb_flow_time* out, uint64_t cap, uint64_t* n, void* stream);
+
+/* ---- session aging (update_sessions_status, src/capture.rs:1497-1551; timed contexts) -----------
+ * The reference ages its session map on every get_sessions / get_current_sessions: it recomputes each
+ * session's SessionStatus {active, added, activated, deactivated} against the wall clock, rebuilds
+ * current_sessions (activity within CONNECTION_CURRENT_TIMEOUT) and removes the sessions whose last
+ * activity is older than CONNECTION_RETENTION_TIMEOUT (src/sessions.rs:10-15: 60 s / 180 s / 86400 s).
+ * fb_flow_age does that over the whole table for a caller-supplied `now_ns` (the clock of the capture
+ * timestamps), with the reference's comparisons (capture.rs:1514-1536) done without wrap-around:
+ *   active  = last_activity + activity_ns >= now      added   = start_time + activity_ns >= now
+ *   current = now < last_activity + current_ns        expired = now > last_activity + retention_ns
+ *   activated = !previous.active && active            deactivated = previous.active && !active
+ * The result is one status byte per table slot (FB_STATUS_* bits; fb_flow_status_dev, joined on
+ * fb_flow_rec.slot).  A zero byte is a flow no aging call has seen since its insert: it has the
+ * reference's insert status (active, added, activated; src/packets.rs:497-502), which is also the
+ * `previous` of its first aging, and is a member of current_sessions (src/packets.rs:532).
+ * With FB_AGE_PURGE the expired flows are removed and the partitions that held them re-packed, which
+ * moves flows to other slots: when stats.purged > 0 the generation (fb_flow_table_info) rises by one,
+ * fb_flow_slot_remap gives this call's old -> new slot map (capacity entries; 0xFFFFFFFF = empty or
+ * removed), the history of the last update is no longer available (fb_flow_history_dev), and the
+ * occupancy fb_flow_table_info_get reports is the purged table's.  When nothing was removed neither the
+ * generation nor the remap changes.  A removed flow that sends again is inserted afresh.
+ * Synchronous: waits for the updates in flight, like a table growth.  FB_ERR_INVAL on a context
+ * without a flow table or without FB_CFG_TIMED (no clock).  `params` NULL = the reference's spans;
+ * `out` may be NULL. */
+typedef struct fb_age_params {
+    uint64_t activity_ns;  /* CONNECTION_ACTIVITY_TIMEOUT  (60 s)    */
+    uint64_t current_ns;   /* CONNECTION_CURRENT_TIMEOUT   (180 s)   */
+    uint64_t retention_ns; /* CONNECTION_RETENTION_TIMEOUT (86400 s) */
+    uint64_t reserved;     /* 0 */
+} fb_age_params;
+typedef struct fb_age_stats {
+    uint64_t flows;         /* flows in the table when the call started                       */
+    uint64_t active;        /* of those: status.active, ...                                   */
+    uint64_t added;
+    uint64_t activated;
+    uint64_t deactivated;
+    uint64_t current;       /* members of current_sessions                                    */
+    uint64_t purged;        /* flows removed (0 without FB_AGE_PURGE)                         */
+    uint64_t remaining;     /* flows - purged                                                 */
+    uint64_t max_partition; /* fullest partition after the call (slots of 512)                */
+    uint64_t reserved[7];
+} fb_age_stats; /* 128 bytes */
+#define FB_AGE_PURGE 1u
+/* fb_flow_status_dev bytes */
+#define FB_STATUS_ACTIVE 1u
+#define FB_STATUS_ADDED 2u
+#define FB_STATUS_ACTIVATED 4u
+#define FB_STATUS_DEACTIVATED 8u
+#define FB_STATUS_CURRENT 16u
+#define FB_STATUS_AGED 128u
+int fb_flow_age(fb_ctx* ctx, uint64_t now_ns, const fb_age_params* params, uint32_t flags, fb_age_stats* out,
+                void* stream);
+/* The status byte of every table slot (min(cap, capacity) bytes, slot order; all zero before the first
+ * fb_flow_age) into DEVICE memory.  Asynchronous. */
+int fb_flow_status_dev(fb_ctx* ctx, uint8_t* d_out, uint64_t cap, void* stream);
 
 /* ---- multi-GPU session table (BASELINE configs[4]) ------------------------------
  * The reference runs one capture task per interface into ONE shared DashMap (src/capture.rs:946-1016,
