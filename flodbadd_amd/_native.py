@@ -68,6 +68,20 @@ AGE_STATS_DTYPE = np.dtype([(f, "<u8") for f in AGE_STATS_FIELDS] + [("reserved"
 assert AGE_PARAMS_DTYPE.itemsize == 32 and AGE_STATS_DTYPE.itemsize == 128
 FB_AGE_PURGE = 1
 STATUS_ACTIVE, STATUS_ADDED, STATUS_ACTIVATED, STATUS_DEACTIVATED, STATUS_CURRENT, STATUS_AGED = 1, 2, 4, 8, 16, 128
+# fb_wl_endpoint / fb_wl_stats (fb_set_whitelist, fb_flow_whitelist: recompute_whitelist_for_sessions,
+# src/whitelists.rs:810-1023) and the per-slot state byte of fb_flow_whitelist_dev (0: Unknown)
+WL_ENDPOINT_DTYPE = np.dtype([("addr", "<u4", (4,)), ("family", "u1"), ("prefix", "u1"), ("protocol", "u1"),
+                              ("flags", "u1"), ("port", "<u2"), ("reserved", "<u2"), ("as_number", "<u4"),
+                              ("owner_id", "<u4"), ("country_id", "<u4"), ("reserved2", "<u4")])
+WL_STATS_FIELDS = ["flows", "conforming", "nonconforming", "host_check", "changed"]
+WL_STATS_DTYPE = np.dtype([(f, "<u8") for f in WL_STATS_FIELDS] + [("reserved", "<u8", (3,))])
+assert WL_ENDPOINT_DTYPE.itemsize == 40 and WL_STATS_DTYPE.itemsize == 64
+FB_WL_NEVER = 0xFF
+FB_WL_HAS_PORT, FB_WL_HAS_ASN, FB_WL_HAS_OWNER, FB_WL_HAS_COUNTRY, FB_WL_HAS_DOMAIN, FB_WL_HAS_PROCESS = 1, 2, 4, 8, 16, 32
+FB_WL_CONFORMING, FB_WL_NONCONFORMING, FB_WL_HOST_CHECK, FB_WL_MASK_UNKNOWN = 1, 2, 4, 128
+FB_WL_MAX_EXACT, FB_WL_MAX_OTHER = 1 << 24, 1 << 16
+# the kernel's staging thresholds (fb_internal.h: kWlLdsRules, kWlLdsGroups), for the tests at them
+WL_LDS_RULES, WL_LDS_GROUPS = 512, 512
 FB_SEGMENT_TIMEOUT_MS = 5000
 FB_CFG_TIMED = 2
 FB_QUEUE_SHARED = 1
@@ -266,6 +280,11 @@ GPU_SYMBOLS = [
     ("fb_flow_export_times", _I, [_P, _P, _U64, _PU64, _P]),
     ("fb_flow_age", _I, [_P, _U64, _P, _U32, _P, _P]),
     ("fb_flow_status_dev", _I, [_P, _P, _U64, _P]),
+    ("fb_set_whitelist", _I, [_P, _P, _U64, _P, _P, _U32]),
+    ("fb_clear_whitelist", _I, [_P]),
+    ("fb_flow_whitelist", _I, [_P, _U32, _P, _P]),
+    ("fb_flow_whitelist_dev", _I, [_P, _P, _U64, _P]),
+    ("fb_flow_export_whitelist_dev", _I, [_P, _U32, _P, _U64, _P, _P]),
 ]
 
 _gpu = None

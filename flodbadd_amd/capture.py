@@ -15,7 +15,8 @@ import ipaddress
 import numpy as np
 
 from . import _native as N
-from .sessions import SessionFilter, flows_to_sessions, ip_to_words
+from .sessions import Session, SessionFilter, WhitelistState, flows_to_sessions, ip_to_words, is_lan_ip
+from .whitelists import Whitelists, is_session_in_whitelist, no_match_reason
 
 
 def lan_v6_table(prefixes):
@@ -90,6 +91,16 @@ class FlodbaddGpuCapture:
         self.track_history = bool(track_history) and flow_capacity > 0
         self.histories = {}
         self._generation = 0  # table growths seen (slots move when the table grows)
+        # whitelist conformance (src/capture.rs:101-106: no list active, conformance true, no exceptions)
+        self._lan_v6 = list(lan_v6)
+        self._asn_records = []
+        self._whitelists = Whitelists()
+        self._wl_name = ""
+        self._wl_installed = None   # (CompiledWhitelist, dns_resolutions) the device holds, or None
+        self._wl_inputs = (None, None)  # the last update's dns_resolutions / process_names
+        self._wl_host_ok = set()    # the Sessions the host resolved to Conforming (process names)
+        self._wl_conformance = True
+        self._wl_exceptions = np.zeros(0, dtype=N.FLOW_REC_DTYPE)
 
     # ---- configuration -------------------------------------------------------------------
     def set_filter(self, flt):
@@ -106,8 +117,10 @@ class FlodbaddGpuCapture:
         N.check(N.gpu_lib().fb_set_service_bitmap(self.ctx, N.ptr(bm)))
 
     def set_lan_v6(self, prefixes):
-        t = lan_v6_table(list(prefixes))
+        prefixes = list(prefixes)
+        t = lan_v6_table(prefixes)
         N.check(N.gpu_lib().fb_set_lan_v6(self.ctx, N.ptr(t) if len(t) else None, len(t)))
+        self._lan_v6 = prefixes
 
     def set_own_ips(self, ips):
         t = own_ip_table(list(ips))
@@ -334,9 +347,14 @@ class FlodbaddGpuCapture:
         table is aged first, as the reference does on every query (capture.rs:1581)."""
         if now_ns is not None:
             self.update_sessions_status(now_ns)
-        return flows_to_sessions(self.export_flows(self.filter), self.histories if self.track_history else None,
-                                 times=self.export_times() if self.timed else None,
-                                 status=self.status_bytes() if self.timed else None)
+        out = flows_to_sessions(self.export_flows(self.filter), self.histories if self.track_history else None,
+                                times=self.export_times() if self.timed else None,
+                                status=self.status_bytes() if self.timed else None,
+                                whitelist=self.whitelist_bytes() if self._wl_name else None)
+        for info in out if self._wl_host_ok else ():  # the host's verdict for the flows the pass left to it
+            if info.session in self._wl_host_ok and info.is_whitelisted is WhitelistState.NonConforming:
+                info.is_whitelisted = WhitelistState.Conforming
+        return out
 
     def get_current_sessions(self, now_ns=None):
         """get_current_sessions (src/capture.rs:1624-1670): the members of current_sessions -- activity
@@ -353,12 +371,16 @@ class FlodbaddGpuCapture:
                                  status=status)
 
     # ---- new-session enrichment (src/packets.rs:429-485) -------------------------------------
-    def set_asn_tables(self, v4, v6):
-        """ASN_RANGE_DTYPE tables (flodbadd_amd.enrich.asn_tables_from_tsv) -> fb_set_asn_tables."""
+    def set_asn_tables(self, v4, v6, records=None):
+        """ASN_RANGE_DTYPE tables (flodbadd_amd.enrich.asn_tables_from_tsv) -> fb_set_asn_tables.
+        records: that function's third result, the (as_number, country, owner) of every
+        fb_asn_range.record -- what the whitelist pass needs for an endpoint's as_owner / as_country."""
         v4 = np.ascontiguousarray(v4, dtype=N.ASN_RANGE_DTYPE)
         v6 = np.ascontiguousarray(v6, dtype=N.ASN_RANGE_DTYPE)
         N.check(N.gpu_lib().fb_set_asn_tables(self.ctx, N.ptr(v4) if len(v4) else None, len(v4),
                                               N.ptr(v6) if len(v6) else None, len(v6)))
+        self._asn_records = list(records) if records is not None else []
+        self._wl_installed = None  # the interned record ids belong to the installed list
 
     def set_blacklists(self, cidrs):
         """CIDR_DTYPE ranges (flodbadd_amd.enrich.blacklists_from_json) -> fb_set_blacklists."""
@@ -385,11 +407,163 @@ class FlodbaddGpuCapture:
         m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
         return d_out.download(np.zeros(cap, dtype=N.FLOW_ENRICH_DTYPE))[:m]
 
+    # ---- whitelist conformance (src/whitelists.rs:810-1023, src/capture.rs:131-183, 463-531) ---
+    def set_custom_whitelists(self, whitelist_json):
+        """set_custom_whitelists (src/capture.rs:463-509): a WhitelistsJSON document (str or dict)
+        becomes the model and "custom_whitelist" the active list; an empty one clears the model (and
+        the name, if it was the custom list).  The states are reset and one pass runs; returns its
+        counters (None without an active list)."""
+        if not whitelist_json:
+            self._whitelists = Whitelists()
+            if self._wl_name == "custom_whitelist":
+                self._wl_name = ""
+        else:
+            try:
+                self._whitelists = Whitelists(whitelist_json)
+                self._wl_name = "custom_whitelist"
+            except (ValueError, TypeError, KeyError):
+                self._wl_name = ""  # "Error setting custom whitelists" (capture.rs:501-506)
+        self.reset_whitelist()
+        return self.update_whitelist()
+
+    def set_whitelist(self, name):
+        """set_whitelist (src/capture.rs:151-179).  There are no built-in lists: a name other than ""
+        must be a list of the model set_custom_whitelists loaded."""
+        if name and name not in self._whitelists.whitelists:
+            raise ValueError("Invalid whitelist name: %s" % name)
+        self._wl_name = name
+        self.reset_whitelist()
+        return self.update_whitelist()
+
+    def get_whitelist_name(self):
+        return self._wl_name
+
+    def reset_whitelist(self):
+        """reset_whitelist (src/capture.rs:131-149): conformance true, no exceptions, every session
+        Unknown (fb_clear_whitelist; the next update installs the list again)."""
+        N.check(N.gpu_lib().fb_clear_whitelist(self.ctx))
+        self._wl_installed = None
+        self._wl_host_ok = set()
+        self._wl_conformance = True
+        self._wl_exceptions = np.zeros(0, dtype=N.FLOW_REC_DTYPE)
+
+    def whitelist_bytes(self):
+        """fb_flow_whitelist_dev: the whitelist state byte of every table slot (index = fb_flow_rec.slot)."""
+        cap = int(self.table_info()["capacity"])
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        if cap:
+            d = N.DeviceBuffer(cap)
+            N.check(N.gpu_lib().fb_flow_whitelist_dev(self.ctx, d.ptr, cap, None))
+            d.download(out, cap)
+        return out[:cap]
+
+    def export_whitelist_flows(self, state_mask):
+        """fb_flow_export_whitelist_dev: the flows whose state byte has a bit of state_mask, slot order."""
+        cap = max(self.flow_count(), 1)
+        d_out, d_n = N.DeviceBuffer(cap * N.FLOW_REC_DTYPE.itemsize), N.DeviceBuffer(8)
+        N.check(N.gpu_lib().fb_flow_export_whitelist_dev(self.ctx, int(state_mask), d_out.ptr, cap, d_n.ptr, None))
+        m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
+        return d_out.download(np.zeros(cap, dtype=N.FLOW_REC_DTYPE))[:m]
+
+    def install_whitelist(self, compiled):
+        """fb_set_whitelist with a CompiledWhitelist (or bare WL_ENDPOINT_DTYPE rows)."""
+        rows = np.ascontiguousarray(getattr(compiled, "rows", compiled), dtype=N.WL_ENDPOINT_DTYPE)
+        own = np.ascontiguousarray(getattr(compiled, "rec_owner_id", np.zeros(0)), dtype=np.uint32)
+        cty = np.ascontiguousarray(getattr(compiled, "rec_country_id", np.zeros(0)), dtype=np.uint32)
+        N.check(N.gpu_lib().fb_set_whitelist(self.ctx, N.ptr(rows) if len(rows) else None, len(rows),
+                                             N.ptr(own) if len(own) else None, N.ptr(cty) if len(own) else None,
+                                             len(own)))
+
+    def whitelist_pass(self):
+        """fb_flow_whitelist: one pass over the table -> the call's counters (fb_wl_stats)."""
+        st = np.zeros(1, dtype=N.WL_STATS_DTYPE)
+        N.check(N.gpu_lib().fb_flow_whitelist(self.ctx, 0, N.ptr(st), None))
+        return {k: int(st[0][k]) for k in N.WL_STATS_FIELDS}
+
+    def _dst_asn(self, flows):
+        """SessionInfo.dst_asn of flow records (src/packets.rs:468-485): Db::lookup of the destination
+        on the GPU unless it is a LAN address -> [(as_number, country, owner) or None]."""
+        ips = [Session.from_key(r).dst_ip for r in flows]
+        rec = self.ip_lookup(ips)[0] if ips else []
+        return [None if (int(k) < 0 or int(k) >= len(self._asn_records) or is_lan_ip(ip, self._lan_v6))
+                else self._asn_records[int(k)] for ip, k in zip(ips, rec)]
+
+    def update_whitelist(self, dns_resolutions=None, process_names=None):
+        """recompute_whitelist_for_sessions (src/whitelists.rs:810-1023) for every session: nothing
+        happens without an active list (whitelists.rs:840-845); otherwise the active list -- with the
+        domains of dns_resolutions {ip: domain} expanded to addresses -- is installed if it is not yet
+        and the table is evaluated in one pass.  process_names {Session: process name}: the flows the
+        pass marks for a host check are then decided by the full endpoint_matches with their domain
+        and process.  Returns the pass's counters, or None."""
+        self._wl_inputs = (dns_resolutions, process_names)
+        if not self._wl_name:
+            return None
+        want = dict(dns_resolutions or {})
+        if self._wl_installed is None or self._wl_installed[1] != want:
+            comp = self._whitelists.compile(self._wl_name, self._asn_records, want)
+            self.install_whitelist(comp)
+            self._wl_installed = (comp, want)
+        comp = self._wl_installed[0]
+        stats = self.whitelist_pass()
+        self._wl_host_ok = set()
+        if process_names and stats["host_check"]:
+            marked = self.export_whitelist_flows(N.FB_WL_HOST_CHECK)
+            for r, asn in zip(marked, self._dst_asn(marked)):
+                s = Session.from_key(r)
+                a = asn or (None, None, None)
+                if is_session_in_whitelist(comp.endpoints, comp.name, want.get(str(s.dst_ip)), str(s.dst_ip), s.dst_port,
+                                           s.protocol.name, a[0], a[1], a[2], process_names.get(s))[0]:
+                    self._wl_host_ok.add(s)
+        exc = self.export_whitelist_flows(N.FB_WL_NONCONFORMING)
+        if self._wl_host_ok and len(exc):
+            exc = exc[np.array([Session.from_key(r) not in self._wl_host_ok for r in exc], dtype=bool)]
+        self._wl_exceptions = exc
+        self._wl_conformance = len(exc) == 0
+        return stats
+
+    def get_whitelist_conformance(self):
+        """get_whitelist_conformance (src/capture.rs:1672-1678): after an update, no exception exists."""
+        self.update_whitelist(*self._wl_inputs)
+        return self._wl_conformance
+
+    def get_whitelist_exceptions(self):
+        """get_whitelist_exceptions(false) (src/capture.rs:1721-1760): the NonConforming sessions as
+        SessionInfo, sorted by Session as new_exceptions.sort() leaves the keys (whitelists.rs:951),
+        each with the reference's whitelist_reason."""
+        self.update_whitelist(*self._wl_inputs)
+        exc = self._wl_exceptions
+        if not len(exc):
+            return []
+        dns, proc = self._wl_inputs[0] or {}, self._wl_inputs[1] or {}
+        comp = self._wl_installed[0]
+        reasons = {}
+        for r, asn in zip(exc, self._dst_asn(exc)):
+            s = Session.from_key(r)
+            a = asn or (None, None, None)
+            # (an exception is a session no endpoint matched: the reason needs no second scan of the list)
+            reasons[s] = no_match_reason(comp.endpoints, comp.name, dns.get(str(s.dst_ip)), str(s.dst_ip), s.dst_port,
+                                         s.protocol.name, a[0], a[1], a[2], proc.get(s))
+        out = flows_to_sessions(exc, self.histories if self.track_history else None,
+                                times=self.export_times() if self.timed else None,
+                                status=self.status_bytes() if self.timed else None)
+        for info in out:
+            info.is_whitelisted = WhitelistState.NonConforming
+            info.whitelist_reason = reasons[info.session]
+        return out
+
+    def create_custom_whitelists(self, dns_resolutions=None, process_names=None):
+        """create_custom_whitelists (src/capture.rs:511-531): the WhitelistsJSON text of a list learned
+        from every session of the table."""
+        sessions = flows_to_sessions(self.export_flows(SessionFilter.All))
+        return Whitelists.new_from_sessions(sessions, dns_resolutions, process_names).to_json()
+
     def clear_all_sessions(self):
         """src/capture.rs:396 (`stop()` clears the table, capture.rs:383)."""
         N.check(N.gpu_lib().fb_flow_clear(self.ctx, None))
         N.check(N.gpu_lib().fb_stream_sync(None))
         self.histories = {}
+        self._wl_host_ok = set()
+        self._wl_exceptions = np.zeros(0, dtype=N.FLOW_REC_DTYPE)
 
     def close(self):
         if getattr(self, "ctx", None):

@@ -118,7 +118,17 @@ struct fb_ctx {
     unsigned long long* d_age_stats = nullptr; // [kAgeStatWords]
     uint32_t* d_age_remap = nullptr;
     uint64_t age_remap_n = 0;
-    void* d_mscratch = nullptr;    // multi-GPU merge scratch (export owner counts / merge tables)
+    // whitelist conformance (fb_set_whitelist / fb_flow_whitelist, fb_whitelist.hip): the installed
+    // list's index, the state plane (allocated by the first pass) and the pass's counters
+    bool wl_active = false;
+    uint32_t *d_wl_a4 = nullptr, *d_wl_k4 = nullptr, *d_wl_k6 = nullptr, *d_wl_gkey = nullptr, *d_wl_gbeg = nullptr;
+    uint4* d_wl_a6 = nullptr;
+    WlRule* d_wl_rules = nullptr;
+    uint32_t *d_wl_owner = nullptr, *d_wl_country = nullptr;
+    uint32_t wl_n4 = 0, wl_n6 = 0, wl_ng = 0, wl_nr = 0, wl_records = 0;
+    uint8_t* d_wl_state = nullptr;             // [table_cap]
+    unsigned long long* d_wl_stats = nullptr;  // [kWlCounters]
+    void* d_mscratch = nullptr;   // multi-GPU merge scratch (export owner counts / merge tables)
     hipEvent_t ev_mscratch = nullptr;  // after the last export / merge that used d_mscratch (either may
                                        // run on any stream: the next use waits for it)
     uint64_t mscratch_bytes = 0;
@@ -546,6 +556,17 @@ int fb_destroy(fb_ctx* c) {
     hipFree(c->d_status);
     hipFree(c->d_age_stats);
     hipFree(c->d_age_remap);
+    hipFree(c->d_wl_a4);
+    hipFree(c->d_wl_k4);
+    hipFree(c->d_wl_a6);
+    hipFree(c->d_wl_k6);
+    hipFree(c->d_wl_gkey);
+    hipFree(c->d_wl_gbeg);
+    hipFree(c->d_wl_rules);
+    hipFree(c->d_wl_owner);
+    hipFree(c->d_wl_country);
+    hipFree(c->d_wl_state);
+    hipFree(c->d_wl_stats);
     hipFree(c->d_mscratch);
     if (c->ev_mscratch) hipEventDestroy(c->ev_mscratch);
     if (c->h_mbox) hipHostFree(c->h_mbox);
@@ -1395,7 +1416,24 @@ static int grow_table(fb_ctx* c, hipStream_t s, uint32_t k) {
         HIP_TRY(hipMemsetAsync(nw_status, 0, cap, s));
         HIP_TRY(launch_age_remap(c->d_status, c->d_remap, c->table_cap, nw_status, s));
     }
+    uint8_t* nw_wl = nullptr;
+    if (c->d_wl_state) {  // ... and the whitelist states (fb_whitelist.hip): the same byte remap
+        if (hipMalloc(&nw_wl, cap) != hipSuccess) {
+            hipFree(nw);
+            hipFree(nw_cc);
+            hipFree(nw_time);
+            hipFree(nw_status);
+            free_new();
+            return set_err(FB_ERR_NOMEM, "grown whitelist plane");
+        }
+        HIP_TRY(hipMemsetAsync(nw_wl, 0, cap, s));
+        HIP_TRY(launch_age_remap(c->d_wl_state, c->d_remap, c->table_cap, nw_wl, s));
+    }
     HIP_TRY(hipStreamSynchronize(s));
+    if (nw_wl) {
+        hipFree(c->d_wl_state);
+        c->d_wl_state = nw_wl;
+    }
     if (c->timed) {
         hipFree(c->d_time);
         c->d_time = nw_time;
@@ -1969,6 +2007,21 @@ int fb_flow_age(fb_ctx* c, uint64_t now_ns, const fb_age_params* params, uint32_
         c->last_part = nullptr;
         c->h_mbox->flows = h[7];
         c->h_mbox->max_part = h[8];
+        if (c->d_wl_state) {  // the whitelist states follow their flows through the published slot map
+            // (on a failure the plane is dropped -- every flow Unknown again -- rather than left behind
+            // its flows)
+            uint8_t* nw_wl = nullptr;
+            hipError_t e = hipMalloc(&nw_wl, c->table_cap);
+            if (e == hipSuccess) e = hipMemsetAsync(nw_wl, 0, c->table_cap, s);
+            if (e == hipSuccess) e = launch_age_remap(c->d_wl_state, c->d_remap, c->table_cap, nw_wl, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            hipFree(c->d_wl_state);
+            c->d_wl_state = e == hipSuccess ? nw_wl : nullptr;
+            if (e != hipSuccess) {
+                hipFree(nw_wl);
+                return set_err(FB_ERR_HIP, "whitelist plane remap: %s", hipGetErrorString(e));
+            }
+        }
     }
     if (out) {
         memset(out, 0, sizeof(*out));
@@ -1995,6 +2048,134 @@ int fb_flow_status_dev(fb_ctx* c, uint8_t* d_out, uint64_t cap, void* stream) {
         HIP_TRY(hipMemcpyAsync(d_out, c->d_status, m, hipMemcpyDeviceToDevice, s));
     else
         HIP_TRY(hipMemsetAsync(d_out, 0, m, s));
+    return FB_OK;
+}
+
+// ---- whitelist conformance (fb_whitelist.hip) -----------------------------------------------------
+// The list is validated and indexed on the host first (build_whitelist_index), so a refused list
+// leaves the installed one untouched; then the old arrays are replaced (no launch may still read them).
+int fb_set_whitelist(fb_ctx* c, const fb_wl_endpoint* eps, uint64_t n, const uint32_t* rec_owner_id,
+                     const uint32_t* rec_country_id, uint32_t n_records) {
+    if (!c || (n && !eps) || (n_records && (!rec_owner_id || !rec_country_id)))
+        return set_err(FB_ERR_INVAL, "bad arguments");
+    if (n > (uint64_t)FB_WL_MAX_EXACT + FB_WL_MAX_OTHER)
+        return set_err(FB_ERR_INVAL, "%llu endpoints: more than FB_WL_MAX_EXACT + FB_WL_MAX_OTHER", (unsigned long long)n);
+    WlIndex ix;
+    if (!build_whitelist_index(eps, n, ix))
+        return set_err(FB_ERR_INVAL, "whitelist endpoint with a bad family, prefix, protocol or flags, or more than "
+                       "%u exact-address / %u other endpoints", FB_WL_MAX_EXACT, FB_WL_MAX_OTHER);
+    DeviceGuard g(c->device);
+    HIP_TRY(hipDeviceSynchronize());
+    c->wl_active = false;
+    int rc = upload_array(&c->d_wl_a4, ix.a4.data(), ix.a4.size());
+    if (!rc) rc = upload_array(&c->d_wl_k4, ix.k4.data(), ix.k4.size());
+    if (!rc) rc = upload_array(&c->d_wl_a6, ix.a6.data(), ix.a6.size());
+    if (!rc) rc = upload_array(&c->d_wl_k6, ix.k6.data(), ix.k6.size());
+    if (!rc) rc = upload_array(&c->d_wl_gkey, ix.gkey.data(), ix.gkey.size());
+    if (!rc) rc = upload_array(&c->d_wl_gbeg, ix.gbeg.data(), ix.gkey.empty() ? 0 : ix.gbeg.size());
+    if (!rc) rc = upload_array(&c->d_wl_rules, ix.rules.data(), ix.rules.size());
+    if (!rc) rc = upload_array(&c->d_wl_owner, rec_owner_id, n_records);
+    if (!rc) rc = upload_array(&c->d_wl_country, rec_country_id, n_records);
+    if (rc) return rc;
+    c->wl_n4 = (uint32_t)ix.a4.size();
+    c->wl_n6 = (uint32_t)ix.a6.size();
+    c->wl_ng = (uint32_t)ix.gkey.size();
+    c->wl_nr = (uint32_t)ix.rules.size();
+    c->wl_records = n_records;
+    c->wl_active = true;
+    return FB_OK;
+}
+
+int fb_clear_whitelist(fb_ctx* c) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    DeviceGuard g(c->device);
+    HIP_TRY(hipDeviceSynchronize());
+    c->wl_active = false;
+    if (c->d_wl_state) HIP_TRY(hipMemset(c->d_wl_state, 0, c->table_cap));  // every state back to Unknown
+    return FB_OK;
+}
+
+// Synchronous, like fb_flow_age: drains the updates in flight, one pass, the counters read back.
+int fb_flow_whitelist(fb_ctx* c, uint32_t flags, fb_wl_stats* out, void* stream) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->wl_active) return set_err(FB_ERR_INVAL, "no whitelist is installed (fb_set_whitelist)");
+    if (flags) return set_err(FB_ERR_INVAL, "unknown flags %u", flags);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = drain_updates(c);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    rc = upload_cfg(c, s);  // the LAN configuration as of now
+    if (rc) return rc;
+    if (!c->d_wl_state) {
+        if (hipMalloc(&c->d_wl_state, c->table_cap) != hipSuccess) {
+            c->d_wl_state = nullptr;
+            return set_err(FB_ERR_NOMEM, "whitelist plane");
+        }
+        HIP_TRY(hipMemsetAsync(c->d_wl_state, 0, c->table_cap, s));
+    }
+    if (!c->d_wl_stats && hipMalloc(&c->d_wl_stats, kWlCounters * 8ull) != hipSuccess) {
+        c->d_wl_stats = nullptr;
+        return set_err(FB_ERR_NOMEM, "whitelist counters");
+    }
+    HIP_TRY(hipMemsetAsync(c->d_wl_stats, 0, kWlCounters * 8ull, s));
+    WlTables w;
+    w.a4 = c->d_wl_a4;
+    w.k4 = c->d_wl_k4;
+    w.a6 = c->d_wl_a6;
+    w.k6 = c->d_wl_k6;
+    w.gkey = c->d_wl_gkey;
+    w.gbeg = c->d_wl_gbeg;
+    w.rules = c->d_wl_rules;
+    w.rec_owner = c->d_wl_owner;
+    w.rec_country = c->d_wl_country;
+    w.n4 = c->wl_n4;
+    w.n6 = c->wl_n6;
+    w.ng = c->wl_ng;
+    w.nr = c->wl_nr;
+    w.n_records = c->wl_records;
+    HIP_TRY(launch_flow_whitelist(w, enrich_tables(c), c->d_cfg, c->d_table, c->table_cap, c->d_wl_state, c->d_wl_stats, s));
+    unsigned long long h[kWlCounters] = {};
+    HIP_TRY(hipMemcpyAsync(h, c->d_wl_stats, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        out->flows = h[0];
+        out->conforming = h[1];
+        out->nonconforming = h[2];
+        out->host_check = h[3];
+        out->changed = h[4];
+    }
+    return FB_OK;
+}
+
+int fb_flow_whitelist_dev(fb_ctx* c, uint8_t* d_out, uint64_t cap, void* stream) {
+    if (!c || (cap && !d_out)) return set_err(FB_ERR_INVAL, "bad arguments");
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t m = std::min<uint64_t>(cap, c->table_cap);
+    if (m == 0) return FB_OK;
+    if (c->d_wl_state)
+        HIP_TRY(hipMemcpyAsync(d_out, c->d_wl_state, m, hipMemcpyDeviceToDevice, s));
+    else
+        HIP_TRY(hipMemsetAsync(d_out, 0, m, s));
+    return FB_OK;
+}
+
+int fb_flow_export_whitelist_dev(fb_ctx* c, uint32_t state_mask, fb_flow_rec* d_out, uint64_t cap, uint64_t* d_n,
+                                 void* stream) {
+    if (!c || !d_n || (cap && !d_out)) return set_err(FB_ERR_INVAL, "bad arguments");
+    if (state_mask & ~(FB_WL_CONFORMING | FB_WL_NONCONFORMING | FB_WL_HOST_CHECK | FB_WL_MASK_UNKNOWN))
+        return set_err(FB_ERR_INVAL, "unknown state_mask bits %u", state_mask);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
+    if (!c->d_table) return FB_OK;
+    const int rc = join_updates(c, s);
+    if (rc) return rc;
+    HIP_TRY(launch_flow_export_whitelist(c->d_table, c->d_wl_state, c->table_cap, state_mask, d_out, cap,
+                                         (unsigned long long*)d_n, c->d_time, s));
     return FB_OK;
 }
 
@@ -2169,6 +2350,7 @@ int fb_flow_clear(fb_ctx* c, void* stream) {
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->d_table, 0, c->table_cap * sizeof(FlowSlot), (hipStream_t)stream));
     if (c->d_status) HIP_TRY(hipMemsetAsync(c->d_status, 0, c->table_cap, (hipStream_t)stream));
+    if (c->d_wl_state) HIP_TRY(hipMemsetAsync(c->d_wl_state, 0, c->table_cap, (hipStream_t)stream));
     c->flow_batch = 0;
     c->clear_seq = c->upd_seq;
     c->last_recs = nullptr;

@@ -23,28 +23,8 @@
 
 namespace fbk {
 
-// a < b over session_key ip words (word 0 most significant); v4 uses word 0 only
-__device__ __forceinline__ bool ip_lt(const uint32_t a[4], const uint32_t b[4], bool v6) {
-    if (!v6) return a[0] < b[0];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (a[k] != b[k]) return a[k] < b[k];
-    return false;
-}
-
-// Db::lookup, src/asn_db.rs:144-166 -- returns the record, or -1 for None.
-__device__ __forceinline__ int32_t asn_lookup(const fb_asn_range* T, uint32_t n, const uint32_t ip[4], bool v6) {
-    uint32_t low = 0u, high = n;
-    while (low < high) {
-        const uint32_t mid = (low + high) >> 1;
-        const fb_asn_range& r = T[mid];
-        const bool ge_start = !ip_lt(ip, r.start, v6), le_end = !ip_lt(r.end, ip, v6);
-        if (ge_start && le_end) return (int32_t)r.record;
-        if (!ge_start) high = mid;
-        else low = mid + 1u;
-    }
-    return -1;
-}
+// (ip_lt and asn_lookup -- Db::lookup, src/asn_db.rs:144-166 -- are in fb_internal.h: the whitelist
+// pass uses them too)
 
 // Lists whose ranges contain ip: the mask of the last elementary interval starting <= ip.
 __device__ __forceinline__ unsigned long long bl_lookup(const EnrichTables& t, const uint32_t ip[4], bool v6) {

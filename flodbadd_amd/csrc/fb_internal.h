@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/flodbadd_gpu.h"
 
 namespace fbk {
@@ -640,6 +642,92 @@ hipError_t launch_ip_lookup(const EnrichTables& t, const fb_ip* ips, uint32_t n,
 hipError_t launch_flow_enrich(const EnrichTables& t, const DevConfig* cfg, const FlowSlot* table,
                               unsigned long long cap, uint32_t new_only, uint32_t batch, fb_flow_enrich* out,
                               unsigned long long out_cap, unsigned long long* d_n, hipStream_t s);
+
+// a < b over session_key ip words (word 0 most significant); v4 uses word 0 only
+__device__ __forceinline__ bool ip_lt(const uint32_t a[4], const uint32_t b[4], bool v6) {
+    if (!v6) return a[0] < b[0];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (a[k] != b[k]) return a[k] < b[k];
+    return false;
+}
+// Db::lookup, src/asn_db.rs:144-166 -- the index of the range it returns, or -1 for None.
+__device__ __forceinline__ int32_t asn_find(const fb_asn_range* T, uint32_t n, const uint32_t ip[4], bool v6) {
+    uint32_t low = 0u, high = n;
+    while (low < high) {
+        const uint32_t mid = (low + high) >> 1;
+        const fb_asn_range& r = T[mid];
+        const bool ge_start = !ip_lt(ip, r.start, v6), le_end = !ip_lt(r.end, ip, v6);
+        if (ge_start && le_end) return (int32_t)mid;
+        if (!ge_start) high = mid;
+        else low = mid + 1u;
+    }
+    return -1;
+}
+// ... its record, or -1.
+__device__ __forceinline__ int32_t asn_lookup(const fb_asn_range* T, uint32_t n, const uint32_t ip[4], bool v6) {
+    uint32_t low = 0u, high = n;
+    while (low < high) {
+        const uint32_t mid = (low + high) >> 1;
+        const fb_asn_range& r = T[mid];
+        const bool ge_start = !ip_lt(ip, r.start, v6), le_end = !ip_lt(r.end, ip, v6);
+        if (ge_start && le_end) return (int32_t)r.record;
+        if (!ge_start) high = mid;
+        else low = mid + 1u;
+    }
+    return -1;
+}
+
+// Whitelist conformance (fb_whitelist.hip, fb_flow_whitelist).  fb_set_whitelist compiles the endpoint
+// list into three structures (build_whitelist_index):
+//   exact   the endpoints that match by one address: per family the addresses ascending and, beside
+//           each, its (protocol | any, port | any) key, ascending inside an address's run (deduplicated);
+//   rules   every other endpoint the device can match -- nets, AS-only, match-all -- sorted by the same key;
+//   groups  the distinct keys of the rules and of the host-check endpoints (domain / process), ascending:
+//           gkey[g] (kWlGroupHostCheck: a domain / process endpoint has this key), the group's rules
+//           rules[gbeg[g] .. gbeg[g + 1]).
+// A flow (protocol P, destination port Q) can only match the endpoints of its four keys wl_key(0 | P,
+// none | Q): the kernel looks each up (one address search, four group searches).
+__host__ __device__ inline uint32_t wl_key(uint32_t proto, bool has_port, uint32_t port) {
+    return proto << 17 | (has_port ? 1u << 16 | port : 0u);
+}
+constexpr uint32_t kWlGroupHostCheck = 0x80000000u;
+struct WlRule {                   // 48 B: three 16-B LDS reads, and a net test of xor / and / or per word
+    uint32_t a[4];                // family 2 / 10: the network (host bits cleared); family 0: as_number,
+                                  // owner_id, country_id, 0
+    uint32_t m[4];                // the prefix mask (IPv4: word 0, the other words 0 like the key's)
+    uint32_t kind;                // family | FB_WL_HAS_ASN/OWNER/COUNTRY << 16 (family 0 only)
+    uint32_t pad[3];
+};
+static_assert(sizeof(WlRule) == 48, "whitelist rule is 48 B");
+// Staged in LDS by every workgroup when both fit (28 KiB: five 256-thread workgroups per CU), else read
+// from global memory.
+constexpr uint32_t kWlLdsRules = 512, kWlLdsGroups = 512;
+constexpr uint32_t kWlCounters = 5;  // fb_wl_stats' first five fields
+struct WlTables {
+    const uint32_t* a4;   // [n4] exact IPv4 addresses
+    const uint32_t* k4;   // [n4] their keys
+    const uint4* a6;      // [n6] exact IPv6 addresses (session_key word order)
+    const uint32_t* k6;
+    const uint32_t* gkey; // [ng]
+    const uint32_t* gbeg; // [ng + 1]
+    const WlRule* rules;  // [nr]
+    const uint32_t* rec_owner;    // [n_records]
+    const uint32_t* rec_country;
+    uint32_t n4, n6, ng, nr, n_records;
+};
+struct WlIndex {  // host form
+    std::vector<uint32_t> a4, k4, k6, gkey, gbeg;
+    std::vector<uint4> a6;
+    std::vector<WlRule> rules;
+};
+// false: an endpoint with a bad family / prefix / protocol, or more than FB_WL_MAX_EXACT / _OTHER
+bool build_whitelist_index(const fb_wl_endpoint* eps, uint64_t n, WlIndex& ix);
+hipError_t launch_flow_whitelist(const WlTables& w, const EnrichTables& t, const DevConfig* cfg, const FlowSlot* table,
+                                 unsigned long long cap, uint8_t* state, unsigned long long* stats, hipStream_t s);
+hipError_t launch_flow_export_whitelist(const FlowSlot* table, const uint8_t* state, unsigned long long cap,
+                                        uint32_t state_mask, fb_flow_rec* out, unsigned long long out_cap,
+                                        unsigned long long* d_n, const FlowTime* plane, hipStream_t s);
 
 hipError_t launch_dns_parse(const uint8_t* frames, unsigned long long frames_bytes, const fb_dns_out* dns, uint32_t n,
                             const fb_batch_stats* stats, fb_dns_msg* msgs, char* names, fb_ip* addrs, hipStream_t s);

@@ -15,6 +15,7 @@ from dataclasses import dataclass, field
 from typing import List, Optional
 
 from ._native import (CONN_STATES, FB_FILTER_ALL, FB_FILTER_GLOBAL_ONLY, FB_FILTER_LOCAL_ONLY, FB_SEEN_NONE,
+                      FB_WL_CONFORMING, FB_WL_NONCONFORMING,
                       FLOW_REC_DTYPE, SESSION_DST_SERVICE, SESSION_LOCAL_DST, SESSION_LOCAL_SRC, SESSION_SELF_DST,
                       SESSION_SELF_SRC, STATUS_ACTIVATED, STATUS_ACTIVE, STATUS_ADDED, STATUS_DEACTIVATED,
                       META_DST_SERVICE, META_HAS_FLAGS, META_LOCAL_DST, META_LOCAL_SRC, META_ORIGINATOR,
@@ -174,11 +175,27 @@ class SessionStatus:
                              bool(b & STATUS_DEACTIVATED))
 
 
+class WhitelistState(enum.Enum):
+    """src/sessions.rs:183-187."""
+    Conforming = "Conforming"
+    NonConforming = "NonConforming"
+    Unknown = "Unknown"
+
+    @staticmethod
+    def from_byte(b):
+        """A state byte of fb_flow_whitelist_dev; 0 (no pass has seen the flow) is Unknown."""
+        b = int(b)
+        if b & FB_WL_CONFORMING:
+            return WhitelistState.Conforming
+        return WhitelistState.NonConforming if b & FB_WL_NONCONFORMING else WhitelistState.Unknown
+
+
 @dataclass
 class SessionInfo:
     """Subset of src/sessions.rs:40-61 that the GPU path owns.  is_local_* / is_self_* and
     dst_service are the values stored when the session was inserted (src/packets.rs:429-466,
-    fb_flow_rec.session_flags); status is None on an untimed capture (no clock to age by)."""
+    fb_flow_rec.session_flags); status is None on an untimed capture (no clock to age by);
+    is_whitelisted / whitelist_reason are what the last whitelist pass left (Unknown before it)."""
     session: Session
     stats: SessionStats = field(default_factory=SessionStats)
     is_local_src: bool = False
@@ -187,6 +204,8 @@ class SessionInfo:
     is_self_dst: bool = False
     dst_service: Optional[str] = None
     status: Optional[SessionStatus] = None
+    is_whitelisted: WhitelistState = WhitelistState.Unknown
+    whitelist_reason: Optional[str] = None
 
 
 _SERVICE_NAMES = None
@@ -291,7 +310,7 @@ def histories_from_records(recs):
     return {k: (h, state.get(k)) for k, h in hist.items()}
 
 
-def flows_to_sessions(flows, histories=None, times=None, status=None):
+def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=None):
     """fb_flow_rec records -> SessionInfo list sorted by the derived Ord of Session.  `histories`
     ({table slot: str}, FlodbaddGpuCapture.histories) supplies the history strings; the locality
     flags and dst_service come from fb_flow_rec.session_flags (stored at insert, src/packets.rs:
@@ -299,7 +318,9 @@ def flows_to_sessions(flows, histories=None, times=None, status=None):
     set at run time names).  `times` (timed contexts): FLOW_TIME_DTYPE records, either joined by
     table slot (fb_flow_export_times) or, when every slot field is 0, one per flow in `flows` order.
     `status` (timed contexts): the status byte of every table slot (fb_flow_status_dev), indexed by
-    fb_flow_rec.slot, decoded into SessionInfo.status; a zero byte gives the insert status."""
+    fb_flow_rec.slot, decoded into SessionInfo.status; a zero byte gives the insert status.
+    `whitelist`: the whitelist state byte of every table slot (fb_flow_whitelist_dev), decoded into
+    SessionInfo.is_whitelisted; without it every session is Unknown."""
     if flows.dtype != FLOW_REC_DTYPE:
         raise TypeError("expected fb_flow_rec records (FLOW_REC_DTYPE), got %s" % flows.dtype)
     tmap = None
@@ -333,6 +354,8 @@ def flows_to_sessions(flows, histories=None, times=None, status=None):
                            bool(f & SESSION_SELF_SRC), bool(f & SESSION_SELF_DST), svc)
         if status is not None:
             info.status = SessionStatus.from_byte(status[int(r["slot"])])
+        if whitelist is not None:
+            info.is_whitelisted = WhitelistState.from_byte(whitelist[int(r["slot"])])
         out.append(info)
     out.sort(key=lambda i: i.session.sort_key())
     return out
@@ -349,6 +372,7 @@ def filter_sessions(sessions: List[SessionInfo], flt: SessionFilter, lan_v6=()) 
 
 
 __all__ = ["Protocol", "SessionFilter", "Session", "SessionPacketData", "SessionStats", "SessionStatus", "SessionInfo",
+           "WhitelistState",
            "ip_to_words", "words_to_ip", "service_name", "records_to_packets", "flows_to_sessions", "filter_sessions",
            "packets_to_parsed", "determine_conn_state", "histories_from_records", "is_lan_ip", "is_local_session",
            "META_HAS_FLAGS", "META_SWAP", "META_ORIGINATOR", "META_LOCAL_SRC", "META_LOCAL_DST",

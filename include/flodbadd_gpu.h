@@ -745,6 +745,90 @@ int fb_flow_age(fb_ctx* ctx, uint64_t now_ns, const fb_age_params* params, uint3
  * fb_flow_age) into DEVICE memory.  Asynchronous. */
 int fb_flow_status_dev(fb_ctx* ctx, uint8_t* d_out, uint64_t cap, void* stream);
 
+/* ---- whitelist conformance (recompute_whitelist_for_sessions, src/whitelists.rs:810-1023, over
+ *      is_session_in_whitelist / endpoint_matches_with_reason, src/whitelists.rs:341-732) ----------
+ * The reference checks every session against the flattened endpoint list of the active whitelist and
+ * keeps SessionInfo.is_whitelisted, the whitelist_exceptions list and the whitelist_conformance flag.
+ * fb_flow_whitelist does that check for every flow of the table in one pass, for a session whose
+ * dst_domain and l7 are None (the device knows neither; the host expands the domains it has resolved
+ * into address endpoints before fb_set_whitelist and resolves the flows marked FB_WL_HOST_CHECK):
+ *   - protocol, port and process must match (src/whitelists.rs:465-491): an endpoint with a process
+ *     never matches here;
+ *   - a domain endpoint does not match by domain; with `ip` specified, an address match returns true at
+ *     once and a mismatch fails the endpoint, whatever its AS fields say (src/whitelists.rs:503-531);
+ *   - with neither domain nor ip, every specified AS field must equal the session's dst_asn
+ *     (src/whitelists.rs:534-595), which is Db::lookup of the destination unless it is a LAN address
+ *     (src/packets.rs:468-485; LAN under the context's CURRENT configuration), None without ASN tables;
+ *     an endpoint with nothing specified matches every session.
+ * One compiled WhitelistEndpoint (src/whitelists.rs:24-34): */
+#define FB_WL_NEVER 0xFFu /* family: an `ip` string that does not parse (ip_matches is false for it);
+                             protocol: a string that is neither TCP nor UDP ignoring ASCII case */
+#define FB_WL_HAS_PORT 1u
+#define FB_WL_HAS_ASN 2u
+#define FB_WL_HAS_OWNER 4u
+#define FB_WL_HAS_COUNTRY 8u
+#define FB_WL_HAS_DOMAIN 16u  /* `domain` is Some */
+#define FB_WL_HAS_PROCESS 32u /* `process` is Some */
+typedef struct fb_wl_endpoint {
+    uint32_t addr[4];    /*  0: `ip`, session_key word order; the host bits of a net are ignored       */
+    uint8_t family;      /* 16: 0 = no ip, 2, 10, FB_WL_NEVER                                          */
+    uint8_t prefix;      /* 17: <= 32 / <= 128; a plain IP is a /32 or /128                            */
+    uint8_t protocol;    /* 18: 0 = any, 6, 17, FB_WL_NEVER                                            */
+    uint8_t flags;       /* 19: FB_WL_HAS_*                                                            */
+    uint16_t port;       /* 20: with FB_WL_HAS_PORT                                                    */
+    uint16_t reserved;   /* 22: 0                                                                      */
+    uint32_t as_number;  /* 24: with FB_WL_HAS_ASN                                                     */
+    uint32_t owner_id;   /* 28: with FB_WL_HAS_OWNER: the caller's id of the ASCII-lower-cased string  */
+    uint32_t country_id; /* 32: with FB_WL_HAS_COUNTRY (ids < 0xFFFFFFFF)                               */
+    uint32_t reserved2;  /* 36: 0                                                                      */
+} fb_wl_endpoint;        /* 40 bytes */
+#define FB_WL_MAX_EXACT (1u << 24) /* endpoints that match by one address (/32, /128), per call       */
+#define FB_WL_MAX_OTHER (1u << 16) /* every other endpoint (nets, AS-only, domain-only, process)      */
+/* Install the flattened endpoint list of the active whitelist (copied and indexed before the call
+ * returns).  rec_owner_id[r] / rec_country_id[r]: the caller's id of the lower-cased owner / country
+ * string of fb_asn_range.record r (the reference compares them with eq_ignore_ascii_case); NULL with
+ * n_records 0, and a record >= n_records has strings no endpoint equals.  n == 0 is an active whitelist
+ * without endpoints: every session is NonConforming (src/whitelists.rs:413-421).  A list beyond
+ * FB_WL_MAX_EXACT / FB_WL_MAX_OTHER, or an endpoint with a bad family / prefix / protocol, fails with
+ * FB_ERR_INVAL and leaves the installed list as it was: nothing is ever truncated. */
+int fb_set_whitelist(fb_ctx* ctx, const fb_wl_endpoint* eps, uint64_t n, const uint32_t* rec_owner_id,
+                     const uint32_t* rec_country_id, uint32_t n_records);
+/* reset_whitelist (src/capture.rs:131-149): no list is active and every flow's state is Unknown. */
+int fb_clear_whitelist(fb_ctx* ctx);
+/* The state byte of a table slot: 0 = Unknown (no pass has seen the flow since its insert), else
+ * FB_WL_CONFORMING or FB_WL_NONCONFORMING; a NonConforming flow also has FB_WL_HOST_CHECK when some
+ * endpoint with a domain or a process matches its protocol and port -- the necessary condition for such
+ * an endpoint to match once the host knows the flow's domain or process: a superset of the flows the
+ * host has to look at, never a verdict. */
+#define FB_WL_CONFORMING 1u
+#define FB_WL_NONCONFORMING 2u
+#define FB_WL_HOST_CHECK 4u
+#define FB_WL_MASK_UNKNOWN 128u /* fb_flow_export_whitelist_dev's state_mask: the flows with a zero byte */
+typedef struct fb_wl_stats {
+    uint64_t flows;         /* flows in the table                                                      */
+    uint64_t conforming;
+    uint64_t nonconforming;
+    uint64_t host_check;    /* of the nonconforming: FB_WL_HOST_CHECK set                              */
+    uint64_t changed;       /* flows whose state byte differs from before the call (the reference bumps
+                               last_modified for those, src/whitelists.rs:975-982)                     */
+    uint64_t reserved[3];
+} fb_wl_stats; /* 64 bytes */
+/* Evaluate every flow against the installed list (the reference's incremental selection is an
+ * optimisation of a pure function of the session, so a full pass gives the same states).  Synchronous:
+ * waits for the updates in flight, like fb_flow_age; timed and untimed contexts.  `flags` must be 0;
+ * `out` may be NULL.  FB_ERR_INVAL without a flow table or without an installed list. */
+int fb_flow_whitelist(fb_ctx* ctx, uint32_t flags, fb_wl_stats* out, void* stream);
+/* The state byte of every table slot (min(cap, capacity) bytes, slot order; zero before the first pass)
+ * into DEVICE memory.  Asynchronous.  The bytes follow their flows through a growth and a purge
+ * (fb_flow_slot_remap's map), and fb_flow_clear zeroes them. */
+int fb_flow_whitelist_dev(fb_ctx* ctx, uint8_t* d_out, uint64_t cap, void* stream);
+/* The fb_flow_rec of the flows whose state byte has a bit of `state_mask` (FB_WL_* bits;
+ * FB_WL_MASK_UNKNOWN selects the zero bytes), slot order -- the whitelist exceptions are
+ * FB_WL_NONCONFORMING; the caller sorts them by Session.  *d_n (device u64) = the matching flows (only
+ * the first `cap` are written).  DEVICE pointers, asynchronous. */
+int fb_flow_export_whitelist_dev(fb_ctx* ctx, uint32_t state_mask, fb_flow_rec* d_out, uint64_t cap, uint64_t* d_n,
+                                 void* stream);
+
 /* ---- multi-GPU session table (BASELINE configs[4]) ------------------------------
  * The reference runs one capture task per interface into ONE shared DashMap (src/capture.rs:946-1016,
  * src/packets.rs:329-535); W ranks that each parse a contiguous packet-index shard into their own
