@@ -531,9 +531,12 @@ __global__ __launch_bounds__(kSegThreads, kSegWaves * FB_SEG_BPC / 4) void k_par
                 kk.bad = false;
                 kk.cls = FB_CLASS_DROP;
                 kk.tcp = kk.v4 = false;
+                // flags: Option<u8> -- any non-zero has_flags byte is Some, and None carries no flag bits
+                // (fb_pkt_out.tcp_flags is 0 then, as from the frame decode)
+                const uint32_t hasf = (d.x & 0xff00u) != 0u ? 1u : 0u;
                 if ((proto == 6u || proto == 17u) && (fam == 2u || fam == 10u))
-                    classify_session(cfg, cfg, proto, fam, src, dst, cc.x & 0xffffu, cc.x >> 16, (d.x >> 8) & 1u,
-                                     d.x & 0xffu, cc.z, cc.w, d.y, kk);
+                    classify_session(cfg, cfg, proto, fam, src, dst, cc.x & 0xffffu, cc.x >> 16, hasf,
+                                     hasf ? d.x & 0xffu : 0u, cc.z, cc.w, d.y, kk);
             }
             const bool is_s = valid && kk.cls == FB_CLASS_SESSION;
             const bool is_d = valid && kk.cls == FB_CLASS_DNS;

@@ -127,8 +127,8 @@ typedef struct fb_parsed_pkt {
     fb_session_key session;    /*  0 */
     uint32_t packet_length;    /* 40: L4 payload bytes                                        */
     uint32_t ip_packet_length; /* 44                                                          */
-    uint8_t tcp_flags;         /* 48                                                          */
-    uint8_t has_flags;         /* 49: 1 = Some(flags)                                          */
+    uint8_t tcp_flags;         /* 48: ignored (taken as 0) when has_flags is 0                 */
+    uint8_t has_flags;         /* 49: non-zero = Some(flags), 0 = None                         */
     uint16_t reserved;         /* 50: 0                                                        */
     uint32_t pkt_index;        /* 52: copied to fb_pkt_out.pkt_index                           */
 } fb_parsed_pkt;               /* 56 bytes */
