@@ -11,12 +11,13 @@ from ._native import (DNS_OUT_DTYPE, FB_CLASS_DNS, FB_CLASS_DROP, FB_CLASS_FILTE
 from .sessions import (Protocol, Session, SessionFilter, SessionInfo, SessionPacketData, SessionStats, SessionStatus,
                        WhitelistState)
 from .whitelists import Whitelists
+from .enrich import Blacklists
 from .queue import DeviceSegBatch, SegQueue
 
 __all__ = ["_native", "DeviceSegBatch", "SegQueue", "gpu_lib", "FbError", "NativeLibraryMissing", "PKT_OUT_DTYPE", "DNS_OUT_DTYPE",
            "STATS_DTYPE", "FLOW_REC_DTYPE", "FB_CLASS_SESSION", "FB_CLASS_DNS", "FB_CLASS_DROP",
            "FB_CLASS_FILTERED", "Protocol", "Session", "SessionFilter", "SessionInfo", "SessionPacketData",
-           "SessionStats", "SessionStatus", "WhitelistState", "Whitelists"]
+           "SessionStats", "SessionStatus", "WhitelistState", "Whitelists", "Blacklists"]
 
 
 def FlodbaddGpuCapture(*args, **kwargs):  # lazy import keeps `import flodbadd_amd` light

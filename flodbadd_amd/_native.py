@@ -82,6 +82,12 @@ FB_WL_CONFORMING, FB_WL_NONCONFORMING, FB_WL_HOST_CHECK, FB_WL_MASK_UNKNOWN = 1,
 FB_WL_MAX_EXACT, FB_WL_MAX_OTHER = 1 << 24, 1 << 16
 # the kernel's staging thresholds (fb_internal.h: kWlLdsRules, kWlLdsGroups), for the tests at them
 WL_LDS_RULES, WL_LDS_GROUPS = 512, 512
+# fb_bl_stats (fb_flow_blacklist: recompute_blacklist_for_sessions, src/blacklists.rs:456-731) and the
+# whitelist state bit of the "Session is blacklisted" fallback (src/capture.rs:1858-1871)
+BL_STATS_FIELDS = ["flows", "blacklisted", "changed", "newly_blacklisted", "cleared", "wl_marked"]
+BL_STATS_DTYPE = np.dtype([(f, "<u8") for f in BL_STATS_FIELDS] + [("reserved", "<u8", (2,))])
+assert BL_STATS_DTYPE.itemsize == 64
+FB_BL_MARK_WHITELIST, FB_WL_BLACKLISTED = 1, 8
 FB_SEGMENT_TIMEOUT_MS = 5000
 FB_CFG_TIMED = 2
 FB_QUEUE_SHARED = 1
@@ -285,6 +291,9 @@ GPU_SYMBOLS = [
     ("fb_flow_whitelist", _I, [_P, _U32, _P, _P]),
     ("fb_flow_whitelist_dev", _I, [_P, _P, _U64, _P]),
     ("fb_flow_export_whitelist_dev", _I, [_P, _U32, _P, _U64, _P, _P]),
+    ("fb_flow_blacklist", _I, [_P, _U32, _P, _P]),
+    ("fb_flow_blacklist_dev", _I, [_P, _P, _U64, _P]),
+    ("fb_flow_export_blacklisted_dev", _I, [_P, _P, _P, _U64, _P, _P]),
 ]
 
 _gpu = None

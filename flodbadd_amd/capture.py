@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _native as N
 from .sessions import Session, SessionFilter, WhitelistState, flows_to_sessions, ip_to_words, is_lan_ip
+from .enrich import Blacklists
 from .whitelists import Whitelists, is_session_in_whitelist, no_match_reason
 
 
@@ -101,6 +102,12 @@ class FlodbaddGpuCapture:
         self._wl_host_ok = set()    # the Sessions the host resolved to Conforming (process names)
         self._wl_conformance = True
         self._wl_exceptions = np.zeros(0, dtype=N.FLOW_REC_DTYPE)
+        # blacklist pass (src/blacklists.rs:456-731): the custom model, the name of every installed
+        # list (bit l of a mask), whether a pass has run and whether one has marked whitelist bytes
+        self._blacklists = Blacklists()
+        self._bl_names = []
+        self._bl_ran = False
+        self._bl_marked = False
 
     # ---- configuration -------------------------------------------------------------------
     def set_filter(self, flt):
@@ -350,7 +357,8 @@ class FlodbaddGpuCapture:
         out = flows_to_sessions(self.export_flows(self.filter), self.histories if self.track_history else None,
                                 times=self.export_times() if self.timed else None,
                                 status=self.status_bytes() if self.timed else None,
-                                whitelist=self.whitelist_bytes() if self._wl_name else None)
+                                whitelist=self.whitelist_bytes() if (self._wl_name or self._bl_marked) else None,
+                                blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None)
         for info in out if self._wl_host_ok else ():  # the host's verdict for the flows the pass left to it
             if info.session in self._wl_host_ok and info.is_whitelisted is WhitelistState.NonConforming:
                 info.is_whitelisted = WhitelistState.Conforming
@@ -368,7 +376,8 @@ class FlodbaddGpuCapture:
         b = status[flows["slot"]] if len(flows) else np.zeros(0, dtype=np.uint8)
         flows = flows[(b == 0) | ((b & N.STATUS_CURRENT) != 0)]
         return flows_to_sessions(flows, self.histories if self.track_history else None, times=self.export_times(),
-                                 status=status)
+                                 status=status,
+                                 blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None)
 
     # ---- new-session enrichment (src/packets.rs:429-485) -------------------------------------
     def set_asn_tables(self, v4, v6, records=None):
@@ -382,10 +391,13 @@ class FlodbaddGpuCapture:
         self._asn_records = list(records) if records is not None else []
         self._wl_installed = None  # the interned record ids belong to the installed list
 
-    def set_blacklists(self, cidrs):
-        """CIDR_DTYPE ranges (flodbadd_amd.enrich.blacklists_from_json) -> fb_set_blacklists."""
+    def set_blacklists(self, cidrs, names=None):
+        """CIDR_DTYPE ranges (flodbadd_amd.enrich.blacklists_from_json) -> fb_set_blacklists.  names:
+        that function's second result, the name of list l (the criticality tags need them; without
+        them list l is called "l")."""
         cidrs = np.ascontiguousarray(cidrs, dtype=N.CIDR_DTYPE)
         N.check(N.gpu_lib().fb_set_blacklists(self.ctx, N.ptr(cidrs) if len(cidrs) else None, len(cidrs)))
+        self._bl_names = list(names) if names is not None else [str(l) for l in range(N.FB_MAX_BLACKLISTS)]
 
     def ip_lookup(self, ips):
         """get_asn + is_ip_blacklisted for addresses (strings / ipaddress objects) ->
@@ -406,6 +418,83 @@ class FlodbaddGpuCapture:
         N.check(N.gpu_lib().fb_flow_enrich_dev(self.ctx, 1 if new_only else 0, d_out.ptr, cap, d_n.ptr, None))
         m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
         return d_out.download(np.zeros(cap, dtype=N.FLOW_ENRICH_DTYPE))[:m]
+
+    # ---- blacklist pass (src/blacklists.rs:404-437, 456-731; src/capture.rs:1680-1783, 1850-1871) ---
+    def set_custom_blacklists(self, blacklist_json):
+        """set_custom_blacklists (src/capture.rs:1772-1783): a BlacklistsJSON document (text) replaces
+        the installed lists -- no local-range filtering for custom lists -- and the sessions are
+        re-evaluated at once (update_sessions).  "" resets to no lists: there is no built-in database.
+        Text that is not a BlacklistsJSON raises ValueError and the installed lists stay as they were."""
+        model = Blacklists(blacklist_json)  # raises before anything is replaced
+        self.set_blacklists(model.cidrs, model.names)
+        self._blacklists = model
+        return self.update_sessions(None, *self._wl_inputs)
+
+    def get_blacklists(self):
+        """get_blacklists (src/capture.rs:459): the custom model as BlacklistsJSON text."""
+        return self._blacklists.to_json()
+
+    def update_blacklist(self, mark_whitelist=True):
+        """recompute_blacklist_for_sessions over every session (fb_flow_blacklist) and, with
+        mark_whitelist, the fallback after it (src/capture.rs:1858-1871): a blacklisted session whose
+        whitelist state is Unknown becomes NonConforming, "Session is blacklisted".  Returns the
+        pass's counters (fb_bl_stats)."""
+        st = np.zeros(1, dtype=N.BL_STATS_DTYPE)
+        N.check(N.gpu_lib().fb_flow_blacklist(self.ctx, N.FB_BL_MARK_WHITELIST if mark_whitelist else 0, N.ptr(st),
+                                              None))
+        out = {k: int(st[0][k]) for k in N.BL_STATS_FIELDS}
+        self._bl_ran = True
+        self._bl_marked = self._bl_marked or out["wl_marked"] > 0
+        return out
+
+    def blacklist_masks(self):
+        """fb_flow_blacklist_dev: the blacklist mask of every table slot (index = fb_flow_rec.slot,
+        bit l = list l); all zero before the first pass."""
+        cap = int(self.table_info()["capacity"])
+        out = np.zeros(max(cap, 1), dtype=np.uint64)
+        if cap:
+            d = N.DeviceBuffer(cap * 8)
+            N.check(N.gpu_lib().fb_flow_blacklist_dev(self.ctx, d.ptr, cap, None))
+            d.download(out, cap * 8)
+        return out[:cap]
+
+    def export_blacklisted_flows(self):
+        """fb_flow_export_blacklisted_dev: (the flows with a non-zero mask, their masks), slot order."""
+        cap = max(self.flow_count(), 1)
+        d_out, d_m, d_n = N.DeviceBuffer(cap * N.FLOW_REC_DTYPE.itemsize), N.DeviceBuffer(cap * 8), N.DeviceBuffer(8)
+        N.check(N.gpu_lib().fb_flow_export_blacklisted_dev(self.ctx, d_out.ptr, d_m.ptr, cap, d_n.ptr, None))
+        m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
+        return (d_out.download(np.zeros(cap, dtype=N.FLOW_REC_DTYPE))[:m],
+                d_m.download(np.zeros(cap, dtype=np.uint64))[:m])
+
+    def get_blacklisted_sessions(self, now_ns=None):
+        """get_blacklisted_sessions(false) (src/capture.rs:1680-1719): after an update, the sessions of
+        the blacklisted list as SessionInfo, in the order new_blacklisted_sessions.sort() leaves the
+        keys (src/blacklists.rs:693)."""
+        self.update_sessions(now_ns, *self._wl_inputs)
+        flows, masks = self.export_blacklisted_flows()
+        if not len(flows):
+            return []
+        by_slot = {int(r["slot"]): m for r, m in zip(flows, masks)}
+        return flows_to_sessions(flows, self.histories if self.track_history else None,
+                                 times=self.export_times() if self.timed else None,
+                                 status=self.status_bytes() if self.timed else None,
+                                 whitelist=self.whitelist_bytes() if (self._wl_name or self._bl_marked) else None,
+                                 blacklist=(by_slot, self._bl_names))
+
+    def get_blacklisted_status(self, now_ns=None):
+        """get_blacklisted_status (src/capture.rs:1762-1770): after an update, some session is blacklisted."""
+        return self.update_sessions(now_ns, *self._wl_inputs)["blacklist"]["blacklisted"] > 0
+
+    def update_sessions(self, now_ns=None, dns_resolutions=None, process_names=None):
+        """update_sessions_internal's per-session passes in the reference's order (src/capture.rs:
+        1811-1882): the status (timed captures, when now_ns is given), the blacklist pass with its
+        whitelist fallback, then the whitelist pass when a list is active.  Returns the three calls'
+        counters ({"status", "blacklist", "whitelist"}; None for a pass that did not run)."""
+        age = self.update_sessions_status(now_ns) if (self.timed and now_ns is not None) else None
+        bl = self.update_blacklist(mark_whitelist=True)
+        wl = self.update_whitelist(dns_resolutions, process_names)
+        return {"status": age, "blacklist": bl, "whitelist": wl}
 
     # ---- whitelist conformance (src/whitelists.rs:810-1023, src/capture.rs:131-183, 463-531) ---
     def set_custom_whitelists(self, whitelist_json):
@@ -442,6 +531,7 @@ class FlodbaddGpuCapture:
         """reset_whitelist (src/capture.rs:131-149): conformance true, no exceptions, every session
         Unknown (fb_clear_whitelist; the next update installs the list again)."""
         N.check(N.gpu_lib().fb_clear_whitelist(self.ctx))
+        self._bl_marked = False  # (the blacklist fallback's bytes are gone with the others)
         self._wl_installed = None
         self._wl_host_ok = set()
         self._wl_conformance = True
@@ -564,6 +654,7 @@ class FlodbaddGpuCapture:
         self.histories = {}
         self._wl_host_ok = set()
         self._wl_exceptions = np.zeros(0, dtype=N.FLOW_REC_DTYPE)
+        self._bl_marked = False
 
     def close(self):
         if getattr(self, "ctx", None):

@@ -128,6 +128,10 @@ struct fb_ctx {
     uint32_t wl_n4 = 0, wl_n6 = 0, wl_ng = 0, wl_nr = 0, wl_records = 0;
     uint8_t* d_wl_state = nullptr;             // [table_cap]
     unsigned long long* d_wl_stats = nullptr;  // [kWlCounters]
+    // blacklist pass (fb_flow_blacklist, fb_blacklist.hip): the mask plane (allocated by the first pass)
+    // and the pass's counters
+    unsigned long long* d_bl_mask = nullptr;   // [table_cap]
+    unsigned long long* d_bl_stats = nullptr;  // [kBlCounters]
     void* d_mscratch = nullptr;   // multi-GPU merge scratch (export owner counts / merge tables)
     hipEvent_t ev_mscratch = nullptr;  // after the last export / merge that used d_mscratch (either may
                                        // run on any stream: the next use waits for it)
@@ -567,6 +571,8 @@ int fb_destroy(fb_ctx* c) {
     hipFree(c->d_wl_country);
     hipFree(c->d_wl_state);
     hipFree(c->d_wl_stats);
+    hipFree(c->d_bl_mask);
+    hipFree(c->d_bl_stats);
     hipFree(c->d_mscratch);
     if (c->ev_mscratch) hipEventDestroy(c->ev_mscratch);
     if (c->h_mbox) hipHostFree(c->h_mbox);
@@ -1429,10 +1435,28 @@ static int grow_table(fb_ctx* c, hipStream_t s, uint32_t k) {
         HIP_TRY(hipMemsetAsync(nw_wl, 0, cap, s));
         HIP_TRY(launch_age_remap(c->d_wl_state, c->d_remap, c->table_cap, nw_wl, s));
     }
+    unsigned long long* nw_bl = nullptr;
+    if (c->d_bl_mask) {  // ... and the blacklist masks (fb_blacklist.hip): the 8-byte remap
+        if (hipMalloc(&nw_bl, cap * 8ull) != hipSuccess) {
+            hipFree(nw);
+            hipFree(nw_cc);
+            hipFree(nw_time);
+            hipFree(nw_status);
+            hipFree(nw_wl);
+            free_new();
+            return set_err(FB_ERR_NOMEM, "grown blacklist plane");
+        }
+        HIP_TRY(hipMemsetAsync(nw_bl, 0, cap * 8ull, s));
+        HIP_TRY(launch_age_remap64(c->d_bl_mask, c->d_remap, c->table_cap, nw_bl, s));
+    }
     HIP_TRY(hipStreamSynchronize(s));
     if (nw_wl) {
         hipFree(c->d_wl_state);
         c->d_wl_state = nw_wl;
+    }
+    if (nw_bl) {
+        hipFree(c->d_bl_mask);
+        c->d_bl_mask = nw_bl;
     }
     if (c->timed) {
         hipFree(c->d_time);
@@ -2022,6 +2046,19 @@ int fb_flow_age(fb_ctx* c, uint64_t now_ns, const fb_age_params* params, uint32_
                 return set_err(FB_ERR_HIP, "whitelist plane remap: %s", hipGetErrorString(e));
             }
         }
+        if (c->d_bl_mask) {  // ... and so do the blacklist masks (dropped on a failure: every flow unseen again)
+            unsigned long long* nw_bl = nullptr;
+            hipError_t e = hipMalloc(&nw_bl, c->table_cap * 8ull);
+            if (e == hipSuccess) e = hipMemsetAsync(nw_bl, 0, c->table_cap * 8ull, s);
+            if (e == hipSuccess) e = launch_age_remap64(c->d_bl_mask, c->d_remap, c->table_cap, nw_bl, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            hipFree(c->d_bl_mask);
+            c->d_bl_mask = e == hipSuccess ? nw_bl : nullptr;
+            if (e != hipSuccess) {
+                hipFree(nw_bl);
+                return set_err(FB_ERR_HIP, "blacklist plane remap: %s", hipGetErrorString(e));
+            }
+        }
     }
     if (out) {
         memset(out, 0, sizeof(*out));
@@ -2176,6 +2213,82 @@ int fb_flow_export_whitelist_dev(fb_ctx* c, uint32_t state_mask, fb_flow_rec* d_
     if (rc) return rc;
     HIP_TRY(launch_flow_export_whitelist(c->d_table, c->d_wl_state, c->table_cap, state_mask, d_out, cap,
                                          (unsigned long long*)d_n, c->d_time, s));
+    return FB_OK;
+}
+
+// ---- blacklist pass (fb_blacklist.hip) ---------------------------------------------------------------
+// Synchronous, like fb_flow_age / fb_flow_whitelist: drains the updates in flight, one pass, the
+// counters read back.  The lists are whatever fb_set_blacklists installed last (none: every mask 0).
+int fb_flow_blacklist(fb_ctx* c, uint32_t flags, fb_bl_stats* out, void* stream) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (flags & ~FB_BL_MARK_WHITELIST) return set_err(FB_ERR_INVAL, "unknown flags %u", flags);
+    const bool mark = (flags & FB_BL_MARK_WHITELIST) != 0u;
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = drain_updates(c);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!c->d_bl_mask) {
+        if (hipMalloc(&c->d_bl_mask, c->table_cap * 8ull) != hipSuccess) {
+            c->d_bl_mask = nullptr;
+            return set_err(FB_ERR_NOMEM, "blacklist plane");
+        }
+        HIP_TRY(hipMemsetAsync(c->d_bl_mask, 0, c->table_cap * 8ull, s));
+    }
+    if (mark && !c->d_wl_state) {  // the fallback writes the whitelist plane: no whitelist pass has made it yet
+        if (hipMalloc(&c->d_wl_state, c->table_cap) != hipSuccess) {
+            c->d_wl_state = nullptr;
+            return set_err(FB_ERR_NOMEM, "whitelist plane");
+        }
+        HIP_TRY(hipMemsetAsync(c->d_wl_state, 0, c->table_cap, s));
+    }
+    if (!c->d_bl_stats && hipMalloc(&c->d_bl_stats, kBlCounters * 8ull) != hipSuccess) {
+        c->d_bl_stats = nullptr;
+        return set_err(FB_ERR_NOMEM, "blacklist counters");
+    }
+    HIP_TRY(hipMemsetAsync(c->d_bl_stats, 0, kBlCounters * 8ull, s));
+    HIP_TRY(launch_flow_blacklist(enrich_tables(c), c->d_table, c->table_cap, c->d_bl_mask,
+                                  mark ? c->d_wl_state : nullptr, c->d_bl_stats, s));
+    unsigned long long h[kBlCounters] = {};
+    HIP_TRY(hipMemcpyAsync(h, c->d_bl_stats, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        out->flows = h[0];
+        out->blacklisted = h[1];
+        out->changed = h[2];
+        out->newly_blacklisted = h[3];
+        out->cleared = h[4];
+        out->wl_marked = h[5];
+    }
+    return FB_OK;
+}
+
+int fb_flow_blacklist_dev(fb_ctx* c, uint64_t* d_out, uint64_t cap, void* stream) {
+    if (!c || (cap && !d_out)) return set_err(FB_ERR_INVAL, "bad arguments");
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t m = std::min<uint64_t>(cap, c->table_cap);
+    if (m == 0) return FB_OK;
+    if (c->d_bl_mask)
+        HIP_TRY(hipMemcpyAsync(d_out, c->d_bl_mask, m * 8ull, hipMemcpyDeviceToDevice, s));
+    else
+        HIP_TRY(hipMemsetAsync(d_out, 0, m * 8ull, s));
+    return FB_OK;
+}
+
+int fb_flow_export_blacklisted_dev(fb_ctx* c, fb_flow_rec* d_out, uint64_t* d_masks, uint64_t cap, uint64_t* d_n,
+                                   void* stream) {
+    if (!c || !d_n || (cap && !d_out)) return set_err(FB_ERR_INVAL, "bad arguments");
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
+    if (!c->d_table || !c->d_bl_mask) return FB_OK;  // no pass yet: no flow has a mask
+    const int rc = join_updates(c, s);
+    if (rc) return rc;
+    HIP_TRY(launch_flow_export_blacklisted(c->d_table, c->d_bl_mask, c->table_cap, d_out,
+                                           (unsigned long long*)d_masks, cap, (unsigned long long*)d_n, c->d_time, s));
     return FB_OK;
 }
 
@@ -2351,6 +2464,7 @@ int fb_flow_clear(fb_ctx* c, void* stream) {
     HIP_TRY(hipMemsetAsync(c->d_table, 0, c->table_cap * sizeof(FlowSlot), (hipStream_t)stream));
     if (c->d_status) HIP_TRY(hipMemsetAsync(c->d_status, 0, c->table_cap, (hipStream_t)stream));
     if (c->d_wl_state) HIP_TRY(hipMemsetAsync(c->d_wl_state, 0, c->table_cap, (hipStream_t)stream));
+    if (c->d_bl_mask) HIP_TRY(hipMemsetAsync(c->d_bl_mask, 0, c->table_cap * 8ull, (hipStream_t)stream));
     c->flow_batch = 0;
     c->clear_seq = c->upd_seq;
     c->last_recs = nullptr;

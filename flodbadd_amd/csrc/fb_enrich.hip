@@ -26,25 +26,8 @@ namespace fbk {
 // (ip_lt and asn_lookup -- Db::lookup, src/asn_db.rs:144-166 -- are in fb_internal.h: the whitelist
 // pass uses them too)
 
-// Lists whose ranges contain ip: the mask of the last elementary interval starting <= ip.
-__device__ __forceinline__ unsigned long long bl_lookup(const EnrichTables& t, const uint32_t ip[4], bool v6) {
-    uint32_t lo = 0u, hi = v6 ? t.m6 : t.m4;  // first interval starting > ip
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        bool gt;
-        if (v6) {
-            const uint4 p = t.bl6_pos[mid];
-            const uint32_t pw[4] = {p.x, p.y, p.z, p.w};
-            gt = ip_lt(ip, pw, true);
-        } else {
-            gt = ip[0] < t.bl4_pos[mid];
-        }
-        if (gt) hi = mid;
-        else lo = mid + 1u;
-    }
-    if (lo == 0u) return 0ull;
-    return v6 ? t.bl6_mask[lo - 1u] : t.bl4_mask[lo - 1u];
-}
+// (bl_lookup and the search step it shares with flow_lookups and the blacklist pass -- bl_probe /
+// bl_step / bl_mask_at -- are there too)
 
 // The four lookups of a new flow (ASN and blacklist mask of src and dst) as independent searches
 // advanced in one loop, so each step issues up to four loads together: the binary searches are
@@ -77,7 +60,7 @@ __device__ __forceinline__ void flow_lookups(const EnrichTables& t, bool v6, con
                 st[k] = *reinterpret_cast<const uint4*>(A[am[k]].start);
                 en[k] = *reinterpret_cast<const uint4*>(A[am[k]].end);
             }
-            if (on_b[k]) bp[k] = v6 ? t.bl6_pos[bm[k]] : make_uint4(t.bl4_pos[bm[k]], 0u, 0u, 0u);
+            if (on_b[k]) bp[k] = bl_probe(t, v6, bm[k]);
         }
         if (!(on_a[0] || on_a[1] || on_b[0] || on_b[1])) break;
 #pragma unroll
@@ -94,17 +77,12 @@ __device__ __forceinline__ void flow_lookups(const EnrichTables& t, bool v6, con
                     alo[k] = am[k] + 1u;
                 }
             }
-            if (on_b[k]) {  // first interval starting > ip
-                const uint32_t pw[4] = {bp[k].x, bp[k].y, bp[k].z, bp[k].w};
-                if (v6 ? ip_lt(ip[k], pw, true) : ip[k][0] < pw[0]) bhi[k] = bm[k];
-                else blo[k] = bm[k] + 1u;
-            }
+            if (on_b[k]) bl_step(ip[k], v6, bp[k], bm[k], blo[k], bhi[k]);  // first interval starting > ip
         }
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        bl[k] = 0ull;
-        if (!skip[k] && blo[k] > 0u) bl[k] = v6 ? t.bl6_mask[blo[k] - 1u] : t.bl4_mask[blo[k] - 1u];
+        bl[k] = skip[k] ? 0ull : bl_mask_at(t, v6, blo[k]);
     }
 }
 

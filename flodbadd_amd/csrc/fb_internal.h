@@ -678,6 +678,49 @@ __device__ __forceinline__ int32_t asn_lookup(const fb_asn_range* T, uint32_t n,
     return -1;
 }
 
+// The blacklist interval search (fb_enrich.hip, fb_blacklist.hip): "first interval starting > ip" by
+// bisection.  One step is a probe (bl_probe: the load) and its comparison (bl_step), kept apart so a
+// caller with several searches can issue every probe before it waits for the first.
+__device__ __forceinline__ uint4 bl_probe(const EnrichTables& t, bool v6, uint32_t mid) {
+    return v6 ? t.bl6_pos[mid] : make_uint4(t.bl4_pos[mid], 0u, 0u, 0u);
+}
+__device__ __forceinline__ void bl_step(const uint32_t ip[4], bool v6, const uint4& p, uint32_t mid, uint32_t& lo,
+                                        uint32_t& hi) {
+    const uint32_t pw[4] = {p.x, p.y, p.z, p.w};
+    if (ip_lt(ip, pw, v6)) hi = mid;
+    else lo = mid + 1u;
+}
+// The mask of the last interval starting <= ip, `lo` being where the search ended (0: none).
+__device__ __forceinline__ unsigned long long bl_mask_at(const EnrichTables& t, bool v6, uint32_t lo) {
+    if (lo == 0u) return 0ull;
+    return v6 ? t.bl6_mask[lo - 1u] : t.bl4_mask[lo - 1u];
+}
+// Lists whose ranges contain ip: the mask of the last elementary interval starting <= ip.
+__device__ __forceinline__ unsigned long long bl_lookup(const EnrichTables& t, const uint32_t ip[4], bool v6) {
+    uint32_t lo = 0u, hi = v6 ? t.m6 : t.m4;  // first interval starting > ip
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        bl_step(ip, v6, bl_probe(t, v6, mid), mid, lo, hi);
+    }
+    return bl_mask_at(t, v6, lo);
+}
+
+// Blacklist pass over the table (fb_blacklist.hip, fb_flow_blacklist): one 64-bit word per table slot,
+// bit l = some range of list l contains the flow's source or destination address (an address whose
+// stored local flag is set is not searched).  Zero: not blacklisted, and the state of a flow no pass
+// has seen.  The call's device counters are fb_bl_stats' first six fields, in order.
+constexpr uint32_t kBlCounters = 6;
+constexpr uint32_t kStateLocalSrc = 1u << 20, kStateLocalDst = 1u << 21;  // hist_state: FB_SESSION_LOCAL_SRC / _DST
+// wl: the whitelist state plane with FB_BL_MARK_WHITELIST (the "Session is blacklisted" fallback), else null
+hipError_t launch_flow_blacklist(const EnrichTables& t, const FlowSlot* table, unsigned long long cap,
+                                 unsigned long long* mask, uint8_t* wl, unsigned long long* stats, hipStream_t s);
+hipError_t launch_flow_export_blacklisted(const FlowSlot* table, const unsigned long long* mask, unsigned long long cap,
+                                          fb_flow_rec* out, unsigned long long* out_masks, unsigned long long out_cap,
+                                          unsigned long long* d_n, const FlowTime* plane, hipStream_t s);
+// the 8-byte form of launch_age_remap: the mask words follow their flows
+hipError_t launch_age_remap64(const unsigned long long* old, const uint32_t* remap, unsigned long long old_cap,
+                              unsigned long long* nw, hipStream_t s);
+
 // Whitelist conformance (fb_whitelist.hip, fb_flow_whitelist).  fb_set_whitelist compiles the endpoint
 // list into three structures (build_whitelist_index):
 //   exact   the endpoints that match by one address: per family the addresses ascending and, beside

@@ -9,8 +9,13 @@ restated for the C ABI's fb_asn_range / fb_cidr tables, and the capture-level ca
                         /32 or /128, unparsable ranges are skipped, and with filter_local_ranges
                         a range entirely inside a known local range is dropped
                         (is_range_local_to_filter, src/blacklists.rs:70-105).
+  Blacklists            the BlacklistsJSON model behind set_custom_blacklists / get_blacklists
+                        (src/blacklists.rs:20-36, 782-815): date, signature and the lists.
+  criticality_of        a flow's blacklist mask as the reference's criticality string
+                        (src/blacklists.rs:608-631).
 """
 import ipaddress
+import json
 
 import numpy as np
 
@@ -85,3 +90,53 @@ def blacklists_from_json(obj, filter_local_ranges=False):
 def mask_names(mask, names):
     """The list names of a blacklist bit mask (is_ip_blacklisted's Vec<String>)."""
     return [n for i, n in enumerate(names) if (int(mask) >> i) & 1]
+
+
+def criticality_of(mask, names):
+    """SessionInfo.criticality of a blacklist mask: the matching names sorted and de-duplicated, as
+    "blacklist:<name>" tags, sorted and de-duplicated again, joined by "," (src/blacklists.rs:608-631;
+    there are no non-blacklist tags to keep: the analyzer is not part of this package)."""
+    if not int(mask):
+        return ""
+    return ",".join(sorted({"blacklist:" + n for n in mask_names(mask, names)}))
+
+
+class Blacklists:
+    """The custom blacklist model (BlacklistsJSON, src/blacklists.rs:20-36): parsed with the
+    reference's strictness -- `date`, `signature`, `blacklists` required, each list a `name` and
+    `ip_ranges` plus optional description / last_updated / source_url, unknown fields refused
+    (deny_unknown_fields) -- and flattened for fb_set_blacklists WITHOUT the local-range filter, as
+    set_custom_blacklists does (Blacklists::new_from_json(json, false), src/blacklists.rs:790-800).
+    The reference keeps the lists in a map by name: a repeated name replaces the earlier list."""
+    _INFO_REQUIRED = ("name", "ip_ranges")
+    _INFO_OPTIONAL = ("description", "last_updated", "source_url")
+
+    def __init__(self, doc=None):
+        self.date, self.signature, self.infos = "", "", []
+        self.cidrs, self.names = np.zeros(0, dtype=N.CIDR_DTYPE), []
+        if doc is None or doc == "":
+            return
+        obj = json.loads(doc) if isinstance(doc, (str, bytes)) else doc
+        if not isinstance(obj, dict) or set(obj) != {"date", "signature", "blacklists"}:
+            raise ValueError("BlacklistsJSON needs exactly date, signature and blacklists")
+        if not isinstance(obj["date"], str) or not isinstance(obj["signature"], str) or \
+                not isinstance(obj["blacklists"], list):
+            raise ValueError("BlacklistsJSON: date and signature are strings, blacklists a list")
+        by_name = {}
+        for info in obj["blacklists"]:
+            if not isinstance(info, dict) or any(k not in info for k in self._INFO_REQUIRED) or \
+                    any(k not in self._INFO_REQUIRED + self._INFO_OPTIONAL for k in info):
+                raise ValueError("BlacklistInfo: missing or unknown field")
+            if not isinstance(info["name"], str) or not isinstance(info["ip_ranges"], list) or \
+                    not all(isinstance(x, str) for x in info["ip_ranges"]) or \
+                    not all(info.get(k) is None or isinstance(info[k], str) for k in self._INFO_OPTIONAL):
+                raise ValueError("BlacklistInfo: bad field type")
+            by_name[info["name"]] = dict(info)
+        self.date, self.signature, self.infos = obj["date"], obj["signature"], list(by_name.values())
+        self.cidrs, self.names = blacklists_from_json({"blacklists": self.infos}, filter_local_ranges=False)
+
+    def to_json(self):
+        """get_blacklists (src/blacklists.rs:802-815): the model as BlacklistsJSON text."""
+        infos = [{"name": i["name"], "description": i.get("description"), "last_updated": i.get("last_updated"),
+                  "source_url": i.get("source_url"), "ip_ranges": list(i["ip_ranges"])} for i in self.infos]
+        return json.dumps({"date": self.date, "signature": self.signature, "blacklists": infos})

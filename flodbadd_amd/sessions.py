@@ -15,7 +15,7 @@ from dataclasses import dataclass, field
 from typing import List, Optional
 
 from ._native import (CONN_STATES, FB_FILTER_ALL, FB_FILTER_GLOBAL_ONLY, FB_FILTER_LOCAL_ONLY, FB_SEEN_NONE,
-                      FB_WL_CONFORMING, FB_WL_NONCONFORMING,
+                      FB_WL_BLACKLISTED, FB_WL_CONFORMING, FB_WL_NONCONFORMING,
                       FLOW_REC_DTYPE, SESSION_DST_SERVICE, SESSION_LOCAL_DST, SESSION_LOCAL_SRC, SESSION_SELF_DST,
                       SESSION_SELF_SRC, STATUS_ACTIVATED, STATUS_ACTIVE, STATUS_ADDED, STATUS_DEACTIVATED,
                       META_DST_SERVICE, META_HAS_FLAGS, META_LOCAL_DST, META_LOCAL_SRC, META_ORIGINATOR,
@@ -195,7 +195,10 @@ class SessionInfo:
     """Subset of src/sessions.rs:40-61 that the GPU path owns.  is_local_* / is_self_* and
     dst_service are the values stored when the session was inserted (src/packets.rs:429-466,
     fb_flow_rec.session_flags); status is None on an untimed capture (no clock to age by);
-    is_whitelisted / whitelist_reason are what the last whitelist pass left (Unknown before it)."""
+    is_whitelisted / whitelist_reason are what the last whitelist pass left (Unknown before it), or
+    NonConforming / "Session is blacklisted" where the blacklist pass found the session Unknown
+    (src/capture.rs:1858-1871); criticality holds the sorted "blacklist:<name>" tags of the last
+    blacklist pass (src/blacklists.rs:612-631; "" before it -- there are no anomaly tags)."""
     session: Session
     stats: SessionStats = field(default_factory=SessionStats)
     is_local_src: bool = False
@@ -206,6 +209,7 @@ class SessionInfo:
     status: Optional[SessionStatus] = None
     is_whitelisted: WhitelistState = WhitelistState.Unknown
     whitelist_reason: Optional[str] = None
+    criticality: str = ""
 
 
 _SERVICE_NAMES = None
@@ -310,7 +314,7 @@ def histories_from_records(recs):
     return {k: (h, state.get(k)) for k, h in hist.items()}
 
 
-def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=None):
+def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=None, blacklist=None):
     """fb_flow_rec records -> SessionInfo list sorted by the derived Ord of Session.  `histories`
     ({table slot: str}, FlodbaddGpuCapture.histories) supplies the history strings; the locality
     flags and dst_service come from fb_flow_rec.session_flags (stored at insert, src/packets.rs:
@@ -320,7 +324,10 @@ def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=
     `status` (timed contexts): the status byte of every table slot (fb_flow_status_dev), indexed by
     fb_flow_rec.slot, decoded into SessionInfo.status; a zero byte gives the insert status.
     `whitelist`: the whitelist state byte of every table slot (fb_flow_whitelist_dev), decoded into
-    SessionInfo.is_whitelisted; without it every session is Unknown."""
+    SessionInfo.is_whitelisted; without it every session is Unknown.  A byte with FB_WL_BLACKLISTED
+    carries the reason "Session is blacklisted".  `blacklist`: (the mask word of every table slot,
+    fb_flow_blacklist_dev; the list names), decoded into SessionInfo.criticality."""
+    from .enrich import criticality_of  # (enrich imports this module)
     if flows.dtype != FLOW_REC_DTYPE:
         raise TypeError("expected fb_flow_rec records (FLOW_REC_DTYPE), got %s" % flows.dtype)
     tmap = None
@@ -355,7 +362,12 @@ def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=
         if status is not None:
             info.status = SessionStatus.from_byte(status[int(r["slot"])])
         if whitelist is not None:
-            info.is_whitelisted = WhitelistState.from_byte(whitelist[int(r["slot"])])
+            b = int(whitelist[int(r["slot"])])
+            info.is_whitelisted = WhitelistState.from_byte(b)
+            if b & FB_WL_BLACKLISTED:
+                info.whitelist_reason = "Session is blacklisted"
+        if blacklist is not None:
+            info.criticality = criticality_of(blacklist[0][int(r["slot"])], blacklist[1])
         out.append(info)
     out.sort(key=lambda i: i.session.sort_key())
     return out

@@ -829,6 +829,46 @@ int fb_flow_whitelist_dev(fb_ctx* ctx, uint8_t* d_out, uint64_t cap, void* strea
 int fb_flow_export_whitelist_dev(fb_ctx* ctx, uint32_t state_mask, fb_flow_rec* d_out, uint64_t cap, uint64_t* d_n,
                                  void* stream);
 
+/* ---- blacklist pass over the session table (src/blacklists.rs:456-731, src/capture.rs:1850-1871) ----
+ * recompute_blacklist_for_sessions gives every session the names of the lists one of whose ranges
+ * contains its source or destination address -- an address whose is_local flag was set when the
+ * session was inserted is left out (fb_flow_rec.session_flags, NOT the context's current LAN
+ * configuration, unlike fb_flow_enrich_dev) -- as "blacklist:<name>" tags in `criticality`.  Here the
+ * names are one 64-bit word per table slot, bit l = list l of fb_set_blacklists; zero = not blacklisted,
+ * also the state of a flow no pass has seen (the reference's empty criticality at insert).  The words
+ * follow their flows through a growth and a purge, and fb_flow_clear zeroes them. */
+#define FB_BL_MARK_WHITELIST 1u /* the fallback of src/capture.rs:1858-1871: a blacklisted flow whose
+                                   whitelist state byte is 0 (Unknown) gets FB_WL_NONCONFORMING |
+                                   FB_WL_BLACKLISTED; no other byte of that plane is touched */
+#define FB_WL_BLACKLISTED 8u    /* whitelist state byte: the reason is "Session is blacklisted" (the
+                                   next fb_flow_whitelist replaces the byte, as the reference's pass
+                                   replaces state and reason) */
+typedef struct fb_bl_stats {
+    uint64_t flows;             /* flows in the table                                                  */
+    uint64_t blacklisted;       /* mask != 0 after the call                                            */
+    uint64_t changed;           /* mask differs from before the call (the reference bumps last_modified
+                                   for exactly these, src/blacklists.rs:655-689)                       */
+    uint64_t newly_blacklisted; /* 0 before, != 0 after                                                */
+    uint64_t cleared;           /* != 0 before, 0 after                                                */
+    uint64_t wl_marked;         /* with FB_BL_MARK_WHITELIST: state bytes set by the fallback          */
+    uint64_t reserved[2];
+} fb_bl_stats; /* 64 bytes */
+/* One pass over every flow against the lists installed by fb_set_blacklists (none installed, or n = 0:
+ * valid, every mask becomes 0 -- the reference with an empty list set).  Synchronous: waits for the
+ * updates in flight, like fb_flow_age / fb_flow_whitelist; timed and untimed contexts.  `flags`:
+ * FB_BL_MARK_WHITELIST or 0 (without it the whitelist plane is neither read nor allocated); `out` may be
+ * NULL.  FB_ERR_INVAL for other flag bits or without a flow table. */
+int fb_flow_blacklist(fb_ctx* ctx, uint32_t flags, fb_bl_stats* out, void* stream);
+/* The mask word of every table slot (min(cap, capacity) words, slot order; zeros before the first
+ * pass) into DEVICE memory.  Asynchronous. */
+int fb_flow_blacklist_dev(fb_ctx* ctx, uint64_t* d_out, uint64_t cap, void* stream);
+/* The fb_flow_rec of the flows with a non-zero mask (get_blacklisted_sessions: the caller sorts them by
+ * Session; slot order inside the 256 slots a workgroup compacts at a time, those runs in the order the
+ * workgroups claimed their place), and beside each its mask in d_masks[cap] (may be NULL).  *d_n (device
+ * u64) = the matching flows (only the first `cap` are written).  DEVICE pointers, asynchronous. */
+int fb_flow_export_blacklisted_dev(fb_ctx* ctx, fb_flow_rec* d_out, uint64_t* d_masks, uint64_t cap, uint64_t* d_n,
+                                   void* stream);
+
 /* ---- multi-GPU session table (BASELINE configs[4]) ------------------------------
  * The reference runs one capture task per interface into ONE shared DashMap (src/capture.rs:946-1016,
  * src/packets.rs:329-535); W ranks that each parse a contiguous packet-index shard into their own
