@@ -139,34 +139,10 @@ __global__ __launch_bounds__(kFlowSlots) void k_flow_age(AgeArgs A) {
     A.remap[g] = keep ? (uint32_t)((size_t)p * kFlowSlots + j) : ~0u;
 }
 
-// Growth: the status bytes follow their flows (remap[old slot] = new slot, ~0u: empty), as the time
-// records do (k_time_remap).  T: a status / whitelist byte, or a blacklist mask word (fb_blacklist.hip).
-template <typename T>
-__global__ __launch_bounds__(256) void k_age_remap(const T* old, const uint32_t* remap, unsigned long long old_cap, T* nw) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
-    if (i >= old_cap) return;
-    const uint32_t d = remap[i];
-    if (d != ~0u) nw[d] = old[i];
-}
-
 hipError_t launch_flow_age(const AgeArgs& a, uint32_t parts, hipStream_t s) {
     if (!a.table || !a.plane || !a.status || !a.stats || (a.purge && !a.remap) || parts == 0u)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_flow_age, dim3(parts), dim3(kFlowSlots), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_age_remap(const uint8_t* old, const uint32_t* remap, unsigned long long old_cap, uint8_t* nw,
-                            hipStream_t s) {
-    const unsigned long long g = (old_cap + 255ull) / 256ull;
-    hipLaunchKernelGGL(k_age_remap<uint8_t>, dim3((uint32_t)g), dim3(256), 0, s, old, remap, old_cap, nw);
-    return hipGetLastError();
-}
-
-hipError_t launch_age_remap64(const unsigned long long* old, const uint32_t* remap, unsigned long long old_cap,
-                              unsigned long long* nw, hipStream_t s) {
-    const unsigned long long g = (old_cap + 255ull) / 256ull;
-    hipLaunchKernelGGL(k_age_remap<unsigned long long>, dim3((uint32_t)g), dim3(256), 0, s, old, remap, old_cap, nw);
     return hipGetLastError();
 }
 

@@ -9,9 +9,9 @@
 // two addresses' list masks (bl_lookup over fb_set_blacklists' elementary intervals), so one 64-bit
 // word per flow is the whole answer; the host turns it into the strings.
 //
-// The words live in a plane of their own, one per table slot, like the status plane of fb_age.hip and
-// the state plane of fb_whitelist.hip: FlowSlot and the update kernels are untouched, and a zero word
-// (no pass has seen the flow) is the reference's insert state, an empty criticality.
+// The words live in a per-slot plane of their own: FlowSlot and the update kernels are
+// untouched, and a zero word (no pass has seen the flow) is the reference's insert state, an empty
+// criticality.
 #include "fb_internal.h"
 
 namespace fbk {
@@ -22,13 +22,12 @@ namespace fbk {
 // (flow_lookups of fb_enrich.hip without its ASN half).  The word is stored only when it changed.
 // kMark (FB_BL_MARK_WHITELIST): a flow with a non-zero mask whose whitelist state byte is 0 (Unknown)
 // gets FB_WL_NONCONFORMING | FB_WL_BLACKLISTED; no other byte of that plane is read or written.
-// Counters as in k_flow_whitelist: a ballot per counter per step, one atomic per counter per workgroup.
+// Counters: PassCounters (fb_internal.h).
 template <bool kMark>
 __global__ __launch_bounds__(256) void k_flow_blacklist(const EnrichTables t, const FlowSlot* T, unsigned long long cap,
                                                         unsigned long long* mask, uint8_t* wl,
                                                         unsigned long long* stats) {
-    __shared__ uint32_t s_cnt[4][kBlCounters];
-    uint32_t cnt[kBlCounters] = {0u, 0u, 0u, 0u, 0u, 0u};  // wave-uniform
+    PassCounters<kBlCounters> cnt;
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < cap; base += stride) {
         const unsigned long long i = base + threadIdx.x;
@@ -61,61 +60,28 @@ __global__ __launch_bounds__(256) void k_flow_blacklist(const EnrichTables t, co
                 marked = true;
             }
         }
-        cnt[0] += (uint32_t)__popcll(__ballot(occ));
-        cnt[1] += (uint32_t)__popcll(__ballot(nw != 0ull));
-        cnt[2] += (uint32_t)__popcll(__ballot(nw != old));
-        cnt[3] += (uint32_t)__popcll(__ballot(old == 0ull && nw != 0ull));
-        cnt[4] += (uint32_t)__popcll(__ballot(old != 0ull && nw == 0ull));
-        cnt[5] += (uint32_t)__popcll(__ballot(marked));
+        cnt.add(0, occ);
+        cnt.add(1, nw != 0ull);
+        cnt.add(2, nw != old);
+        cnt.add(3, old == 0ull && nw != 0ull);
+        cnt.add(4, old != 0ull && nw == 0ull);
+        cnt.add(5, marked);
     }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0u)
-        for (uint32_t k = 0; k < kBlCounters; ++k) s_cnt[wave][k] = cnt[k];
-    __syncthreads();
-    if (threadIdx.x < kBlCounters) {  // one atomic per counter per workgroup
-        const unsigned long long s = (unsigned long long)s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] +
-                                     s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
-        if (s) atomicAdd(stats + threadIdx.x, s);
-    }
+    cnt.flush(stats);
 }
 
-// k_flow_export (fb_flow.hip) with "the mask word is not zero" as the predicate: a ballot, one atomic
-// per block, slot order inside a block's step.  out_masks (may be null): the word beside each record.
+// The flows whose mask word is not zero; out_masks (may be null): the word beside each record.
 __global__ __launch_bounds__(256) void k_flow_export_blacklisted(const FlowSlot* T, const unsigned long long* mask,
                                                                  unsigned long long cap, fb_flow_rec* out,
                                                                  unsigned long long* out_masks,
                                                                  unsigned long long out_cap, unsigned long long* d_n,
                                                                  const FlowTime* plane) {
-    __shared__ unsigned long long sh[4];
-    __shared__ unsigned long long s_base;
-    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < cap; base += stride) {
-        const unsigned long long i = base + threadIdx.x;
-        unsigned long long w = 0ull;
-        if (i < cap && T[i].tag >= 2u) w = mask[i];
-        const bool take = w != 0ull;
-        const unsigned long long m = __ballot(take);
-        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-        if (lane == 0u) sh[wave] = __popcll(m);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned long long tot = sh[0] + sh[1] + sh[2] + sh[3];
-            s_base = tot ? atomicAdd(d_n, tot) : 0ull;
-        }
-        __syncthreads();
-        unsigned long long pos = s_base + __popcll(m & ((1ull << lane) - 1ull));
-        for (uint32_t v = 0; v < wave; ++v) pos += sh[v];
-        if (take && pos < out_cap) {
-            fb_flow_rec r = flow_rec_of(T[i], (uint32_t)i);
-            if (plane) {  // a timed context: the segment state with the 5-s timeout (fb_time.hip)
-                r.segment_count = plane[i].segment_count;
-                r.in_segment = plane[i].in_segment;
-            }
-            out[pos] = r;
+    sweep_compact(
+        cap, out_cap, d_n, [=](unsigned long long i) { return T[i].tag >= 2u ? mask[i] : 0ull; },
+        [=](unsigned long long i, unsigned long long pos, unsigned long long w) {
+            out[pos] = flow_rec_at(T, plane, i);
             if (out_masks) out_masks[pos] = w;
-        }
-        __syncthreads();
-    }
+        });
 }
 
 #ifndef FB_BL_GRID
@@ -127,12 +93,11 @@ hipError_t launch_flow_blacklist(const EnrichTables& t, const FlowSlot* table, u
                                  unsigned long long* mask, uint8_t* wl, unsigned long long* stats, hipStream_t s) {
     if (!table || !mask || !stats || cap == 0ull) return hipErrorInvalidValue;
     if ((t.m4 && (!t.bl4_pos || !t.bl4_mask)) || (t.m6 && (!t.bl6_pos || !t.bl6_mask))) return hipErrorInvalidValue;
-    unsigned long long g = (cap + 255ull) / 256ull;
-    if (g > FB_BL_GRID) g = FB_BL_GRID;
+    const dim3 g(sweep_grid(cap, FB_BL_GRID));
     if (wl)
-        hipLaunchKernelGGL(k_flow_blacklist<true>, dim3((uint32_t)g), dim3(256), 0, s, t, table, cap, mask, wl, stats);
+        hipLaunchKernelGGL(k_flow_blacklist<true>, g, dim3(256), 0, s, t, table, cap, mask, wl, stats);
     else
-        hipLaunchKernelGGL(k_flow_blacklist<false>, dim3((uint32_t)g), dim3(256), 0, s, t, table, cap, mask, wl, stats);
+        hipLaunchKernelGGL(k_flow_blacklist<false>, g, dim3(256), 0, s, t, table, cap, mask, wl, stats);
     return hipGetLastError();
 }
 
@@ -140,11 +105,8 @@ hipError_t launch_flow_export_blacklisted(const FlowSlot* table, const unsigned 
                                           fb_flow_rec* out, unsigned long long* out_masks, unsigned long long out_cap,
                                           unsigned long long* d_n, const FlowTime* plane, hipStream_t s) {
     if (!table || !mask || !d_n || (out_cap && !out)) return hipErrorInvalidValue;
-    unsigned long long g = (cap + 255ull) / 256ull;
-    if (g > 1024ull) g = 1024ull;
-    if (g == 0ull) g = 1ull;
-    hipLaunchKernelGGL(k_flow_export_blacklisted, dim3((uint32_t)g), dim3(256), 0, s, table, mask, cap, out, out_masks,
-                       out_cap, d_n, plane);
+    hipLaunchKernelGGL(k_flow_export_blacklisted, dim3(sweep_grid(cap, 1024ull)), dim3(256), 0, s, table, mask, cap,
+                       out, out_masks, out_cap, d_n, plane);
     return hipGetLastError();
 }
 

@@ -53,6 +53,29 @@ struct UpdScratch {
     uint32_t* order = nullptr;     // [flow_parts + kK2Lead + 1] K2's partition order (FlowParams::order)
 };
 
+// Per-slot planes: arrays beside the table, one element per slot, that a flow's element follows through
+// every slot move.  Described once here; the functions below (plane_ensure .. plane_copy_out) are the
+// only code that allocates, moves, clears or frees one, so a new plane is one entry and its pass.
+enum PlaneId : uint32_t { kPlaneTime, kPlaneStatus, kPlaneWl, kPlaneBl, kPlanes };
+struct PlaneDesc {
+    size_t elem;       // bytes per slot
+    const char* name;  // in error text
+    bool lazy;         // made (zeroed) by the first pass that writes it, a zero element standing for "no pass
+                       // has seen the flow": fb_flow_clear zeroes it.  Else: made with a timed context's table,
+                       // and an insert rewrites the element
+    bool age_moves;    // k_flow_age moves it in place with the slots of a purge; else it follows through the
+                       // slot map the purge publishes
+    hipError_t (*remap)(const void* old, const uint32_t* remap, unsigned long long old_cap, void* nw, hipStream_t s);
+};
+static const PlaneDesc kPlaneDesc[kPlanes] = {
+    {sizeof(FlowTime), "time plane", false, true, launch_plane_remap<FlowTime>},        // fb_time.hip
+    {1, "status plane", true, true, launch_plane_remap<uint8_t>},                       // fb_age.hip, kAge*
+    {1, "whitelist plane", true, false, launch_plane_remap<uint8_t>},                   // fb_whitelist.hip, FB_WL_*
+    {8, "blacklist plane", true, false, launch_plane_remap<unsigned long long>},        // fb_blacklist.hip
+};
+// the counter words of one synchronous pass over the table (pass_begin / pass_end)
+constexpr uint32_t kPassStatWords = std::max({kAgeStatWords, kWlCounters, kBlCounters});
+
 struct fb_ctx {
     int device = 0;
     DevConfig* h_cfg = nullptr;  // host shadow
@@ -103,35 +126,29 @@ struct fb_ctx {
     bool grow = true;               // FB_CFG_FIXED_TABLE clears it
     uint32_t* d_remap = nullptr;    // the last growth's old -> new slot map
     uint4* d_char_call = nullptr;   // [table_cap] first update call of S s H h per slot (the merge's)
-    // timed contexts (FB_CFG_TIMED, fb_time.hip): the time plane, the next update's frame times, the
-    // capture-time pass's scratch (its last use: ev_tscratch)
+    void* d_plane[kPlanes] = {};    // [table_cap] each (kPlaneDesc); null: not made yet
+    template <typename T>
+    T* plane(PlaneId p) const { return static_cast<T*>(d_plane[p]); }
+    unsigned long long* d_pass_stats = nullptr;  // [kPassStatWords]
+    // timed contexts (FB_CFG_TIMED, fb_time.hip): the next update's frame times, the capture-time pass's
+    // scratch (its last use: ev_tscratch)
     bool timed = false;
-    FlowTime* d_time = nullptr;               // [table_cap]
     const unsigned long long* next_ts = nullptr;
     void* d_tscratch = nullptr;
     uint64_t tscratch_bytes = 0;
     hipEvent_t ev_tscratch = nullptr;
-    // session aging (fb_flow_age, fb_age.hip): the status plane (allocated by the first aging call), the
-    // call's counters, and the buffer the next purge writes its slot map into (swapped with d_remap
-    // when the purge removed something)
-    uint8_t* d_status = nullptr;               // [table_cap]
-    unsigned long long* d_age_stats = nullptr; // [kAgeStatWords]
+    // session aging (fb_flow_age, fb_age.hip): the buffer the next purge writes its slot map into (swapped
+    // with d_remap when the purge removed something)
     uint32_t* d_age_remap = nullptr;
     uint64_t age_remap_n = 0;
     // whitelist conformance (fb_set_whitelist / fb_flow_whitelist, fb_whitelist.hip): the installed
-    // list's index, the state plane (allocated by the first pass) and the pass's counters
+    // list's index
     bool wl_active = false;
     uint32_t *d_wl_a4 = nullptr, *d_wl_k4 = nullptr, *d_wl_k6 = nullptr, *d_wl_gkey = nullptr, *d_wl_gbeg = nullptr;
     uint4* d_wl_a6 = nullptr;
     WlRule* d_wl_rules = nullptr;
     uint32_t *d_wl_owner = nullptr, *d_wl_country = nullptr;
     uint32_t wl_n4 = 0, wl_n6 = 0, wl_ng = 0, wl_nr = 0, wl_records = 0;
-    uint8_t* d_wl_state = nullptr;             // [table_cap]
-    unsigned long long* d_wl_stats = nullptr;  // [kWlCounters]
-    // blacklist pass (fb_flow_blacklist, fb_blacklist.hip): the mask plane (allocated by the first pass)
-    // and the pass's counters
-    unsigned long long* d_bl_mask = nullptr;   // [table_cap]
-    unsigned long long* d_bl_stats = nullptr;  // [kBlCounters]
     void* d_mscratch = nullptr;   // multi-GPU merge scratch (export owner counts / merge tables)
     hipEvent_t ev_mscratch = nullptr;  // after the last export / merge that used d_mscratch (either may
                                        // run on any stream: the next use waits for it)
@@ -231,6 +248,114 @@ static int guard_next_error_word(fb_ctx* c, hipStream_t s) {
 static int drain_updates(fb_ctx* c) {
     if (c->async_k && c->upd) HIP_TRY(hipStreamSynchronize(c->upd));
     if (c->hist_pending) HIP_TRY(hipEventSynchronize(c->ev_hist));  // (before scratch is freed)
+    return FB_OK;
+}
+
+// ---- per-slot planes (kPlaneDesc) ----------------------------------------------------------------
+static hipError_t plane_zero(fb_ctx* c, PlaneId p, hipStream_t s) {
+    return c->d_plane[p] ? hipMemsetAsync(c->d_plane[p], 0, c->table_cap * kPlaneDesc[p].elem, s) : hipSuccess;
+}
+// The plane exists (made zeroed when it does not).
+static int plane_ensure(fb_ctx* c, PlaneId p, hipStream_t s) {
+    if (c->d_plane[p]) return FB_OK;
+    if (hipMalloc(&c->d_plane[p], c->table_cap * kPlaneDesc[p].elem) != hipSuccess) {
+        c->d_plane[p] = nullptr;
+        return set_err(FB_ERR_NOMEM, "%s", kPlaneDesc[p].name);
+    }
+    HIP_TRY(plane_zero(c, p, s));
+    return FB_OK;
+}
+// A slot move (remap[old slot] = new slot, ~0u: none) into a table of new_cap slots: nw, new_cap elements
+// the caller allocated, is zeroed and every element put at its flow's new slot.
+static hipError_t plane_move(const fb_ctx* c, PlaneId p, const uint32_t* remap, uint64_t new_cap, hipStream_t s,
+                             void* nw) {
+    const hipError_t e = hipMemsetAsync(nw, 0, new_cap * kPlaneDesc[p].elem, s);
+    return e != hipSuccess ? e : kPlaneDesc[p].remap(c->d_plane[p], remap, c->table_cap, nw, s);
+}
+// After a purge that moved slots: the planes k_flow_age does not move itself follow through the slot map
+// it published (c->d_remap).  A plane whose move failed is dropped -- every flow reads as unseen /
+// Unknown again -- rather than left behind its flows, and the call reports the error.
+static int planes_follow_purge(fb_ctx* c, hipStream_t s) {
+    int rc = FB_OK;
+    for (uint32_t p = 0; p < kPlanes; ++p) {
+        if (kPlaneDesc[p].age_moves || !c->d_plane[p]) continue;
+        void* nw = nullptr;
+        hipError_t e = hipMalloc(&nw, c->table_cap * kPlaneDesc[p].elem);
+        if (e == hipSuccess) e = plane_move(c, (PlaneId)p, c->d_remap, c->table_cap, s, nw);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            hipFree(nw);
+            nw = nullptr;
+            if (!rc) rc = set_err(FB_ERR_HIP, "%s remap: %s", kPlaneDesc[p].name, hipGetErrorString(e));
+        }
+        hipFree(c->d_plane[p]);
+        c->d_plane[p] = nw;
+    }
+    return rc;
+}
+// fb_flow_clear: every flow is gone, so the lazily made planes read "unseen" everywhere.
+static int planes_clear(fb_ctx* c, hipStream_t s) {
+    for (uint32_t p = 0; p < kPlanes; ++p)
+        if (kPlaneDesc[p].lazy) HIP_TRY(plane_zero(c, (PlaneId)p, s));
+    return FB_OK;
+}
+static void planes_free(fb_ctx* c) {
+    for (void*& p : c->d_plane) {
+        hipFree(p);
+        p = nullptr;
+    }
+}
+// The fb_flow_*_dev getters: min(cap, table capacity) elements; a plane no pass has made reads zeros.
+static int plane_copy_out(fb_ctx* c, PlaneId p, void* d_out, uint64_t cap, void* stream) {
+    if (!c || (cap && !d_out)) return set_err(FB_ERR_INVAL, "bad arguments");
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t bytes = std::min<uint64_t>(cap, c->table_cap) * kPlaneDesc[p].elem;
+    if (bytes == 0) return FB_OK;
+    if (c->d_plane[p])
+        HIP_TRY(hipMemcpyAsync(d_out, c->d_plane[p], bytes, hipMemcpyDeviceToDevice, s));
+    else
+        HIP_TRY(hipMemsetAsync(d_out, 0, bytes, s));
+    return FB_OK;
+}
+
+// A synchronous pass over the table (fb_flow_age / _whitelist / _blacklist) drains the updates in flight
+// and starts from `words` zeroed counter words; pass_end reads them back once the pass has run.
+static int pass_begin(fb_ctx* c, uint32_t words, hipStream_t s) {
+    const int rc = drain_updates(c);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!c->d_pass_stats && hipMalloc(&c->d_pass_stats, kPassStatWords * 8ull) != hipSuccess) {
+        c->d_pass_stats = nullptr;
+        return set_err(FB_ERR_NOMEM, "pass counters");
+    }
+    HIP_TRY(hipMemsetAsync(c->d_pass_stats, 0, words * 8ull, s));
+    return FB_OK;
+}
+static int pass_end(fb_ctx* c, unsigned long long* h, uint32_t words, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(h, c->d_pass_stats, words * 8ull, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return FB_OK;
+}
+
+// The host form of a compacting export: a device buffer of `cap` records of `rec` bytes, the _dev export
+// into it (run(d_out), counting into c->d_n), the count read back, min(count, cap) records copied out.
+template <typename Run>
+static int export_to_host(fb_ctx* c, void* out, uint64_t cap, size_t rec, uint64_t* n, hipStream_t s, const char* what,
+                          Run run) {
+    void* d_out = nullptr;
+    if (hipMalloc(&d_out, cap * rec) != hipSuccess) return set_err(FB_ERR_NOMEM, "export buffer");
+    unsigned long long h = 0;
+    const int rc = run(d_out);
+    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(&h, c->d_n, 8, hipMemcpyDeviceToHost, s);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(s);
+    const uint64_t got = std::min<uint64_t>(h, cap);
+    if (!rc && e == hipSuccess && got) e = hipMemcpyAsync(out, d_out, got * rec, hipMemcpyDeviceToHost, s);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(s);
+    hipFree(d_out);
+    if (rc) return rc;
+    if (e != hipSuccess) return set_err(FB_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    *n = got;
     return FB_OK;
 }
 
@@ -522,9 +647,8 @@ fb_ctx* fb_create(int device, const fb_config* cfg) {
         if (ok) memset(c->h_mbox, 0, sizeof(FlowMailbox));
         c->grow = (cfg->flags & FB_CFG_FIXED_TABLE) == 0u;
         c->timed = (cfg->flags & FB_CFG_TIMED) != 0u;
-        if (ok && c->timed)
-            ok = hipMalloc(&c->d_time, cap * sizeof(FlowTime)) == hipSuccess &&
-                 hipMemset(c->d_time, 0, cap * sizeof(FlowTime)) == hipSuccess &&
+        if (ok && c->timed)  // (zeroed on the null stream, which upload_cfg below synchronises before the return)
+            ok = plane_ensure(c, kPlaneTime, nullptr) == FB_OK &&
                  hipEventCreateWithFlags(&c->ev_tscratch, hipEventDisableTiming) == hipSuccess;
         ok = ok && ensure_flow_scratch(c, cfg->max_batch_packets, nullptr) == FB_OK;
     }
@@ -554,11 +678,10 @@ int fb_destroy(fb_ctx* c) {
     hipFree(c->d_partials);
     hipFree(c->d_remap);
     hipFree(c->d_char_call);
-    hipFree(c->d_time);
+    planes_free(c);
+    hipFree(c->d_pass_stats);
     hipFree(c->d_tscratch);
     if (c->ev_tscratch) hipEventDestroy(c->ev_tscratch);
-    hipFree(c->d_status);
-    hipFree(c->d_age_stats);
     hipFree(c->d_age_remap);
     hipFree(c->d_wl_a4);
     hipFree(c->d_wl_k4);
@@ -569,10 +692,6 @@ int fb_destroy(fb_ctx* c) {
     hipFree(c->d_wl_rules);
     hipFree(c->d_wl_owner);
     hipFree(c->d_wl_country);
-    hipFree(c->d_wl_state);
-    hipFree(c->d_wl_stats);
-    hipFree(c->d_bl_mask);
-    hipFree(c->d_bl_stats);
     hipFree(c->d_mscratch);
     if (c->ev_mscratch) hipEventDestroy(c->ev_mscratch);
     if (c->h_mbox) hipHostFree(c->h_mbox);
@@ -1359,125 +1478,57 @@ static int empty_update(fb_ctx* c) {
 // ---- table growth -------------------------------------------------------------------------------
 // Doubles the table on the device: every slot re-inserted into 2x partitions (k_flow_grow), the old
 // -> new slot map kept for fb_flow_slot_remap.  Drains the updates in flight first: growth is rare.
+// Every buffer of the grown table is held by a Grown until the growth is complete; only then are the
+// context's pointers swapped in (the Grown then holds the old buffers), and whatever it holds when it
+// goes out of scope is freed -- a failed growth leaves the context as it was.
+namespace {
+struct Grown {
+    FlowSlot* table = nullptr;
+    unsigned long long* partials = nullptr;
+    uint32_t *hcount = nullptr, *part_base = nullptr, *hist_slow = nullptr, *remap = nullptr;
+    uint4* char_call = nullptr;
+    void* plane[kPlanes] = {};
+    ~Grown() {
+        for (void* p : {(void*)table, (void*)partials, (void*)hcount, (void*)part_base, (void*)hist_slow, (void*)remap,
+                        (void*)char_call})
+            hipFree(p);
+        for (void* p : plane) hipFree(p);
+    }
+};
+}  // namespace
 static int grow_table(fb_ctx* c, hipStream_t s, uint32_t k) {
     int rc = drain_updates(c);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(s));
-    const uint64_t cap = c->table_cap << k;
-    FlowSlot* nw = nullptr;
-    unsigned long long* partials = nullptr;
-    if (hipMalloc(&nw, cap * sizeof(FlowSlot)) != hipSuccess) return set_err(FB_ERR_NOMEM, "grown flow table");
-    uint32_t *hcount = nullptr, *part_base = nullptr, *hist_slow = nullptr;
-    auto free_new = [&]() {
-        hipFree(partials);
-        hipFree(hcount);
-        hipFree(part_base);
-        hipFree(hist_slow);
-    };
-    if (hipMalloc(&partials, 4ull * (cap / kFlowSlots) * 8ull) != hipSuccess ||
-        hipMalloc(&hcount, cap * 4ull) != hipSuccess ||
-        hipMalloc(&part_base, (cap / kFlowSlots + 1ull) * 4ull) != hipSuccess ||
-        hipMalloc(&hist_slow, (cap / kFlowSlots + 1ull) * 4ull) != hipSuccess) {
-        free_new();
-        hipFree(nw);
+    const uint64_t cap = c->table_cap << k, parts = cap / kFlowSlots;
+    Grown g;
+    if (hipMalloc(&g.table, cap * sizeof(FlowSlot)) != hipSuccess) return set_err(FB_ERR_NOMEM, "grown flow table");
+    if (hipMalloc(&g.partials, 4ull * parts * 8ull) != hipSuccess || hipMalloc(&g.hcount, cap * 4ull) != hipSuccess ||
+        hipMalloc(&g.part_base, (parts + 1ull) * 4ull) != hipSuccess ||
+        hipMalloc(&g.hist_slow, (parts + 1ull) * 4ull) != hipSuccess)
         return set_err(FB_ERR_NOMEM, "grown flow table partials");
-    }
-    hipFree(c->d_remap);
-    c->d_remap = nullptr;
-    c->remap_n = 0;
-    if (hipMalloc(&c->d_remap, c->table_cap * 4ull) != hipSuccess) {
-        hipFree(nw);
-        free_new();
-        return set_err(FB_ERR_NOMEM, "slot remap");
-    }
-    HIP_TRY(hipMemsetAsync(nw, 0, cap * sizeof(FlowSlot), s));
-    uint4* nw_cc = nullptr;
-    if (hipMalloc(&nw_cc, cap * sizeof(uint4)) != hipSuccess) {
-        hipFree(nw);
-        free_new();
+    if (hipMalloc(&g.remap, c->table_cap * 4ull) != hipSuccess) return set_err(FB_ERR_NOMEM, "slot remap");
+    if (hipMalloc(&g.char_call, cap * sizeof(uint4)) != hipSuccess)
         return set_err(FB_ERR_NOMEM, "grown character-call array");
-    }
-    HIP_TRY(launch_flow_grow(c->d_table, c->flow_parts, k, c->flow_shift - k, nw, c->d_remap, c->d_char_call, nw_cc,
-                             s));
-    FlowTime* nw_time = nullptr;
-    if (c->timed) {  // the time records follow their flows' new slots
-        if (hipMalloc(&nw_time, cap * sizeof(FlowTime)) != hipSuccess) {
-            hipFree(nw);
-            hipFree(nw_cc);
-            free_new();
-            return set_err(FB_ERR_NOMEM, "grown time plane");
-        }
-        HIP_TRY(hipMemsetAsync(nw_time, 0, cap * sizeof(FlowTime), s));
-        HIP_TRY(launch_time_remap(c->d_time, c->d_remap, c->table_cap, nw_time, s));
-    }
-    uint8_t* nw_status = nullptr;
-    if (c->d_status) {  // ... and so do the status bytes of the aging calls so far (fb_age.hip)
-        if (hipMalloc(&nw_status, cap) != hipSuccess) {
-            hipFree(nw);
-            hipFree(nw_cc);
-            hipFree(nw_time);
-            free_new();
-            return set_err(FB_ERR_NOMEM, "grown status plane");
-        }
-        HIP_TRY(hipMemsetAsync(nw_status, 0, cap, s));
-        HIP_TRY(launch_age_remap(c->d_status, c->d_remap, c->table_cap, nw_status, s));
-    }
-    uint8_t* nw_wl = nullptr;
-    if (c->d_wl_state) {  // ... and the whitelist states (fb_whitelist.hip): the same byte remap
-        if (hipMalloc(&nw_wl, cap) != hipSuccess) {
-            hipFree(nw);
-            hipFree(nw_cc);
-            hipFree(nw_time);
-            hipFree(nw_status);
-            free_new();
-            return set_err(FB_ERR_NOMEM, "grown whitelist plane");
-        }
-        HIP_TRY(hipMemsetAsync(nw_wl, 0, cap, s));
-        HIP_TRY(launch_age_remap(c->d_wl_state, c->d_remap, c->table_cap, nw_wl, s));
-    }
-    unsigned long long* nw_bl = nullptr;
-    if (c->d_bl_mask) {  // ... and the blacklist masks (fb_blacklist.hip): the 8-byte remap
-        if (hipMalloc(&nw_bl, cap * 8ull) != hipSuccess) {
-            hipFree(nw);
-            hipFree(nw_cc);
-            hipFree(nw_time);
-            hipFree(nw_status);
-            hipFree(nw_wl);
-            free_new();
-            return set_err(FB_ERR_NOMEM, "grown blacklist plane");
-        }
-        HIP_TRY(hipMemsetAsync(nw_bl, 0, cap * 8ull, s));
-        HIP_TRY(launch_age_remap64(c->d_bl_mask, c->d_remap, c->table_cap, nw_bl, s));
+    HIP_TRY(hipMemsetAsync(g.table, 0, cap * sizeof(FlowSlot), s));
+    HIP_TRY(launch_flow_grow(c->d_table, c->flow_parts, k, c->flow_shift - k, g.table, g.remap, c->d_char_call,
+                             g.char_call, s));
+    for (uint32_t p = 0; p < kPlanes; ++p) {  // every plane made so far follows its flows' new slots
+        if (!c->d_plane[p]) continue;
+        if (hipMalloc(&g.plane[p], cap * kPlaneDesc[p].elem) != hipSuccess)
+            return set_err(FB_ERR_NOMEM, "grown %s", kPlaneDesc[p].name);
+        HIP_TRY(plane_move(c, (PlaneId)p, g.remap, cap, s, g.plane[p]));
     }
     HIP_TRY(hipStreamSynchronize(s));
-    if (nw_wl) {
-        hipFree(c->d_wl_state);
-        c->d_wl_state = nw_wl;
-    }
-    if (nw_bl) {
-        hipFree(c->d_bl_mask);
-        c->d_bl_mask = nw_bl;
-    }
-    if (c->timed) {
-        hipFree(c->d_time);
-        c->d_time = nw_time;
-    }
-    if (nw_status) {
-        hipFree(c->d_status);
-        c->d_status = nw_status;
-    }
-    hipFree(c->d_table);
-    hipFree(c->d_partials);
-    hipFree(c->d_hcount);
-    hipFree(c->d_part_base);
-    hipFree(c->d_hist_slow);
-    c->d_table = nw;
-    hipFree(c->d_char_call);
-    c->d_char_call = nw_cc;
-    c->d_partials = partials;
-    c->d_hcount = hcount;
-    c->d_part_base = part_base;
-    c->d_hist_slow = hist_slow;
+    std::swap(c->d_table, g.table);
+    std::swap(c->d_partials, g.partials);
+    std::swap(c->d_hcount, g.hcount);
+    std::swap(c->d_part_base, g.part_base);
+    std::swap(c->d_hist_slow, g.hist_slow);
+    std::swap(c->d_remap, g.remap);
+    std::swap(c->d_char_call, g.char_call);
+    for (uint32_t p = 0; p < kPlanes; ++p)
+        if (g.plane[p]) std::swap(c->d_plane[p], g.plane[p]);
     c->remap_n = c->table_cap;
     c->table_cap = cap;
     c->flow_parts <<= k;
@@ -1633,7 +1684,7 @@ static int flow_update(fb_ctx* c, const fb_pkt_out* d_recs, const uint32_t* d_se
                                ++c->upd_seq, s));
     if (c->timed) {  // the capture-time pass over the placed records (fb_time.hip)
         const uint32_t slots = p.max_recs < n_slots ? p.max_recs : n_slots;
-        HIP_TRY(launch_time_update(p, slots, c->table_cap, c->d_time, c->next_ts, c->d_tscratch, s));
+        HIP_TRY(launch_time_update(p, slots, c->table_cap, c->plane<FlowTime>(kPlaneTime), c->next_ts, c->d_tscratch, s));
         HIP_TRY(hipEventRecord(c->ev_tscratch, s));
         c->next_ts = nullptr;
     }
@@ -1921,7 +1972,7 @@ int fb_flow_export_sessions_dev(fb_ctx* c, uint32_t filter, fb_flow_rec* d_out, 
     if (!rc && filter != FB_FILTER_ALL) rc = upload_cfg(c, s);  // the LAN configuration as of now
     if (rc) return rc;
     HIP_TRY(launch_flow_export(c->d_table, c->table_cap, d_out, cap, (unsigned long long*)d_n, s, filter, c->d_cfg,
-                               c->d_time));
+                               c->plane<FlowTime>(kPlaneTime)));
     return FB_OK;
 }
 
@@ -1933,7 +1984,8 @@ int fb_flow_export_times_dev(fb_ctx* c, fb_flow_time* d_out, uint64_t cap, uint6
     HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
     int rc = join_updates(c, s);
     if (rc) return rc;
-    HIP_TRY(launch_time_export(c->d_table, c->d_time, c->table_cap, d_out, cap, (unsigned long long*)d_n, s));
+    HIP_TRY(launch_time_export(c->d_table, c->plane<FlowTime>(kPlaneTime), c->table_cap, d_out, cap,
+                               (unsigned long long*)d_n, s));
     return FB_OK;
 }
 
@@ -1943,21 +1995,9 @@ int fb_flow_export_times(fb_ctx* c, fb_flow_time* out, uint64_t cap, uint64_t* n
     if (!c->timed) return set_err(FB_ERR_INVAL, "the context was created without FB_CFG_TIMED");
     if (cap == 0) return FB_OK;
     DeviceGuard g(c->device);
-    hipStream_t s = (hipStream_t)stream;
-    fb_flow_time* d_out = nullptr;
-    if (hipMalloc(&d_out, cap * sizeof(fb_flow_time)) != hipSuccess) return set_err(FB_ERR_NOMEM, "export buffer");
-    unsigned long long h = 0;
-    int rc = fb_flow_export_times_dev(c, d_out, cap, reinterpret_cast<uint64_t*>(c->d_n), stream);
-    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(&h, c->d_n, 8, hipMemcpyDeviceToHost, s);
-    if (!rc && e == hipSuccess) e = hipStreamSynchronize(s);
-    const uint64_t got = std::min<uint64_t>(h, cap);
-    if (!rc && e == hipSuccess && got) e = hipMemcpyAsync(out, d_out, got * sizeof(fb_flow_time), hipMemcpyDeviceToHost, s);
-    if (!rc && e == hipSuccess) e = hipStreamSynchronize(s);
-    hipFree(d_out);
-    if (rc) return rc;
-    if (e != hipSuccess) return set_err(FB_ERR_HIP, "time export: %s", hipGetErrorString(e));
-    *n = got;
-    return FB_OK;
+    return export_to_host(c, out, cap, sizeof(fb_flow_time), n, (hipStream_t)stream, "time export", [&](void* d_out) {
+        return fb_flow_export_times_dev(c, (fb_flow_time*)d_out, cap, reinterpret_cast<uint64_t*>(c->d_n), stream);
+    });
 }
 
 int fb_flow_export_dev(fb_ctx* c, fb_flow_rec* d_out, uint64_t cap, uint64_t* d_n, void* stream) {
@@ -1981,20 +2021,9 @@ int fb_flow_age(fb_ctx* c, uint64_t now_ns, const fb_age_params* params, uint32_
     const bool purge = (flags & FB_AGE_PURGE) != 0u;
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
-    int rc = drain_updates(c);
+    int rc = pass_begin(c, kAgeStatWords, s);
+    if (!rc) rc = plane_ensure(c, kPlaneStatus, s);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    if (!c->d_status) {
-        if (hipMalloc(&c->d_status, c->table_cap) != hipSuccess) {
-            c->d_status = nullptr;
-            return set_err(FB_ERR_NOMEM, "status plane");
-        }
-        HIP_TRY(hipMemsetAsync(c->d_status, 0, c->table_cap, s));
-    }
-    if (!c->d_age_stats && hipMalloc(&c->d_age_stats, kAgeStatWords * 8ull) != hipSuccess) {
-        c->d_age_stats = nullptr;
-        return set_err(FB_ERR_NOMEM, "aging counters");
-    }
     if (purge && c->age_remap_n != c->table_cap) {
         hipFree(c->d_age_remap);
         c->d_age_remap = nullptr;
@@ -2005,14 +2034,13 @@ int fb_flow_age(fb_ctx* c, uint64_t now_ns, const fb_age_params* params, uint32_
         }
         c->age_remap_n = c->table_cap;
     }
-    HIP_TRY(hipMemsetAsync(c->d_age_stats, 0, kAgeStatWords * 8ull, s));
     AgeArgs a;
     a.table = c->d_table;
-    a.plane = c->d_time;
+    a.plane = c->plane<FlowTime>(kPlaneTime);
     a.char_call = c->d_char_call;
-    a.status = c->d_status;
+    a.status = c->plane<uint8_t>(kPlaneStatus);
     a.remap = purge ? c->d_age_remap : nullptr;
-    a.stats = c->d_age_stats;
+    a.stats = c->d_pass_stats;
     a.now = now_ns;
     a.activity = ap.activity_ns;
     a.current = ap.current_ns;
@@ -2020,8 +2048,8 @@ int fb_flow_age(fb_ctx* c, uint64_t now_ns, const fb_age_params* params, uint32_
     a.purge = purge ? 1u : 0u;
     HIP_TRY(launch_flow_age(a, c->flow_parts, s));
     unsigned long long h[kAgeStatWords] = {};
-    HIP_TRY(hipMemcpyAsync(h, c->d_age_stats, sizeof(h), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    rc = pass_end(c, h, kAgeStatWords, s);
+    if (rc) return rc;
     if (h[6]) {  // flows were removed: survivors of their partitions may have moved
         std::swap(c->d_remap, c->d_age_remap);
         c->age_remap_n = c->d_age_remap ? c->remap_n : 0;  // (the old map's size; reallocated if it differs)
@@ -2031,34 +2059,8 @@ int fb_flow_age(fb_ctx* c, uint64_t now_ns, const fb_age_params* params, uint32_
         c->last_part = nullptr;
         c->h_mbox->flows = h[7];
         c->h_mbox->max_part = h[8];
-        if (c->d_wl_state) {  // the whitelist states follow their flows through the published slot map
-            // (on a failure the plane is dropped -- every flow Unknown again -- rather than left behind
-            // its flows)
-            uint8_t* nw_wl = nullptr;
-            hipError_t e = hipMalloc(&nw_wl, c->table_cap);
-            if (e == hipSuccess) e = hipMemsetAsync(nw_wl, 0, c->table_cap, s);
-            if (e == hipSuccess) e = launch_age_remap(c->d_wl_state, c->d_remap, c->table_cap, nw_wl, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            hipFree(c->d_wl_state);
-            c->d_wl_state = e == hipSuccess ? nw_wl : nullptr;
-            if (e != hipSuccess) {
-                hipFree(nw_wl);
-                return set_err(FB_ERR_HIP, "whitelist plane remap: %s", hipGetErrorString(e));
-            }
-        }
-        if (c->d_bl_mask) {  // ... and so do the blacklist masks (dropped on a failure: every flow unseen again)
-            unsigned long long* nw_bl = nullptr;
-            hipError_t e = hipMalloc(&nw_bl, c->table_cap * 8ull);
-            if (e == hipSuccess) e = hipMemsetAsync(nw_bl, 0, c->table_cap * 8ull, s);
-            if (e == hipSuccess) e = launch_age_remap64(c->d_bl_mask, c->d_remap, c->table_cap, nw_bl, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            hipFree(c->d_bl_mask);
-            c->d_bl_mask = e == hipSuccess ? nw_bl : nullptr;
-            if (e != hipSuccess) {
-                hipFree(nw_bl);
-                return set_err(FB_ERR_HIP, "blacklist plane remap: %s", hipGetErrorString(e));
-            }
-        }
+        rc = planes_follow_purge(c, s);
+        if (rc) return rc;
     }
     if (out) {
         memset(out, 0, sizeof(*out));
@@ -2076,16 +2078,7 @@ int fb_flow_age(fb_ctx* c, uint64_t now_ns, const fb_age_params* params, uint32_
 }
 
 int fb_flow_status_dev(fb_ctx* c, uint8_t* d_out, uint64_t cap, void* stream) {
-    if (!c || (cap && !d_out)) return set_err(FB_ERR_INVAL, "bad arguments");
-    DeviceGuard g(c->device);
-    hipStream_t s = (hipStream_t)stream;
-    const uint64_t m = std::min<uint64_t>(cap, c->table_cap);
-    if (m == 0) return FB_OK;
-    if (c->d_status)
-        HIP_TRY(hipMemcpyAsync(d_out, c->d_status, m, hipMemcpyDeviceToDevice, s));
-    else
-        HIP_TRY(hipMemsetAsync(d_out, 0, m, s));
-    return FB_OK;
+    return plane_copy_out(c, kPlaneStatus, d_out, cap, stream);
 }
 
 // ---- whitelist conformance (fb_whitelist.hip) -----------------------------------------------------
@@ -2128,7 +2121,8 @@ int fb_clear_whitelist(fb_ctx* c) {
     DeviceGuard g(c->device);
     HIP_TRY(hipDeviceSynchronize());
     c->wl_active = false;
-    if (c->d_wl_state) HIP_TRY(hipMemset(c->d_wl_state, 0, c->table_cap));  // every state back to Unknown
+    HIP_TRY(plane_zero(c, kPlaneWl, nullptr));  // every state back to Unknown
+    HIP_TRY(hipStreamSynchronize(nullptr));
     return FB_OK;
 }
 
@@ -2140,23 +2134,10 @@ int fb_flow_whitelist(fb_ctx* c, uint32_t flags, fb_wl_stats* out, void* stream)
     if (flags) return set_err(FB_ERR_INVAL, "unknown flags %u", flags);
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
-    int rc = drain_updates(c);
+    int rc = pass_begin(c, kWlCounters, s);
+    if (!rc) rc = upload_cfg(c, s);  // the LAN configuration as of now
+    if (!rc) rc = plane_ensure(c, kPlaneWl, s);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    rc = upload_cfg(c, s);  // the LAN configuration as of now
-    if (rc) return rc;
-    if (!c->d_wl_state) {
-        if (hipMalloc(&c->d_wl_state, c->table_cap) != hipSuccess) {
-            c->d_wl_state = nullptr;
-            return set_err(FB_ERR_NOMEM, "whitelist plane");
-        }
-        HIP_TRY(hipMemsetAsync(c->d_wl_state, 0, c->table_cap, s));
-    }
-    if (!c->d_wl_stats && hipMalloc(&c->d_wl_stats, kWlCounters * 8ull) != hipSuccess) {
-        c->d_wl_stats = nullptr;
-        return set_err(FB_ERR_NOMEM, "whitelist counters");
-    }
-    HIP_TRY(hipMemsetAsync(c->d_wl_stats, 0, kWlCounters * 8ull, s));
     WlTables w;
     w.a4 = c->d_wl_a4;
     w.k4 = c->d_wl_k4;
@@ -2172,10 +2153,11 @@ int fb_flow_whitelist(fb_ctx* c, uint32_t flags, fb_wl_stats* out, void* stream)
     w.ng = c->wl_ng;
     w.nr = c->wl_nr;
     w.n_records = c->wl_records;
-    HIP_TRY(launch_flow_whitelist(w, enrich_tables(c), c->d_cfg, c->d_table, c->table_cap, c->d_wl_state, c->d_wl_stats, s));
+    HIP_TRY(launch_flow_whitelist(w, enrich_tables(c), c->d_cfg, c->d_table, c->table_cap, c->plane<uint8_t>(kPlaneWl),
+                                  c->d_pass_stats, s));
     unsigned long long h[kWlCounters] = {};
-    HIP_TRY(hipMemcpyAsync(h, c->d_wl_stats, sizeof(h), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    rc = pass_end(c, h, kWlCounters, s);
+    if (rc) return rc;
     if (out) {
         memset(out, 0, sizeof(*out));
         out->flows = h[0];
@@ -2188,16 +2170,7 @@ int fb_flow_whitelist(fb_ctx* c, uint32_t flags, fb_wl_stats* out, void* stream)
 }
 
 int fb_flow_whitelist_dev(fb_ctx* c, uint8_t* d_out, uint64_t cap, void* stream) {
-    if (!c || (cap && !d_out)) return set_err(FB_ERR_INVAL, "bad arguments");
-    DeviceGuard g(c->device);
-    hipStream_t s = (hipStream_t)stream;
-    const uint64_t m = std::min<uint64_t>(cap, c->table_cap);
-    if (m == 0) return FB_OK;
-    if (c->d_wl_state)
-        HIP_TRY(hipMemcpyAsync(d_out, c->d_wl_state, m, hipMemcpyDeviceToDevice, s));
-    else
-        HIP_TRY(hipMemsetAsync(d_out, 0, m, s));
-    return FB_OK;
+    return plane_copy_out(c, kPlaneWl, d_out, cap, stream);
 }
 
 int fb_flow_export_whitelist_dev(fb_ctx* c, uint32_t state_mask, fb_flow_rec* d_out, uint64_t cap, uint64_t* d_n,
@@ -2211,8 +2184,8 @@ int fb_flow_export_whitelist_dev(fb_ctx* c, uint32_t state_mask, fb_flow_rec* d_
     if (!c->d_table) return FB_OK;
     const int rc = join_updates(c, s);
     if (rc) return rc;
-    HIP_TRY(launch_flow_export_whitelist(c->d_table, c->d_wl_state, c->table_cap, state_mask, d_out, cap,
-                                         (unsigned long long*)d_n, c->d_time, s));
+    HIP_TRY(launch_flow_export_whitelist(c->d_table, c->plane<uint8_t>(kPlaneWl), c->table_cap, state_mask, d_out, cap,
+                                         (unsigned long long*)d_n, c->plane<FlowTime>(kPlaneTime), s));
     return FB_OK;
 }
 
@@ -2226,33 +2199,16 @@ int fb_flow_blacklist(fb_ctx* c, uint32_t flags, fb_bl_stats* out, void* stream)
     const bool mark = (flags & FB_BL_MARK_WHITELIST) != 0u;
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
-    int rc = drain_updates(c);
+    int rc = pass_begin(c, kBlCounters, s);
+    if (!rc) rc = plane_ensure(c, kPlaneBl, s);
+    // the fallback writes the whitelist plane, which no whitelist pass may have made yet
+    if (!rc && mark) rc = plane_ensure(c, kPlaneWl, s);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    if (!c->d_bl_mask) {
-        if (hipMalloc(&c->d_bl_mask, c->table_cap * 8ull) != hipSuccess) {
-            c->d_bl_mask = nullptr;
-            return set_err(FB_ERR_NOMEM, "blacklist plane");
-        }
-        HIP_TRY(hipMemsetAsync(c->d_bl_mask, 0, c->table_cap * 8ull, s));
-    }
-    if (mark && !c->d_wl_state) {  // the fallback writes the whitelist plane: no whitelist pass has made it yet
-        if (hipMalloc(&c->d_wl_state, c->table_cap) != hipSuccess) {
-            c->d_wl_state = nullptr;
-            return set_err(FB_ERR_NOMEM, "whitelist plane");
-        }
-        HIP_TRY(hipMemsetAsync(c->d_wl_state, 0, c->table_cap, s));
-    }
-    if (!c->d_bl_stats && hipMalloc(&c->d_bl_stats, kBlCounters * 8ull) != hipSuccess) {
-        c->d_bl_stats = nullptr;
-        return set_err(FB_ERR_NOMEM, "blacklist counters");
-    }
-    HIP_TRY(hipMemsetAsync(c->d_bl_stats, 0, kBlCounters * 8ull, s));
-    HIP_TRY(launch_flow_blacklist(enrich_tables(c), c->d_table, c->table_cap, c->d_bl_mask,
-                                  mark ? c->d_wl_state : nullptr, c->d_bl_stats, s));
+    HIP_TRY(launch_flow_blacklist(enrich_tables(c), c->d_table, c->table_cap, c->plane<unsigned long long>(kPlaneBl),
+                                  mark ? c->plane<uint8_t>(kPlaneWl) : nullptr, c->d_pass_stats, s));
     unsigned long long h[kBlCounters] = {};
-    HIP_TRY(hipMemcpyAsync(h, c->d_bl_stats, sizeof(h), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    rc = pass_end(c, h, kBlCounters, s);
+    if (rc) return rc;
     if (out) {
         memset(out, 0, sizeof(*out));
         out->flows = h[0];
@@ -2266,16 +2222,7 @@ int fb_flow_blacklist(fb_ctx* c, uint32_t flags, fb_bl_stats* out, void* stream)
 }
 
 int fb_flow_blacklist_dev(fb_ctx* c, uint64_t* d_out, uint64_t cap, void* stream) {
-    if (!c || (cap && !d_out)) return set_err(FB_ERR_INVAL, "bad arguments");
-    DeviceGuard g(c->device);
-    hipStream_t s = (hipStream_t)stream;
-    const uint64_t m = std::min<uint64_t>(cap, c->table_cap);
-    if (m == 0) return FB_OK;
-    if (c->d_bl_mask)
-        HIP_TRY(hipMemcpyAsync(d_out, c->d_bl_mask, m * 8ull, hipMemcpyDeviceToDevice, s));
-    else
-        HIP_TRY(hipMemsetAsync(d_out, 0, m * 8ull, s));
-    return FB_OK;
+    return plane_copy_out(c, kPlaneBl, d_out, cap, stream);
 }
 
 int fb_flow_export_blacklisted_dev(fb_ctx* c, fb_flow_rec* d_out, uint64_t* d_masks, uint64_t cap, uint64_t* d_n,
@@ -2284,11 +2231,12 @@ int fb_flow_export_blacklisted_dev(fb_ctx* c, fb_flow_rec* d_out, uint64_t* d_ma
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
-    if (!c->d_table || !c->d_bl_mask) return FB_OK;  // no pass yet: no flow has a mask
+    if (!c->d_table || !c->d_plane[kPlaneBl]) return FB_OK;  // no pass yet: no flow has a mask
     const int rc = join_updates(c, s);
     if (rc) return rc;
-    HIP_TRY(launch_flow_export_blacklisted(c->d_table, c->d_bl_mask, c->table_cap, d_out,
-                                           (unsigned long long*)d_masks, cap, (unsigned long long*)d_n, c->d_time, s));
+    HIP_TRY(launch_flow_export_blacklisted(c->d_table, c->plane<unsigned long long>(kPlaneBl), c->table_cap, d_out,
+                                           (unsigned long long*)d_masks, cap, (unsigned long long*)d_n,
+                                           c->plane<FlowTime>(kPlaneTime), s));
     return FB_OK;
 }
 
@@ -2403,25 +2351,13 @@ int fb_flow_export_sessions(fb_ctx* c, uint32_t filter, fb_flow_rec* out, uint64
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     uint64_t total = 0;
-    int rc = fb_flow_count(c, &total, stream);
-    if (!rc && filter != FB_FILTER_ALL) rc = upload_cfg(c, s);
+    const int rc = fb_flow_count(c, &total, stream);
     if (rc) return rc;
     const uint64_t m = std::min(total, cap);
     if (m == 0) return FB_OK;
-    fb_flow_rec* d_out = nullptr;
-    if (hipMalloc(&d_out, m * sizeof(fb_flow_rec)) != hipSuccess) return set_err(FB_ERR_NOMEM, "export buffer");
-    unsigned long long h = 0;
-    hipError_t e = hipMemsetAsync(c->d_n, 0, 8, s);
-    if (e == hipSuccess) e = launch_flow_export(c->d_table, c->table_cap, d_out, m, c->d_n, s, filter, c->d_cfg, c->d_time);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, c->d_n, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    const uint64_t got = std::min<uint64_t>(h, m);
-    if (e == hipSuccess && got) e = hipMemcpyAsync(out, d_out, got * sizeof(fb_flow_rec), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    hipFree(d_out);
-    if (e != hipSuccess) return set_err(FB_ERR_HIP, "flow export: %s", hipGetErrorString(e));
-    *n = got;
-    return FB_OK;
+    return export_to_host(c, out, m, sizeof(fb_flow_rec), n, s, "flow export", [&](void* d_out) {
+        return fb_flow_export_sessions_dev(c, filter, (fb_flow_rec*)d_out, m, reinterpret_cast<uint64_t*>(c->d_n), stream);
+    });
 }
 
 int fb_flow_export(fb_ctx* c, fb_flow_rec* out, uint64_t cap, uint64_t* n, void* stream) {
@@ -2459,12 +2395,11 @@ int fb_flow_clear(fb_ctx* c, void* stream) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
     if (!c->d_table) return FB_OK;
     DeviceGuard g(c->device);
-    const int rc = join_updates(c, (hipStream_t)stream);
+    int rc = join_updates(c, (hipStream_t)stream);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->d_table, 0, c->table_cap * sizeof(FlowSlot), (hipStream_t)stream));
-    if (c->d_status) HIP_TRY(hipMemsetAsync(c->d_status, 0, c->table_cap, (hipStream_t)stream));
-    if (c->d_wl_state) HIP_TRY(hipMemsetAsync(c->d_wl_state, 0, c->table_cap, (hipStream_t)stream));
-    if (c->d_bl_mask) HIP_TRY(hipMemsetAsync(c->d_bl_mask, 0, c->table_cap * 8ull, (hipStream_t)stream));
+    rc = planes_clear(c, (hipStream_t)stream);
+    if (rc) return rc;
     c->flow_batch = 0;
     c->clear_seq = c->upd_seq;
     c->last_recs = nullptr;

@@ -100,25 +100,12 @@ __global__ __launch_bounds__(256) void k_flow_enrich(const EnrichTables t, const
                                                      unsigned long long cap, uint32_t new_only, uint32_t batch,
                                                      fb_flow_enrich* out, unsigned long long out_cap,
                                                      unsigned long long* d_n) {
-    __shared__ unsigned long long sh[4];
-    __shared__ unsigned long long s_base;
-    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < cap; base += stride) {
-        const unsigned long long i = base + threadIdx.x;
-        bool take = i < cap && T[i].tag >= 2ull;
-        if (take && new_only) take = (uint32_t)(T[i].first_seen >> 32) == batch;
-        const unsigned long long m = __ballot(take);
-        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-        if (lane == 0u) sh[wave] = __popcll(m);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned long long tot = sh[0] + sh[1] + sh[2] + sh[3];
-            s_base = tot ? atomicAdd(d_n, tot) : 0ull;
-        }
-        __syncthreads();
-        unsigned long long pos = s_base + __popcll(m & ((1ull << lane) - 1ull));
-        for (uint32_t w = 0; w < wave; ++w) pos += sh[w];
-        if (take && pos < out_cap) {
+    sweep_compact(
+        cap, out_cap, d_n,
+        [=](unsigned long long i) {
+            return T[i].tag >= 2u && (!new_only || (uint32_t)(T[i].first_seen >> 32) == batch);
+        },
+        [=](unsigned long long i, unsigned long long pos, bool) {
             const uint32_t* k = T[i].key;
             const uint32_t src[4] = {k[0], k[1], k[2], k[3]}, dst[4] = {k[4], k[5], k[6], k[7]};
             const uint32_t fam = (k[9] >> 8) & 0xFFu;
@@ -143,9 +130,7 @@ __global__ __launch_bounds__(256) void k_flow_enrich(const EnrichTables t, const
             r.src_blacklists = bl[0];
             r.dst_blacklists = bl[1];
             out[pos] = r;
-        }
-        __syncthreads();
-    }
+        });
 }
 
 hipError_t launch_ip_lookup(const EnrichTables& t, const fb_ip* ips, uint32_t n, int32_t* asn,
@@ -161,11 +146,8 @@ hipError_t launch_ip_lookup(const EnrichTables& t, const fb_ip* ips, uint32_t n,
 hipError_t launch_flow_enrich(const EnrichTables& t, const DevConfig* cfg, const FlowSlot* table,
                               unsigned long long cap, uint32_t new_only, uint32_t batch, fb_flow_enrich* out,
                               unsigned long long out_cap, unsigned long long* d_n, hipStream_t s) {
-    unsigned long long g = (cap + 255ull) / 256ull;
-    if (g > FB_ENRICH_GRID) g = FB_ENRICH_GRID;
-    if (g == 0ull) g = 1ull;
-    hipLaunchKernelGGL(k_flow_enrich, dim3((uint32_t)g), dim3(256), 0, s, t, cfg, table, cap, new_only, batch, out,
-                       out_cap, d_n);
+    hipLaunchKernelGGL(k_flow_enrich, dim3(sweep_grid(cap, FB_ENRICH_GRID)), dim3(256), 0, s, t, cfg, table, cap,
+                       new_only, batch, out, out_cap, d_n);
     return hipGetLastError();
 }
 

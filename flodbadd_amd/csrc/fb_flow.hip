@@ -1394,35 +1394,14 @@ __global__ __launch_bounds__(256) void k_flow_export(const FlowSlot* T, unsigned
                                                      fb_flow_rec* out, unsigned long long out_cap,
                                                      unsigned long long* d_n, uint32_t filter, const DevConfig* cfg,
                                                      const FlowTime* plane) {
-    __shared__ unsigned long long sh[4];
-    __shared__ unsigned long long s_base;
-    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < cap; base += stride) {
-        const unsigned long long i = base + threadIdx.x;
-        bool occ = i < cap && T[i].tag >= 2ull;
-        // get_sessions' read-time filter (src/capture.rs:1603-1608): is_lan_ip evaluated now
-        if (occ && filter != FB_FILTER_ALL) occ = slot_local(cfg, T[i]) == (filter == FB_FILTER_LOCAL_ONLY);
-        const unsigned long long m = __ballot(occ);
-        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-        if (lane == 0u) sh[wave] = __popcll(m);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned long long tot = sh[0] + sh[1] + sh[2] + sh[3];
-            s_base = tot ? atomicAdd(d_n, tot) : 0ull;
-        }
-        __syncthreads();
-        unsigned long long pos = s_base + __popcll(m & ((1ull << lane) - 1ull));
-        for (uint32_t w = 0; w < wave; ++w) pos += sh[w];
-        if (occ && pos < out_cap) {
-            fb_flow_rec r = flow_rec_of(T[i], (uint32_t)i);
-            if (plane) {  // a timed context: the segment state with the 5-s timeout (fb_time.hip)
-                r.segment_count = plane[i].segment_count;
-                r.in_segment = plane[i].in_segment;
-            }
-            out[pos] = r;
-        }
-        __syncthreads();
-    }
+    sweep_compact(
+        cap, out_cap, d_n,
+        [=](unsigned long long i) {
+            // get_sessions' read-time filter (src/capture.rs:1603-1608): is_lan_ip evaluated now
+            return T[i].tag >= 2u &&
+                   (filter == FB_FILTER_ALL || slot_local(cfg, T[i]) == (filter == FB_FILTER_LOCAL_ONLY));
+        },
+        [=](unsigned long long i, unsigned long long pos, bool) { out[pos] = flow_rec_at(T, plane, i); });
 }
 
 __global__ __launch_bounds__(256) void k_flow_count(const FlowSlot* T, unsigned long long cap,
@@ -1484,20 +1463,14 @@ hipError_t launch_flow_grow(const FlowSlot* old, uint32_t old_parts, uint32_t k,
 hipError_t launch_flow_export(const FlowSlot* table, unsigned long long cap, fb_flow_rec* out,
                               unsigned long long out_cap, unsigned long long* d_n, hipStream_t s, uint32_t filter,
                               const DevConfig* cfg, const FlowTime* plane) {
-    unsigned long long g = (cap + 255ull) / 256ull;
-    if (g > 1024ull) g = 1024ull;
-    if (g == 0ull) g = 1ull;
     if (!cfg) filter = FB_FILTER_ALL;
-    hipLaunchKernelGGL(k_flow_export, dim3((uint32_t)g), dim3(256), 0, s, table, cap, out, out_cap, d_n, filter, cfg,
-                       plane);
+    hipLaunchKernelGGL(k_flow_export, dim3(sweep_grid(cap, 1024ull)), dim3(256), 0, s, table, cap, out, out_cap, d_n,
+                       filter, cfg, plane);
     return hipGetLastError();
 }
 hipError_t launch_flow_count(const FlowSlot* table, unsigned long long cap, unsigned long long* d_n,
                              hipStream_t s) {
-    unsigned long long g = (cap + 255ull) / 256ull;
-    if (g > 1024ull) g = 1024ull;
-    if (g == 0ull) g = 1ull;
-    hipLaunchKernelGGL(k_flow_count, dim3((uint32_t)g), dim3(256), 0, s, table, cap, d_n);
+    hipLaunchKernelGGL(k_flow_count, dim3(sweep_grid(cap, 1024ull)), dim3(256), 0, s, table, cap, d_n);
     return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "../../include/flodbadd_gpu.h"
@@ -333,6 +334,97 @@ __device__ __forceinline__ fb_flow_rec flow_rec_of(const FlowSlot& t, uint32_t s
     r.reserved[0] = r.reserved[1] = r.reserved[2] = 0u;
     return r;
 }
+// ... of slot i of a table; on a timed context (plane != nullptr) the segment state with the 5-s
+// timeout comes from the flow's time record (fb_time.hip).
+__device__ __forceinline__ fb_flow_rec flow_rec_at(const FlowSlot* T, const FlowTime* plane, unsigned long long i) {
+    fb_flow_rec r = flow_rec_of(T[i], (uint32_t)i);
+    if (plane) {
+        r.segment_count = plane[i].segment_count;
+        r.in_segment = plane[i].in_segment;
+    }
+    return r;
+}
+
+// The sweeps over the table (exports, enrichment, the whitelist / blacklist passes, the flow count)
+// run 256-thread workgroups that stride over the slots: the grid for `slots` slots, at most max_grid
+// workgroups and at least one.
+inline uint32_t sweep_grid(unsigned long long slots, unsigned long long max_grid) {
+    return (uint32_t)std::max(1ull, std::min((slots + 255ull) / 256ull, max_grid));
+}
+
+// Sweep and compact: every slot i < cap for which take(i) is truthy gets the next output position,
+// and emit(i, pos, v) -- v being what take(i) returned, so a predicate can hand the store a value it
+// loaded -- runs for the positions below out_cap; *d_n (zeroed by the caller) ends as the number
+// taken, stored or not.  256-thread workgroups: per step a ballot, the waves' counts summed in LDS,
+// one atomic per workgroup, slot order inside a step (not across workgroups).
+template <typename Take, typename Emit>
+__device__ __forceinline__ void sweep_compact(unsigned long long cap, unsigned long long out_cap,
+                                              unsigned long long* d_n, Take take, Emit emit) {
+    __shared__ unsigned long long sh[4];
+    __shared__ unsigned long long s_base;
+    // (256, not blockDim.x: read inside this function the block size lands in vector registers, and the
+    // wave-uniform base and stride with it -- 4 VGPRs in every kernel that uses the sweep)
+    const unsigned long long stride = (unsigned long long)gridDim.x * 256u;
+    for (unsigned long long base = (unsigned long long)blockIdx.x * 256u; base < cap; base += stride) {
+        const unsigned long long i = base + threadIdx.x;
+        const auto v = i < cap ? take(i) : decltype(take(i))();
+        const bool taken = static_cast<bool>(v);
+        const unsigned long long m = __ballot(taken);
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        if (lane == 0u) sh[wave] = __popcll(m);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const unsigned long long tot = sh[0] + sh[1] + sh[2] + sh[3];
+            s_base = tot ? atomicAdd(d_n, tot) : 0ull;
+        }
+        __syncthreads();
+        unsigned long long pos = s_base + __popcll(m & ((1ull << lane) - 1ull));
+        for (uint32_t w = 0; w < wave; ++w) pos += sh[w];
+        if (taken && pos < out_cap) emit(i, pos, v);
+        __syncthreads();
+    }
+}
+
+// The counters of a pass over the table (fb_flow_whitelist, fb_flow_blacklist), 256-thread
+// workgroups: add() sums a per-lane flag over the wave with a ballot (every lane of the workgroup
+// calls it, the count is wave-uniform), flush() leaves the waves' sums in LDS and issues one atomic
+// per non-zero counter per workgroup.
+template <uint32_t N>
+struct PassCounters {
+    uint32_t cnt[N] = {};
+    __device__ __forceinline__ void add(uint32_t k, bool f) { cnt[k] += (uint32_t)__popcll(__ballot(f)); }
+    __device__ __forceinline__ void flush(unsigned long long* stats) {
+        __shared__ uint32_t s_cnt[4][N];
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        if (lane == 0u)
+            for (uint32_t k = 0; k < N; ++k) s_cnt[wave][k] = cnt[k];
+        __syncthreads();
+        if (threadIdx.x < N) {
+            const unsigned long long t = (unsigned long long)s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] +
+                                         s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
+            if (t) atomicAdd(stats + threadIdx.x, t);
+        }
+    }
+};
+
+// A per-slot plane follows its flows through a slot move (a growth, a purge): remap[old slot] = new
+// slot, ~0u for an empty or removed one; `nw` is zeroed by the caller.  T: a time record, a status /
+// whitelist byte, a blacklist mask word.
+template <typename T>
+__global__ __launch_bounds__(256) void k_plane_remap(const T* old, const uint32_t* remap, unsigned long long old_cap,
+                                                     T* nw) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (i >= old_cap) return;
+    const uint32_t d = remap[i];
+    if (d != ~0u) nw[d] = old[i];
+}
+template <typename T>
+hipError_t launch_plane_remap(const void* old, const uint32_t* remap, unsigned long long old_cap, void* nw,
+                              hipStream_t s) {
+    hipLaunchKernelGGL(k_plane_remap<T>, dim3((uint32_t)((old_cap + 255ull) / 256ull)), dim3(256), 0, s,
+                       static_cast<const T*>(old), remap, old_cap, static_cast<T*>(nw));
+    return hipGetLastError();
+}
 
 // Owner rank of a key in the multi-GPU merge (fb_flow_export_merge_dev): the high word of its
 // fb_flow_hash scaled to [0, world).
@@ -590,8 +682,6 @@ unsigned long long* time_key_array(void* scratch);
 hipError_t launch_time_prepare(void* scratch, uint32_t n_slots, hipStream_t s);
 hipError_t launch_time_update(const FlowParams& p, uint32_t n_slots, uint64_t cap, FlowTime* plane,
                               const unsigned long long* ts, void* scratch, hipStream_t s);
-hipError_t launch_time_remap(const FlowTime* old, const uint32_t* remap, unsigned long long old_cap, FlowTime* nw,
-                             hipStream_t s);
 hipError_t launch_time_export(const FlowSlot* table, const FlowTime* plane, unsigned long long cap, fb_flow_time* out,
                               unsigned long long out_cap, unsigned long long* d_n, hipStream_t s);
 
@@ -614,8 +704,6 @@ struct AgeArgs {
     uint32_t purge;
 };
 hipError_t launch_flow_age(const AgeArgs& a, uint32_t parts, hipStream_t s);
-hipError_t launch_age_remap(const uint8_t* old, const uint32_t* remap, unsigned long long old_cap, uint8_t* nw,
-                            hipStream_t s);
 
 // Per-flow history characters of the last update (fb_hist.hip): the update's FlowParams (its
 // entries, transposed original rows, combined-group maps, per-slot counts) and the outputs.
@@ -717,9 +805,6 @@ hipError_t launch_flow_blacklist(const EnrichTables& t, const FlowSlot* table, u
 hipError_t launch_flow_export_blacklisted(const FlowSlot* table, const unsigned long long* mask, unsigned long long cap,
                                           fb_flow_rec* out, unsigned long long* out_masks, unsigned long long out_cap,
                                           unsigned long long* d_n, const FlowTime* plane, hipStream_t s);
-// the 8-byte form of launch_age_remap: the mask words follow their flows
-hipError_t launch_age_remap64(const unsigned long long* old, const uint32_t* remap, unsigned long long old_cap,
-                              unsigned long long* nw, hipStream_t s);
 
 // Whitelist conformance (fb_whitelist.hip, fb_flow_whitelist).  fb_set_whitelist compiles the endpoint
 // list into three structures (build_whitelist_index):

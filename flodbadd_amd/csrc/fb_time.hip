@@ -52,8 +52,6 @@ namespace fbk {
 
 namespace {
 
-constexpr uint32_t kTmThreads = 256;
-
 // chrono's (a - b).num_milliseconds(): the signed difference truncated toward zero
 __device__ __forceinline__ long long ms_between(unsigned long long a, unsigned long long b) {
     return ((long long)a - (long long)b) / 1000000ll;
@@ -492,43 +490,17 @@ __global__ __launch_bounds__(kRunThreads) void k_time_runs(const uint32_t* ks, u
     }
 }
 
-// Growth: the time records follow their flows (remap[old slot] = new slot, ~0u: empty).
-__global__ __launch_bounds__(kTmThreads) void k_time_remap(const FlowTime* old, const uint32_t* remap,
-                                                           unsigned long long old_cap, FlowTime* nw) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * kTmThreads + threadIdx.x;
-    if (i >= old_cap) return;
-    const uint32_t d = remap[i];
-    if (d != ~0u) nw[d] = old[i];
-}
-
 // fb_flow_export_times_dev: every flow's time record with its slot.
 __global__ __launch_bounds__(256) void k_time_export(const FlowSlot* T, const FlowTime* plane, unsigned long long cap,
                                                      fb_flow_time* out, unsigned long long out_cap,
                                                      unsigned long long* d_n) {
-    __shared__ unsigned long long sh[4];
-    __shared__ unsigned long long s_base;
-    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < cap; base += stride) {
-        const unsigned long long i = base + threadIdx.x;
-        const bool occ = i < cap && T[i].tag >= 2u;
-        const unsigned long long m = __ballot(occ);
-        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-        if (lane == 0u) sh[wave] = __popcll(m);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned long long tot = sh[0] + sh[1] + sh[2] + sh[3];
-            s_base = tot ? atomicAdd(d_n, tot) : 0ull;
-        }
-        __syncthreads();
-        unsigned long long pos = s_base + __popcll(m & ((1ull << lane) - 1ull));
-        for (uint32_t w = 0; w < wave; ++w) pos += sh[w];
-        if (occ && pos < out_cap) {
+    sweep_compact(
+        cap, out_cap, d_n, [=](unsigned long long i) { return T[i].tag >= 2u; },
+        [=](unsigned long long i, unsigned long long pos, bool) {
             fb_flow_time o = plane[i];
             o.slot = (uint32_t)i;
             out[pos] = o;
-        }
-        __syncthreads();
-    }
+        });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -624,19 +596,10 @@ hipError_t launch_time_update(const FlowParams& p, uint32_t n_slots, uint64_t ca
     return hipGetLastError();
 }
 
-hipError_t launch_time_remap(const FlowTime* old, const uint32_t* remap, unsigned long long old_cap, FlowTime* nw,
-                             hipStream_t s) {
-    const unsigned long long g = (old_cap + kTmThreads - 1) / kTmThreads;
-    hipLaunchKernelGGL(k_time_remap, dim3((uint32_t)g), dim3(kTmThreads), 0, s, old, remap, old_cap, nw);
-    return hipGetLastError();
-}
-
 hipError_t launch_time_export(const FlowSlot* table, const FlowTime* plane, unsigned long long cap, fb_flow_time* out,
                               unsigned long long out_cap, unsigned long long* d_n, hipStream_t s) {
-    unsigned long long g = (cap + 255ull) / 256ull;
-    if (g > 1024ull) g = 1024ull;
-    if (g == 0ull) g = 1ull;
-    hipLaunchKernelGGL(k_time_export, dim3((uint32_t)g), dim3(256), 0, s, table, plane, cap, out, out_cap, d_n);
+    hipLaunchKernelGGL(k_time_export, dim3(sweep_grid(cap, 1024ull)), dim3(256), 0, s, table, plane, cap, out, out_cap,
+                       d_n);
     return hipGetLastError();
 }
 

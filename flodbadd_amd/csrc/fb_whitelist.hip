@@ -10,8 +10,8 @@
 // The verdict is a boolean over the endpoints -- "some endpoint matches" --, so neither the reference's
 // first-match order nor duplicates matter, and the index is free to reorder and deduplicate.
 //
-// The state lives in a plane of its own, one byte per table slot (FB_WL_*), like the status plane of
-// fb_age.hip: FlowSlot and the update kernels are untouched.
+// The state lives in a per-slot plane of its own, one byte per table slot (FB_WL_*):
+// FlowSlot and the update kernels are untouched.
 #include <algorithm>
 
 #include "fb_internal.h"
@@ -141,8 +141,7 @@ __device__ __forceinline__ uint32_t wl_eval(const WlTables& W, const EnrichTable
 // kStaged: the group table and the rules fit kWlLdsGroups / kWlLdsRules and every workgroup copies them
 // into LDS once (coalesced), so the per-lane group searches and rule scans -- divergent addresses --
 // stay on the CU.  Otherwise they are read from global memory (L2).
-// Counters: each wave sums its lanes' flags with a ballot per pass over the table (fb_age.hip's
-// wave_count, accumulated), and the workgroup issues one atomic per counter at the end.
+// Counters: PassCounters (fb_internal.h).
 template <bool kStaged>
 __global__ __launch_bounds__(256) void k_flow_whitelist(const WlTables W, const EnrichTables E, const DevConfig* cfg,
                                                         const FlowSlot* T, unsigned long long cap, uint8_t* state,
@@ -150,7 +149,6 @@ __global__ __launch_bounds__(256) void k_flow_whitelist(const WlTables W, const 
     __shared__ uint32_t s_gkey[kStaged ? kWlLdsGroups : 1u];
     __shared__ uint32_t s_gbeg[kStaged ? kWlLdsGroups + 1u : 1u];
     __shared__ uint4 s_rules[kStaged ? kWlLdsRules * 3u : 1u];
-    __shared__ uint32_t s_cnt[4][kWlCounters];
     if (kStaged) {
         for (uint32_t j = threadIdx.x; j < W.ng; j += 256u) s_gkey[j] = W.gkey[j];
         for (uint32_t j = threadIdx.x; j < W.ng + 1u; j += 256u) s_gbeg[j] = W.gbeg[j];
@@ -158,7 +156,7 @@ __global__ __launch_bounds__(256) void k_flow_whitelist(const WlTables W, const 
         for (uint32_t j = threadIdx.x; j < W.nr * 3u; j += 256u) s_rules[j] = src[j];
         __syncthreads();
     }
-    uint32_t cnt[kWlCounters] = {0u, 0u, 0u, 0u, 0u};  // wave-uniform
+    PassCounters<kWlCounters> cnt;
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < cap; base += stride) {
         const unsigned long long i = base + threadIdx.x;
@@ -172,59 +170,28 @@ __global__ __launch_bounds__(256) void k_flow_whitelist(const WlTables W, const 
                 nb = wl_eval(W, E, cfg, W.gkey, W.gbeg, W.rules, T[i].key);
             if (nb != old) state[i] = (uint8_t)nb;
         }
-        cnt[0] += (uint32_t)__popcll(__ballot(occ));
-        cnt[1] += (uint32_t)__popcll(__ballot((nb & FB_WL_CONFORMING) != 0u));
-        cnt[2] += (uint32_t)__popcll(__ballot((nb & FB_WL_NONCONFORMING) != 0u));
-        cnt[3] += (uint32_t)__popcll(__ballot((nb & FB_WL_HOST_CHECK) != 0u));
-        cnt[4] += (uint32_t)__popcll(__ballot(occ && nb != old));
+        cnt.add(0, occ);
+        cnt.add(1, (nb & FB_WL_CONFORMING) != 0u);
+        cnt.add(2, (nb & FB_WL_NONCONFORMING) != 0u);
+        cnt.add(3, (nb & FB_WL_HOST_CHECK) != 0u);
+        cnt.add(4, occ && nb != old);
     }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0u)
-        for (uint32_t k = 0; k < kWlCounters; ++k) s_cnt[wave][k] = cnt[k];
-    __syncthreads();
-    if (threadIdx.x < kWlCounters) {  // one atomic per counter per workgroup
-        const unsigned long long t = (unsigned long long)s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] +
-                                     s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
-        if (t) atomicAdd(stats + threadIdx.x, t);
-    }
+    cnt.flush(stats);
 }
 
-// k_flow_export (fb_flow.hip) with the state byte as the predicate: a ballot, one atomic per block.
+// The flows whose state byte state_mask selects (FB_WL_MASK_UNKNOWN: a zero byte, or no plane yet).
 __global__ __launch_bounds__(256) void k_flow_export_whitelist(const FlowSlot* T, const uint8_t* state,
                                                                unsigned long long cap, uint32_t state_mask,
                                                                fb_flow_rec* out, unsigned long long out_cap,
                                                                unsigned long long* d_n, const FlowTime* plane) {
-    __shared__ unsigned long long sh[4];
-    __shared__ unsigned long long s_base;
-    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < cap; base += stride) {
-        const unsigned long long i = base + threadIdx.x;
-        bool take = i < cap && T[i].tag >= 2u;
-        if (take) {
+    sweep_compact(
+        cap, out_cap, d_n,
+        [=](unsigned long long i) {
+            if (T[i].tag < 2u) return false;
             const uint32_t b = state ? state[i] : 0u;
-            take = b ? (b & state_mask & 0x7Fu) != 0u : (state_mask & FB_WL_MASK_UNKNOWN) != 0u;
-        }
-        const unsigned long long m = __ballot(take);
-        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-        if (lane == 0u) sh[wave] = __popcll(m);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned long long tot = sh[0] + sh[1] + sh[2] + sh[3];
-            s_base = tot ? atomicAdd(d_n, tot) : 0ull;
-        }
-        __syncthreads();
-        unsigned long long pos = s_base + __popcll(m & ((1ull << lane) - 1ull));
-        for (uint32_t w = 0; w < wave; ++w) pos += sh[w];
-        if (take && pos < out_cap) {
-            fb_flow_rec r = flow_rec_of(T[i], (uint32_t)i);
-            if (plane) {  // a timed context: the segment state with the 5-s timeout (fb_time.hip)
-                r.segment_count = plane[i].segment_count;
-                r.in_segment = plane[i].in_segment;
-            }
-            out[pos] = r;
-        }
-        __syncthreads();
-    }
+            return b ? (b & state_mask & 0x7Fu) != 0u : (state_mask & FB_WL_MASK_UNKNOWN) != 0u;
+        },
+        [=](unsigned long long i, unsigned long long pos, bool) { out[pos] = flow_rec_at(T, plane, i); });
 }
 
 #ifndef FB_WL_GRID
@@ -236,23 +203,19 @@ hipError_t launch_flow_whitelist(const WlTables& w, const EnrichTables& t, const
     if ((w.ng && (!w.gkey || !w.gbeg)) || (w.nr && !w.rules) || (w.n4 && (!w.a4 || !w.k4)) ||
         (w.n6 && (!w.a6 || !w.k6)) || (w.n_records && (!w.rec_owner || !w.rec_country)))
         return hipErrorInvalidValue;
-    unsigned long long g = (cap + 255ull) / 256ull;
-    if (g > FB_WL_GRID) g = FB_WL_GRID;
+    const dim3 g(sweep_grid(cap, FB_WL_GRID));
     if (w.ng <= kWlLdsGroups && w.nr <= kWlLdsRules && w.ng)
-        hipLaunchKernelGGL(k_flow_whitelist<true>, dim3((uint32_t)g), dim3(256), 0, s, w, t, cfg, table, cap, state, stats);
+        hipLaunchKernelGGL(k_flow_whitelist<true>, g, dim3(256), 0, s, w, t, cfg, table, cap, state, stats);
     else
-        hipLaunchKernelGGL(k_flow_whitelist<false>, dim3((uint32_t)g), dim3(256), 0, s, w, t, cfg, table, cap, state, stats);
+        hipLaunchKernelGGL(k_flow_whitelist<false>, g, dim3(256), 0, s, w, t, cfg, table, cap, state, stats);
     return hipGetLastError();
 }
 
 hipError_t launch_flow_export_whitelist(const FlowSlot* table, const uint8_t* state, unsigned long long cap,
                                         uint32_t state_mask, fb_flow_rec* out, unsigned long long out_cap,
                                         unsigned long long* d_n, const FlowTime* plane, hipStream_t s) {
-    unsigned long long g = (cap + 255ull) / 256ull;
-    if (g > 1024ull) g = 1024ull;
-    if (g == 0ull) g = 1ull;
-    hipLaunchKernelGGL(k_flow_export_whitelist, dim3((uint32_t)g), dim3(256), 0, s, table, state, cap, state_mask, out,
-                       out_cap, d_n, plane);
+    hipLaunchKernelGGL(k_flow_export_whitelist, dim3(sweep_grid(cap, 1024ull)), dim3(256), 0, s, table, state, cap,
+                       state_mask, out, out_cap, d_n, plane);
     return hipGetLastError();
 }
 

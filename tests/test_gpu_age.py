@@ -367,6 +367,82 @@ def test_growth_carries_status():
         cap.close()
 
 
+def planes_by_key(cap):
+    """Per flow key: (status byte, whitelist byte, blacklist mask, time record without its slot); the slot
+    of every key; and the three lazily made planes whole."""
+    fl, tm = cap.export_flows(), cap.export_times()
+    planes = (cap.status_bytes(), cap.whitelist_bytes(), cap.blacklist_masks())
+    tms = tm[np.argsort(tm["slot"], kind="stable")]
+    tt = tms[np.searchsorted(tms["slot"], fl["slot"])].copy()
+    assert len(tm) == len(fl) and (tt["slot"] == fl["slot"]).all()
+    tt["slot"] = 0
+    slots = fl["slot"].tolist()
+    by_key = {k: (int(planes[0][s]), int(planes[1][s]), int(planes[2][s]), t.tobytes())
+              for k, s, t in zip(keyb(fl), slots, tt)}
+    return by_key, dict(zip(keyb(fl), slots)), planes
+
+
+def test_all_planes_follow_every_slot_move():
+    """All four per-slot planes (time, status, whitelist, blacklist) alive through one purge, one growth and
+    one clear: 1,400 flows in 4 partitions of 512 slots (about 350 each), every other one last seen two days
+    before the rest; aged without purge, one whitelist pass, one blacklist pass with the fallback."""
+    from flodbadd_amd.enrich import blacklists_from_json
+    from flodbadd_amd.whitelists import rows_from_flows
+    from test_gpu_blacklist import LISTS, mixed_packets, pkt
+    day2 = 2 * 86400 * S
+    pk = mixed_packets()[:1400]
+    ts = np.array([T0 + (0 if k & 1 else day2) + k * 1000 for k in range(len(pk))], dtype=np.uint64)
+    cap = FlodbaddGpuCapture(0, session_filter=SessionFilter.All, flow_capacity=1 << 11, timed=True)
+    ref, model = coracle.Flows(), StatusModel()
+    try:
+        cap.process_parsed(pk, ts=ts)
+        ref.update(coracle.process_parsed(coracle.make_cfg(2), packets_to_parsed(pk))[0], ts=ts)
+        info = cap.table_info()
+        assert info["capacity"] == 1 << 11 and info["max_partition"] > 300
+        check_table(cap, ref, "before the passes")
+        check_age(cap, model, ref, T0 + day2 + 100 * S, purge=False)
+        cap.install_whitelist(rows_from_flows(cap.export_flows()[::2]))
+        wst = cap.whitelist_pass()
+        cap.set_blacklists(*blacklists_from_json(LISTS))
+        bst = cap.update_blacklist(mark_whitelist=True)
+        snap, slot0, _ = planes_by_key(cap)
+        assert len(snap) == 1400 == wst["flows"] == bst["flows"] and 0 < wst["conforming"] < 1400
+        assert 100 < bst["blacklisted"] < 1400
+        for j in range(3):  # every plane holds more than one value: a mix-up between flows would show
+            assert len({v[j] for v in snap.values()}) > 1, j
+
+        def unoccupied_read_zero(slot, planes):
+            free = np.ones(len(planes[0]), dtype=bool)
+            free[list(slot.values())] = False
+            assert free.sum() == len(free) - len(slot) and not any(p[free].any() for p in planes)
+
+        # 1. a purge that removes half: the survivors keep everything but take the status this call computes
+        now = T0 + day2 + 150 * S
+        want, removed, wstats = model_age(model, ref, now, purge=True)
+        ag = cap.update_sessions_status(now, purge=True)
+        assert {k: ag[k] for k in wstats} == wstats and ag["purged"] == len(removed) == 700
+        s1, slot1, planes1 = planes_by_key(cap)
+        assert set(s1) == set(snap) - removed
+        assert all(s1[k] == (want[k],) + snap[k][1:] for k in s1)
+        assert any(slot1[k] != slot0[k] for k in s1)
+        unoccupied_read_zero(slot1, planes1)
+        # 2. 3,000 new flows grow the table: every old flow keeps all four, the new ones read zero
+        more = [pkt("UDP", "192.168.1.9", 40001 + 2 * (k % 9000), "48.%d.%d.%d" % (k >> 16, (k >> 8) & 255, k & 255), 53)
+                for k in range(3000)]
+        cap.process_parsed(more, ts=np.full(3000, now + 100 * S, dtype=np.uint64))
+        assert cap.table_info()["capacity"] > 1 << 11
+        s2, slot2, planes2 = planes_by_key(cap)
+        assert len(s2) == len(s1) + 3000 and all(s2[k] == s1[k] for k in s1)
+        assert all(s2[k][:3] == (0, 0, 0) for k in s2 if k not in s1)
+        unoccupied_read_zero(slot2, planes2)
+        # 3. clear_all_sessions: the three lazily made planes read zero over the whole capacity
+        cap.clear_all_sessions()
+        planes3 = (cap.status_bytes(), cap.whitelist_bytes(), cap.blacklist_masks())
+        assert all(len(p) == cap.table_info()["capacity"] and not p.any() for p in planes3)
+    finally:
+        cap.close()
+
+
 def test_refusals():
     lib = N.gpu_lib()
     plain = FlodbaddGpuCapture(0, session_filter=SessionFilter.All, flow_capacity=1 << 10)

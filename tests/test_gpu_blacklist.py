@@ -466,15 +466,67 @@ def test_sweep_and_compaction_edges():
         cap.close()
 
 
+# The other compacting exports -> (record dtype, the _dev call into (d_out, cap, d_n)).  The whitelist
+# export selects the conforming flows only, so its total is below the occupancy.
+OTHER_EXPORTS = {
+    "sessions": (N.FLOW_REC_DTYPE, lambda lib, ctx, out, c, n: lib.fb_flow_export_sessions_dev(ctx, N.FB_FILTER_ALL, out, c, n, None)),
+    "whitelist": (N.FLOW_REC_DTYPE, lambda lib, ctx, out, c, n: lib.fb_flow_export_whitelist_dev(ctx, N.FB_WL_CONFORMING, out, c, n, None)),
+    "times": (N.FLOW_TIME_DTYPE, lambda lib, ctx, out, c, n: lib.fb_flow_export_times_dev(ctx, out, c, n, None)),
+}
+
+
+@pytest.mark.parametrize("which", sorted(OTHER_EXPORTS))
+def test_compaction_edges_of_the_other_exports(which):
+    """The output-capacity edge of test_sweep_and_compaction_edges for the session, whitelist and time
+    exports, against a completely full 512-slot partition: *d_n is the total whatever the capacity, exactly
+    `cap` distinct records arrive, each one of the full export's, and nothing is written behind them."""
+    dtype, call = OTHER_EXPORTS[which]
+    guard, rec = 64, dtype.itemsize
+
+    def raw(cap, c):
+        d_out, d_n = N.DeviceBuffer(c * rec + guard), N.DeviceBuffer(8)
+        d_out.upload(np.full(c * rec + guard, 0xA5, dtype=np.uint8))
+        N.check(call(N.gpu_lib(), cap.ctx, d_out.ptr, c, d_n.ptr))
+        n = int(d_n.download(np.zeros(1, dtype=np.uint64))[0])
+        b = d_out.download(np.zeros(c * rec + guard, dtype=np.uint8))
+        return n, b[: c * rec].view(dtype), bool((b[c * rec:] == 0xA5).all())
+
+    cap = FlodbaddGpuCapture(0, session_filter=SessionFilter.All, flow_capacity=512, grow=False, timed=True)
+    try:
+        pk = mixed_packets()[:512]
+        cap.process_parsed(pk, ts=(T0 + np.arange(512, dtype=np.uint64) * 1000))
+        assert cap.flow_count() == 512
+        cap.install_whitelist(rows_from_flows(cap.export_flows()[::2]))
+        cap.whitelist_pass()
+        total = int((cap.whitelist_bytes() == N.FB_WL_CONFORMING).sum()) if which == "whitelist" else 512
+        assert 65 < total <= 512
+        n, full, ok = raw(cap, total)
+        assert n == total and ok and len(set(full["slot"].tolist())) == total
+        allowed = {r.tobytes() for r in full}
+        for c in (0, 1, 63, 64, 65):
+            n, recs, ok = raw(cap, c)
+            print("%s export, cap %d: d_n %d, %d distinct slots" % (which, c, n, len(set(recs["slot"].tolist()))))
+            assert n == total and ok
+            assert len(set(recs["slot"].tolist())) == c and {r.tobytes() for r in recs} <= allowed
+    finally:
+        cap.close()
+
+
 def test_table_larger_than_the_grid():
     """2^19 slots: the pass's and the export's grids stop at 1024 workgroups (2^18 slots), so every thread
     takes more than one step of the sweep."""
-    cap = FlodbaddGpuCapture(0, session_filter=SessionFilter.All, flow_capacity=1 << 19, grow=False)
+    cap = FlodbaddGpuCapture(0, session_filter=SessionFilter.All, flow_capacity=1 << 19, grow=False, timed=True)
     ref = blref.BlRef()
     try:
-        cap.process_parsed(mixed_packets())
-        slots = cap.export_flows()["slot"]
+        pk = mixed_packets()
+        cap.process_parsed(pk, ts=(T0 + np.arange(len(pk), dtype=np.uint64) * 1000))
+        flows, times = cap.export_flows(), cap.export_times()
+        slots = flows["slot"]
         assert cap.table_info()["capacity"] == 1 << 19 and int(slots.min()) < 1 << 18 <= int(slots.max())
+        # the session and the time export: every flow put in, once, and the same slots from both
+        assert len(flows) == len(times) == cap.flow_count() == len(pk) == len({p.session for p in pk})
+        assert sorted(slots.tolist()) == sorted(times["slot"].tolist()) and len(set(slots.tolist())) == len(flows)
+        assert sorted(times["last_activity_ns"].tolist()) == (T0 + np.arange(len(pk), dtype=np.uint64) * 1000).tolist()
         names = install(cap, ref, LISTS)
         known = {}
         check_pass(cap, ref, names, known, mark=True, wl_bytes={})
