@@ -88,6 +88,20 @@ BL_STATS_FIELDS = ["flows", "blacklisted", "changed", "newly_blacklisted", "clea
 BL_STATS_DTYPE = np.dtype([(f, "<u8") for f in BL_STATS_FIELDS] + [("reserved", "<u8", (2,))])
 assert BL_STATS_DTYPE.itemsize == 64
 FB_BL_MARK_WHITELIST, FB_WL_BLACKLISTED = 1, 8
+# the anomaly pass (fb_flow_anomaly: SessionAnalyzer, src/analyzer.rs): forest nodes, model parameters,
+# the per-slot record of fb_flow_anomaly_dev (all zero: no pass has seen the flow) and the counters
+FB_AN_FEATURES, FB_IF_MAX_TREES, FB_IF_MAX_TREE_NODES, FB_IF_MAX_DEPTH, FB_IF_LEAF = 10, 64, 255, 12, 0xFFFFFFFF
+FB_AN_MAX_SERVICE_CODE = 1000000
+IF_NODE_DTYPE = np.dtype([("normal", "<f8", (FB_AN_FEATURES,)), ("value", "<f8"), ("left", "<u4"), ("right", "<u4")])
+AN_PARAMS_DTYPE = np.dtype([("mean", "<f8", (FB_AN_FEATURES,)), ("std", "<f8", (FB_AN_FEATURES,)),
+                            ("suspicious_cut", "<f8"), ("abnormal_cut", "<f8"), ("has_stats", "<u4"),
+                            ("sample_size", "<u4")])
+AN_REC_DTYPE = np.dtype([("path_sum", "<f8"), ("diag", "<u4"), ("level", "u1"), ("reserved", "u1", (3,))])
+AN_STATS_FIELDS = ["flows", "normal", "suspicious", "abnormal", "changed", "newly_anomalous", "cleared"]
+AN_STATS_DTYPE = np.dtype([(f, "<u8") for f in AN_STATS_FIELDS] + [("reserved", "<u8")])
+assert (IF_NODE_DTYPE.itemsize, AN_PARAMS_DTYPE.itemsize, AN_REC_DTYPE.itemsize, AN_STATS_DTYPE.itemsize) == (96, 184, 16, 64)
+FB_AN_UNSEEN, FB_AN_NORMAL, FB_AN_SUSPICIOUS, FB_AN_ABNORMAL = 0, 1, 2, 3
+FB_AN_DIAG_HIGH, FB_AN_DIAG_LOW, FB_AN_DIAG_DEVIATES = 1, 2, 3
 FB_SEGMENT_TIMEOUT_MS = 5000
 FB_CFG_TIMED = 2
 FB_QUEUE_SHARED = 1
@@ -294,6 +308,15 @@ GPU_SYMBOLS = [
     ("fb_flow_blacklist", _I, [_P, _U32, _P, _P]),
     ("fb_flow_blacklist_dev", _I, [_P, _P, _U64, _P]),
     ("fb_flow_export_blacklisted_dev", _I, [_P, _P, _P, _U64, _P, _P]),
+    ("fb_if_validate", _I, [_P, _U64, _P, _U32]),
+    ("fb_set_service_codes", _I, [_P, _P]),
+    ("fb_set_anomaly_model", _I, [_P, _P, _U64, _P, _U32, _P, _P]),
+    ("fb_clear_anomaly_model", _I, [_P]),
+    ("fb_flow_anomaly", _I, [_P, _U32, _P, _P]),
+    ("fb_flow_anomaly_dev", _I, [_P, _P, _U64, _P]),
+    ("fb_flow_export_anomalous_dev", _I, [_P, _U32, _P, _P, _U64, _P, _P]),
+    ("fb_flow_features_dev", _I, [_P, _P, _P, _U64, _P, _P]),
+    ("fb_if_score_dev", _I, [_P, _P, _U64, _P, _P]),
 ]
 
 _gpu = None

@@ -17,6 +17,7 @@ import numpy as np
 from . import _native as N
 from .sessions import Session, SessionFilter, WhitelistState, flows_to_sessions, ip_to_words, is_lan_ip
 from .enrich import Blacklists
+from .analyzer import SessionAnalyzer, anomaly_tag_of, default_service_codes, merge_criticality, path_cut
 from .whitelists import Whitelists, is_session_in_whitelist, no_match_reason
 
 
@@ -108,6 +109,12 @@ class FlodbaddGpuCapture:
         self._bl_names = []
         self._bl_ran = False
         self._bl_marked = False
+        # anomaly pass (src/analyzer.rs): the analyzer's host state, the model the device holds, and what the
+        # last analyze_sessions did (None: no analysis yet; "model" / "warming_up" / "no_model")
+        self.analyzer = SessionAnalyzer()
+        self._an_model = None
+        self._an_mode = None
+        self._an_codes = False  # the device holds service codes (analyzer.default_service_codes, or a model's)
 
     # ---- configuration -------------------------------------------------------------------
     def set_filter(self, flt):
@@ -354,7 +361,8 @@ class FlodbaddGpuCapture:
         table is aged first, as the reference does on every query (capture.rs:1581)."""
         if now_ns is not None:
             self.update_sessions_status(now_ns)
-        out = flows_to_sessions(self.export_flows(self.filter), self.histories if self.track_history else None,
+        flows = self.export_flows(self.filter)
+        out = flows_to_sessions(flows, self.histories if self.track_history else None,
                                 times=self.export_times() if self.timed else None,
                                 status=self.status_bytes() if self.timed else None,
                                 whitelist=self.whitelist_bytes() if (self._wl_name or self._bl_marked) else None,
@@ -362,7 +370,7 @@ class FlodbaddGpuCapture:
         for info in out if self._wl_host_ok else ():  # the host's verdict for the flows the pass left to it
             if info.session in self._wl_host_ok and info.is_whitelisted is WhitelistState.NonConforming:
                 info.is_whitelisted = WhitelistState.Conforming
-        return out
+        return self._merge_anomaly(out, flows)
 
     def get_current_sessions(self, now_ns=None):
         """get_current_sessions (src/capture.rs:1624-1670): the members of current_sessions -- activity
@@ -375,9 +383,10 @@ class FlodbaddGpuCapture:
         flows, status = self.export_flows(self.filter), self.status_bytes()
         b = status[flows["slot"]] if len(flows) else np.zeros(0, dtype=np.uint8)
         flows = flows[(b == 0) | ((b & N.STATUS_CURRENT) != 0)]
-        return flows_to_sessions(flows, self.histories if self.track_history else None, times=self.export_times(),
-                                 status=status,
-                                 blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None)
+        out = flows_to_sessions(flows, self.histories if self.track_history else None, times=self.export_times(),
+                                status=status,
+                                blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None)
+        return self._merge_anomaly(out, flows)
 
     # ---- new-session enrichment (src/packets.rs:429-485) -------------------------------------
     def set_asn_tables(self, v4, v6, records=None):
@@ -476,11 +485,12 @@ class FlodbaddGpuCapture:
         if not len(flows):
             return []
         by_slot = {int(r["slot"]): m for r, m in zip(flows, masks)}
-        return flows_to_sessions(flows, self.histories if self.track_history else None,
-                                 times=self.export_times() if self.timed else None,
-                                 status=self.status_bytes() if self.timed else None,
-                                 whitelist=self.whitelist_bytes() if (self._wl_name or self._bl_marked) else None,
-                                 blacklist=(by_slot, self._bl_names))
+        out = flows_to_sessions(flows, self.histories if self.track_history else None,
+                                times=self.export_times() if self.timed else None,
+                                status=self.status_bytes() if self.timed else None,
+                                whitelist=self.whitelist_bytes() if (self._wl_name or self._bl_marked) else None,
+                                blacklist=(by_slot, self._bl_names))
+        return self._merge_anomaly(out, flows)
 
     def get_blacklisted_status(self, now_ns=None):
         """get_blacklisted_status (src/capture.rs:1762-1770): after an update, some session is blacklisted."""
@@ -495,6 +505,142 @@ class FlodbaddGpuCapture:
         bl = self.update_blacklist(mark_whitelist=True)
         wl = self.update_whitelist(dns_resolutions, process_names)
         return {"status": age, "blacklist": bl, "whitelist": wl}
+
+    # ---- anomaly pass (src/analyzer.rs; fb_flow_anomaly) ------------------------------------------
+    def set_anomaly_model(self, forest, stats, thresholds, service_codes=None):
+        """Install a model on the device (fb_set_anomaly_model): an analyzer.Forest, feature_stats' result
+        (mean, std, has_stats), the (suspicious, abnormal) SCORE thresholds -- turned into path cuts with
+        path_cut -- and the service codes (default: analyzer.default_service_codes).  A forest the device
+        rejects raises FbError and the installed model stays."""
+        mean, std, has = stats
+        prm = np.zeros(1, dtype=N.AN_PARAMS_DTYPE)
+        prm[0]["mean"], prm[0]["std"], prm[0]["has_stats"] = mean, std, 1 if has else 0
+        prm[0]["suspicious_cut"] = path_cut(thresholds[0], forest.sample_size, forest.n_trees)
+        prm[0]["abnormal_cut"] = path_cut(thresholds[1], forest.sample_size, forest.n_trees)
+        prm[0]["sample_size"] = forest.sample_size
+        codes = np.ascontiguousarray(default_service_codes() if service_codes is None else service_codes, dtype=np.uint32)
+        if codes.size != 65536:
+            raise ValueError("service codes: one uint32 per port (65536), got %d" % codes.size)
+        N.check(N.gpu_lib().fb_set_anomaly_model(self.ctx, N.ptr(forest.nodes), len(forest.nodes), N.ptr(forest.first),
+                                                 forest.n_trees, N.ptr(prm), N.ptr(codes)))
+        self._an_model = (forest, (list(mean), list(std), bool(has)), (float(thresholds[0]), float(thresholds[1])))
+        self._an_codes = True
+
+    def clear_anomaly_model(self):
+        """fb_clear_anomaly_model: no model, every record back to zero."""
+        N.check(N.gpu_lib().fb_clear_anomaly_model(self.ctx))
+        self._an_model = None
+
+    def anomaly_pass(self):
+        """fb_flow_anomaly with the installed model -> the pass's counters (fb_an_stats)."""
+        st = np.zeros(1, dtype=N.AN_STATS_DTYPE)
+        N.check(N.gpu_lib().fb_flow_anomaly(self.ctx, 0, N.ptr(st), None))
+        return {k: int(st[0][k]) for k in N.AN_STATS_FIELDS}
+
+    def anomaly_records(self):
+        """fb_flow_anomaly_dev: the AN_REC_DTYPE record of every table slot (index = fb_flow_rec.slot); all
+        zero before the first pass."""
+        cap = int(self.table_info()["capacity"])
+        out = np.zeros(max(cap, 1), dtype=N.AN_REC_DTYPE)
+        if cap:
+            d = N.DeviceBuffer(cap * N.AN_REC_DTYPE.itemsize)
+            N.check(N.gpu_lib().fb_flow_anomaly_dev(self.ctx, d.ptr, cap, None))
+            d.download(out, cap * N.AN_REC_DTYPE.itemsize)
+        return out[:cap]
+
+    def export_features(self):
+        """fb_flow_features_dev: (float64 [flows][10], their table slots) -- the training data."""
+        if not self._an_codes:  # feature 7 reads the device's service codes: the defaults, unless a model brought its own
+            N.check(N.gpu_lib().fb_set_service_codes(self.ctx, N.ptr(default_service_codes())))
+            self._an_codes = True
+        cap = max(self.flow_count(), 1)
+        d_f, d_s, d_n = N.DeviceBuffer(cap * 8 * N.FB_AN_FEATURES), N.DeviceBuffer(cap * 4), N.DeviceBuffer(8)
+        N.check(N.gpu_lib().fb_flow_features_dev(self.ctx, d_f.ptr, d_s.ptr, cap, d_n.ptr, None))
+        m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
+        return (d_f.download(np.zeros((cap, N.FB_AN_FEATURES), dtype=np.float64))[:m],
+                d_s.download(np.zeros(cap, dtype=np.uint32))[:m])
+
+    def export_anomalous_flows(self, min_level=N.FB_AN_SUSPICIOUS):
+        """fb_flow_export_anomalous_dev: (the flows at min_level or above, their records)."""
+        cap = max(self.flow_count(), 1)
+        d_out, d_r, d_n = (N.DeviceBuffer(cap * N.FLOW_REC_DTYPE.itemsize), N.DeviceBuffer(cap * N.AN_REC_DTYPE.itemsize),
+                           N.DeviceBuffer(8))
+        N.check(N.gpu_lib().fb_flow_export_anomalous_dev(self.ctx, int(min_level), d_out.ptr, d_r.ptr, cap, d_n.ptr, None))
+        m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
+        return (d_out.download(np.zeros(cap, dtype=N.FLOW_REC_DTYPE))[:m],
+                d_r.download(np.zeros(cap, dtype=N.AN_REC_DTYPE))[:m])
+
+    def analyze_sessions(self, now_ns=None):
+        """SessionAnalyzer::analyze_sessions (src/analyzer.rs:1200-1570) over every session -- the consumer's
+        call, not part of update_sessions.  Every flow's vector joins the analyzer's recent_data (Session
+        order); during the warm-up (30 s of the caller's clock from the first call) the model is trained and
+        sessions without a tag read "anomaly:normal/warming_up"; after it the model is trained if there is
+        none ("anomaly:normal/no_model" while fewer than two distinct vectors exist), installed, and one
+        device pass scores every flow.  Returns the pass's counters, or None when no pass ran."""
+        a = self.analyzer
+        feats, slots = self.export_features()
+        flows = self.export_flows()
+        by_slot = {int(s): k for k, s in enumerate(slots)}
+        order = sorted(range(len(flows)), key=lambda k: Session.from_key(flows[k]).sort_key())
+        a.add_session_data(feats[by_slot[int(flows[k]["slot"])]] for k in order)
+        warming = a.warming_up(now_ns)
+        if warming or a.forest is None:
+            a.train()
+            self._an_model = None
+        if warming:
+            self._an_mode = "warming_up"
+            return None
+        if a.forest is None:
+            self._an_mode = "no_model"
+            return None
+        want = (a.forest, a.stats, (a.suspicious_threshold, a.abnormal_threshold))
+        if self._an_model is None or self._an_model[0] is not want[0] or self._an_model[1:] != want[1:]:
+            self.set_anomaly_model(*want)
+        self._an_mode = "model"
+        return self.anomaly_pass()
+
+    def _merge_anomaly(self, infos, flows):
+        """The anomaly: tag of the last analysis merged into each SessionInfo's criticality; before any
+        analysis nothing changes.  A flow no pass has seen (inserted since) keeps what it has."""
+        if self._an_mode is None or not infos:
+            return infos
+        if self._an_mode == "model":
+            recs = self.anomaly_records()
+            slot = {Session.from_key(r): int(r["slot"]) for r in flows}
+            for i in infos:
+                rec = recs[slot[i.session]]
+                if rec["level"]:
+                    i.criticality = merge_criticality(i.criticality, *anomaly_tag_of(rec))
+        elif self._an_mode == "warming_up":
+            for i in infos:
+                if not i.criticality:
+                    i.criticality = "anomaly:normal/warming_up"   # src/analyzer.rs:1288-1292
+        else:
+            for i in infos:
+                if "blacklist:" not in i.criticality:
+                    i.criticality = "anomaly:normal/no_model"     # src/analyzer.rs:1547-1551
+        return infos
+
+    def get_anomalous_sessions(self, now_ns=None):
+        """get_anomalous_sessions: the suspicious and abnormal sessions of the last analysis as SessionInfo,
+        in Session order."""
+        if self._an_mode != "model":
+            return []
+        flows, _ = self.export_anomalous_flows(N.FB_AN_SUSPICIOUS)
+        if not len(flows):
+            return []
+        out = flows_to_sessions(flows, self.histories if self.track_history else None,
+                                times=self.export_times() if self.timed else None,
+                                status=self.status_bytes() if self.timed else None,
+                                whitelist=self.whitelist_bytes() if (self._wl_name or self._bl_marked) else None,
+                                blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None)
+        return self._merge_anomaly(out, flows)
+
+    def get_anomalous_status(self):
+        """get_anomalous_status: some session of the last analysis is suspicious or abnormal."""
+        if self._an_mode != "model":
+            return False
+        return len(self.export_anomalous_flows(N.FB_AN_SUSPICIOUS)[0]) > 0
 
     # ---- whitelist conformance (src/whitelists.rs:810-1023, src/capture.rs:131-183, 463-531) ---
     def set_custom_whitelists(self, whitelist_json):

@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -56,7 +57,7 @@ struct UpdScratch {
 // Per-slot planes: arrays beside the table, one element per slot, that a flow's element follows through
 // every slot move.  Described once here; the functions below (plane_ensure .. plane_copy_out) are the
 // only code that allocates, moves, clears or frees one, so a new plane is one entry and its pass.
-enum PlaneId : uint32_t { kPlaneTime, kPlaneStatus, kPlaneWl, kPlaneBl, kPlanes };
+enum PlaneId : uint32_t { kPlaneTime, kPlaneStatus, kPlaneWl, kPlaneBl, kPlaneAn, kPlanes };
 struct PlaneDesc {
     size_t elem;       // bytes per slot
     const char* name;  // in error text
@@ -72,9 +73,10 @@ static const PlaneDesc kPlaneDesc[kPlanes] = {
     {1, "status plane", true, true, launch_plane_remap<uint8_t>},                       // fb_age.hip, kAge*
     {1, "whitelist plane", true, false, launch_plane_remap<uint8_t>},                   // fb_whitelist.hip, FB_WL_*
     {8, "blacklist plane", true, false, launch_plane_remap<unsigned long long>},        // fb_blacklist.hip
+    {sizeof(fb_an_rec), "anomaly plane", true, false, launch_plane_remap<fb_an_rec>},   // fb_anomaly.hip
 };
 // the counter words of one synchronous pass over the table (pass_begin / pass_end)
-constexpr uint32_t kPassStatWords = std::max({kAgeStatWords, kWlCounters, kBlCounters});
+constexpr uint32_t kPassStatWords = std::max({kAgeStatWords, kWlCounters, kBlCounters, kAnCounters});
 
 struct fb_ctx {
     int device = 0;
@@ -149,6 +151,13 @@ struct fb_ctx {
     WlRule* d_wl_rules = nullptr;
     uint32_t *d_wl_owner = nullptr, *d_wl_country = nullptr;
     uint32_t wl_n4 = 0, wl_n6 = 0, wl_ng = 0, wl_nr = 0, wl_records = 0;
+    // anomaly pass (fb_set_anomaly_model / fb_flow_anomaly, fb_anomaly.hip): the installed model
+    bool an_active = false;
+    fb_if_node* d_an_nodes = nullptr;
+    uint32_t* d_an_first = nullptr;
+    uint32_t* d_an_service = nullptr;  // [65536]; null: every code 0
+    uint32_t an_trees = 0;
+    fb_an_params an_prm = {};
     void* d_mscratch = nullptr;   // multi-GPU merge scratch (export owner counts / merge tables)
     hipEvent_t ev_mscratch = nullptr;  // after the last export / merge that used d_mscratch (either may
                                        // run on any stream: the next use waits for it)
@@ -692,6 +701,9 @@ int fb_destroy(fb_ctx* c) {
     hipFree(c->d_wl_rules);
     hipFree(c->d_wl_owner);
     hipFree(c->d_wl_country);
+    hipFree(c->d_an_nodes);
+    hipFree(c->d_an_first);
+    hipFree(c->d_an_service);
     hipFree(c->d_mscratch);
     if (c->ev_mscratch) hipEventDestroy(c->ev_mscratch);
     if (c->h_mbox) hipHostFree(c->h_mbox);
@@ -2237,6 +2249,158 @@ int fb_flow_export_blacklisted_dev(fb_ctx* c, fb_flow_rec* d_out, uint64_t* d_ma
     HIP_TRY(launch_flow_export_blacklisted(c->d_table, c->plane<unsigned long long>(kPlaneBl), c->table_cap, d_out,
                                            (unsigned long long*)d_masks, cap, (unsigned long long*)d_n,
                                            c->plane<FlowTime>(kPlaneTime), s));
+    return FB_OK;
+}
+
+// ---- anomaly pass (fb_anomaly.hip) -------------------------------------------------------------------
+int fb_if_validate(const fb_if_node* nodes, uint64_t n_nodes, const uint32_t* first, uint32_t n_trees) {
+    if (!forest_valid(nodes, n_nodes, first, n_trees))
+        return set_err(FB_ERR_INVAL, "forest: 1..%u trees of 1..%u nodes, children above their parent and inside the tree, "
+                       "leaves at most %u below the root, finite values and normals", FB_IF_MAX_TREES, FB_IF_MAX_TREE_NODES,
+                       FB_IF_MAX_DEPTH);
+    return FB_OK;
+}
+
+static AnForest an_forest(const fb_ctx* c) {
+    AnForest f;
+    if (c->an_active) {
+        f.nodes = c->d_an_nodes;
+        f.first = c->d_an_first;
+        f.n_trees = c->an_trees;
+        f.prm = c->an_prm;
+    }
+    f.service_code = c->d_an_service;
+    return f;
+}
+
+static bool service_codes_valid(const uint32_t* service_code) {
+    for (uint32_t p = 0; service_code && p < 65536u; ++p)
+        if (service_code[p] >= FB_AN_MAX_SERVICE_CODE) return false;
+    return true;
+}
+
+int fb_set_service_codes(fb_ctx* c, const uint32_t* service_code) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    if (!service_codes_valid(service_code)) return set_err(FB_ERR_INVAL, "a service code is %u or above", FB_AN_MAX_SERVICE_CODE);
+    DeviceGuard g(c->device);
+    HIP_TRY(hipDeviceSynchronize());  // no sweep in flight reads the old codes
+    return upload_array(&c->d_an_service, service_code, service_code ? (size_t)65536 : (size_t)0);
+}
+
+// Everything is checked, and the new arrays are on the device, before the installed model is touched.
+int fb_set_anomaly_model(fb_ctx* c, const fb_if_node* nodes, uint64_t n_nodes, const uint32_t* first, uint32_t n_trees,
+                         const fb_an_params* prm, const uint32_t* service_code) {
+    if (!c || !nodes || !first || !prm) return set_err(FB_ERR_INVAL, "bad arguments");
+    const int v = fb_if_validate(nodes, n_nodes, first, n_trees);
+    if (v) return v;
+    for (int j = 0; j < FB_AN_FEATURES; ++j)
+        if (!std::isfinite(prm->mean[j]) || !std::isfinite(prm->std[j]))
+            return set_err(FB_ERR_INVAL, "feature %d: mean / std not finite", j);
+    if (std::isnan(prm->suspicious_cut) || std::isnan(prm->abnormal_cut) || prm->has_stats > 1u)
+        return set_err(FB_ERR_INVAL, "a cut is NaN, or has_stats is not 0 / 1");
+    if (!service_codes_valid(service_code)) return set_err(FB_ERR_INVAL, "a service code is %u or above", FB_AN_MAX_SERVICE_CODE);
+    DeviceGuard g(c->device);
+    fb_if_node* d_nodes = nullptr;
+    uint32_t *d_first = nullptr, *d_service = nullptr;
+    int rc = upload_array(&d_nodes, nodes, (size_t)n_nodes);
+    if (!rc) rc = upload_array(&d_first, first, (size_t)n_trees + 1u);
+    if (!rc) rc = upload_array(&d_service, service_code, service_code ? (size_t)65536 : (size_t)0);
+    hipError_t e = rc ? hipSuccess : hipDeviceSynchronize();  // no pass in flight reads the old arrays
+    if (rc || e != hipSuccess) {
+        hipFree(d_nodes);
+        hipFree(d_first);
+        hipFree(d_service);
+        return rc ? rc : set_err(FB_ERR_HIP, "hipDeviceSynchronize: %s", hipGetErrorString(e));
+    }
+    hipFree(c->d_an_nodes);
+    hipFree(c->d_an_first);
+    hipFree(c->d_an_service);
+    c->d_an_nodes = d_nodes;
+    c->d_an_first = d_first;
+    c->d_an_service = d_service;
+    c->an_trees = n_trees;
+    c->an_prm = *prm;
+    c->an_active = true;
+    return FB_OK;
+}
+
+int fb_clear_anomaly_model(fb_ctx* c) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    DeviceGuard g(c->device);
+    HIP_TRY(hipDeviceSynchronize());
+    c->an_active = false;
+    HIP_TRY(plane_zero(c, kPlaneAn, nullptr));  // every record back to "unseen"
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return FB_OK;
+}
+
+// Synchronous, like fb_flow_blacklist: drains the updates in flight, one pass, the counters read back.
+int fb_flow_anomaly(fb_ctx* c, uint32_t flags, fb_an_stats* out, void* stream) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->an_active) return set_err(FB_ERR_INVAL, "no anomaly model is installed (fb_set_anomaly_model)");
+    if (flags) return set_err(FB_ERR_INVAL, "unknown flags %u", flags);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = pass_begin(c, kAnCounters, s);
+    if (!rc) rc = plane_ensure(c, kPlaneAn, s);
+    if (rc) return rc;
+    HIP_TRY(launch_flow_anomaly(an_forest(c), c->d_table, c->plane<FlowTime>(kPlaneTime), c->table_cap,
+                                c->plane<fb_an_rec>(kPlaneAn), c->d_pass_stats, s));
+    unsigned long long h[kAnCounters] = {};
+    rc = pass_end(c, h, kAnCounters, s);
+    if (rc) return rc;
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        out->flows = h[0];
+        out->normal = h[1];
+        out->suspicious = h[2];
+        out->abnormal = h[3];
+        out->changed = h[4];
+        out->newly_anomalous = h[5];
+        out->cleared = h[6];
+    }
+    return FB_OK;
+}
+
+int fb_flow_anomaly_dev(fb_ctx* c, fb_an_rec* d_out, uint64_t cap, void* stream) {
+    return plane_copy_out(c, kPlaneAn, d_out, cap, stream);
+}
+
+int fb_flow_export_anomalous_dev(fb_ctx* c, uint32_t min_level, fb_flow_rec* d_out, fb_an_rec* d_recs, uint64_t cap,
+                                 uint64_t* d_n, void* stream) {
+    if (!c || !d_n || (cap && !d_out)) return set_err(FB_ERR_INVAL, "bad arguments");
+    if (min_level < FB_AN_NORMAL || min_level > FB_AN_ABNORMAL) return set_err(FB_ERR_INVAL, "min_level %u", min_level);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
+    if (!c->d_table || !c->d_plane[kPlaneAn]) return FB_OK;  // no pass yet: no flow has a level
+    const int rc = join_updates(c, s);
+    if (rc) return rc;
+    HIP_TRY(launch_flow_export_anomalous(c->d_table, c->plane<fb_an_rec>(kPlaneAn), c->table_cap, min_level, d_out, d_recs,
+                                         cap, (unsigned long long*)d_n, c->plane<FlowTime>(kPlaneTime), s));
+    return FB_OK;
+}
+
+int fb_flow_features_dev(fb_ctx* c, double* d_feat, uint32_t* d_slot, uint64_t cap, uint64_t* d_n, void* stream) {
+    if (!c || !d_n || (cap && (!d_feat || !d_slot))) return set_err(FB_ERR_INVAL, "bad arguments");
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
+    if (!c->d_table) return FB_OK;
+    const int rc = join_updates(c, s);
+    if (rc) return rc;
+    HIP_TRY(launch_flow_features(c->d_table, c->plane<FlowTime>(kPlaneTime), an_forest(c).service_code, c->table_cap, d_feat,
+                                 d_slot, cap, (unsigned long long*)d_n, s));
+    return FB_OK;
+}
+
+int fb_if_score_dev(fb_ctx* c, const double* d_feat, uint64_t n, double* d_path_sum, void* stream) {
+    if (!c || (n && (!d_feat || !d_path_sum))) return set_err(FB_ERR_INVAL, "bad arguments");
+    if (!c->an_active) return set_err(FB_ERR_INVAL, "no anomaly model is installed (fb_set_anomaly_model)");
+    if (n == 0) return FB_OK;
+    DeviceGuard g(c->device);
+    HIP_TRY(launch_if_score(an_forest(c), d_feat, n, d_path_sum, (hipStream_t)stream));
     return FB_OK;
 }
 

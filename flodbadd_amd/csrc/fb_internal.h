@@ -806,6 +806,33 @@ hipError_t launch_flow_export_blacklisted(const FlowSlot* table, const unsigned 
                                           fb_flow_rec* out, unsigned long long* out_masks, unsigned long long out_cap,
                                           unsigned long long* d_n, const FlowTime* plane, hipStream_t s);
 
+// Anomaly pass over the table (fb_anomaly.hip, fb_flow_anomaly): one fb_an_rec per table slot -- the sum
+// of the leaf values of the flow's walk through the installed forest, its level against the two cuts and
+// its diagnostic codes; all zero: no pass has seen the flow.  The call's device counters are
+// fb_an_stats' first seven fields, in order.
+constexpr uint32_t kAnCounters = 7;
+static_assert(sizeof(fb_if_node) == 96 && sizeof(fb_an_rec) == 16 && sizeof(fb_an_params) == 184, "anomaly ABI");
+struct AnForest {  // the installed model (device pointers)
+    const fb_if_node* nodes = nullptr;
+    const uint32_t* first = nullptr;         // [n_trees + 1]
+    const uint32_t* service_code = nullptr;  // [65536], or null: zeros
+    uint32_t n_trees = 0;
+    fb_an_params prm = {};
+};
+// fb_if_validate's rules (host): they bound the device's walk
+bool forest_valid(const fb_if_node* nodes, uint64_t n_nodes, const uint32_t* first, uint32_t n_trees);
+// plane: the time plane of a timed context (features 1 and 4), else null
+hipError_t launch_flow_anomaly(const AnForest& f, const FlowSlot* table, const FlowTime* plane, unsigned long long cap,
+                               fb_an_rec* recs, unsigned long long* stats, hipStream_t s);
+hipError_t launch_if_score(const AnForest& f, const double* feat, unsigned long long n, double* path_sum, hipStream_t s);
+hipError_t launch_flow_features(const FlowSlot* table, const FlowTime* plane, const uint32_t* service_code,
+                                unsigned long long cap, double* feat, uint32_t* slot, unsigned long long out_cap,
+                                unsigned long long* d_n, hipStream_t s);
+hipError_t launch_flow_export_anomalous(const FlowSlot* table, const fb_an_rec* recs, unsigned long long cap,
+                                        uint32_t min_level, fb_flow_rec* out, fb_an_rec* out_recs,
+                                        unsigned long long out_cap, unsigned long long* d_n, const FlowTime* plane,
+                                        hipStream_t s);
+
 // Whitelist conformance (fb_whitelist.hip, fb_flow_whitelist).  fb_set_whitelist compiles the endpoint
 // list into three structures (build_whitelist_index):
 //   exact   the endpoints that match by one address: per family the addresses ascending and, beside

@@ -198,7 +198,8 @@ class SessionInfo:
     is_whitelisted / whitelist_reason are what the last whitelist pass left (Unknown before it), or
     NonConforming / "Session is blacklisted" where the blacklist pass found the session Unknown
     (src/capture.rs:1858-1871); criticality holds the sorted "blacklist:<name>" tags of the last
-    blacklist pass (src/blacklists.rs:612-631; "" before it -- there are no anomaly tags)."""
+    blacklist pass (src/blacklists.rs:612-631; "" before it) and, once FlodbaddGpuCapture.analyze_sessions
+    has run, the merged "anomaly:<level>[/<diagnostic>]" tag (src/analyzer.rs:630-653)."""
     session: Session
     stats: SessionStats = field(default_factory=SessionStats)
     is_local_src: bool = False

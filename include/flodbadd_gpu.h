@@ -869,6 +869,118 @@ int fb_flow_blacklist_dev(fb_ctx* ctx, uint64_t* d_out, uint64_t cap, void* stre
 int fb_flow_export_blacklisted_dev(fb_ctx* ctx, fb_flow_rec* d_out, uint64_t* d_masks, uint64_t cap, uint64_t* d_n,
                                    void* stream);
 
+/* ---- anomaly pass over the session table (src/analyzer.rs) -------------------------------------------
+ * The reference's SessionAnalyzer scores every session with an Extended Isolation Forest over a
+ * 10-feature vector (compute_features, src/analyzer.rs:716-793) and writes "anomaly:<level>[/<diagnostic>]"
+ * into `criticality` (analyze_session, 562-660).  The forest crate's generator and tree layout are not
+ * part of the reference's sources, so the model is DEFINED here: the host trains and
+ * installs a forest in the format below, the device computes the features of every flow from the table,
+ * walks every tree in f64 and keeps, per table slot, the exact sum of the leaf values, the level and the
+ * diagnostic codes.  Every operation is a separately rounded IEEE double operation (no fused
+ * multiply-add), so a host restatement reproduces every bit.
+ *
+ * Features (index: value), one double[FB_AN_FEATURES] per flow:
+ *   0 process: 0.0 (no L7 here)                      1 duration: timed contexts, (double)ms / 1000.0 with
+ *   ms = (int64)(t - start_time_ns) / 1000000 (truncated toward zero; may be negative), t = end_time_ns
+ *   when set, else last_activity_ns; untimed contexts 0.0 (no clock)
+ *   2 (double)(inbound_bytes + outbound_bytes)       3 (double)(orig_pkts + resp_pkts)
+ *   4 segment interarrival: timed, div ? ((double)total_segment_interarrival_ms / 1000.0) / (double)div
+ *     : 0.0; untimed 0.0                             5 outbound ? (double)inbound / (double)outbound : 0.0
+ *   6 packets ? (double)(in + out) / (double)(orig + resp) : 0.0
+ *   7 (double)service_code[dst_port] when the stored FB_SESSION_DST_SERVICE flag is set, else 0.0
+ *   8 1.0 when the stored FB_SESSION_SELF_DST flag is set, else 0.0         9 missed bytes: 0.0
+ *   (src/packets.rs:364: always 0 on the capture path) */
+#define FB_AN_FEATURES 10
+#define FB_IF_MAX_TREES 64
+#define FB_IF_MAX_TREE_NODES 255 /* sample_size <= 128 -> at most 255 nodes */
+#define FB_IF_MAX_DEPTH 12       /* the reference's recursion cap, src/analyzer.rs:523 */
+#define FB_IF_LEAF 0xFFFFFFFFu
+#define FB_AN_MAX_SERVICE_CODE 1000000u /* service codes are below this */
+typedef struct fb_if_node {        /* 96 bytes */
+    double normal[FB_AN_FEATURES]; /*  0: internal node: split normal; leaf: zeros                       */
+    double value;                  /* 80: internal: split offset b; leaf: depth + c(size), host-computed */
+    uint32_t left, right;          /* 88, 92: indices RELATIVE to the tree's first node, both > this
+                                      node's index; left == FB_IF_LEAF marks a leaf                       */
+} fb_if_node;
+/* Tree t is nodes [first[t], first[t + 1]), its root first; first[0] = 0, first[n_trees] = n_nodes.
+ * The walk of one tree: from the root, at an internal node s = 0.0; for j = 0..9: s = s + x[j] *
+ * normal[j] (each product and each sum rounded on its own); left iff s < value (a NaN goes right); at
+ * the leaf its value is added to path_sum (0.0 at the start, trees in order). */
+typedef struct fb_an_params {
+    double mean[FB_AN_FEATURES];   /*   0: feature_stats, src/analyzer.rs:317-353                        */
+    double std[FB_AN_FEATURES];    /*  80 */
+    double suspicious_cut;         /* 160: level 2 iff path_sum <= suspicious_cut (and not level 3)      */
+    double abnormal_cut;           /* 168: level 3 iff path_sum <= abnormal_cut; a cut is -log2(score
+                                      threshold) * c(sample_size) * n_trees, i.e. score >= threshold
+                                      (src/analyzer.rs:586-592) decided on the path sum                   */
+    uint32_t has_stats;            /* 176: 0 / 1: the reference's counts > 1; 0: every diagnostic code 0 */
+    uint32_t sample_size;          /* 180: the forest's sample size (kept for the host's score)          */
+} fb_an_params;                    /* 184 bytes */
+enum fb_an_level { FB_AN_UNSEEN = 0, FB_AN_NORMAL = 1, FB_AN_SUSPICIOUS = 2, FB_AN_ABNORMAL = 3 };
+/* Diagnostic codes (src/analyzer.rs:356-487), two bits per feature i in fb_an_rec.diag (bits 2i, 2i + 1),
+ * only for a suspicious or abnormal flow: the reference's FEATURE_DEFS call indices 0, 6 and 8
+ * categorical (its table names index 6 DestService and index 7 AvgPacketSize although the vector holds
+ * them the other way round; kept).  Categorical: FB_AN_DIAG_DEVIATES iff std <= 1e-6 && |x - mean| >
+ * 1e-6.  Numeric: std > 1e-6: z = (x - mean) / std, HIGH iff z >= 2.5, LOW iff z <= -2.5; else
+ * DEVIATES iff |x - mean| > 1e-6. */
+enum fb_an_diag { FB_AN_DIAG_NONE = 0, FB_AN_DIAG_HIGH = 1, FB_AN_DIAG_LOW = 2, FB_AN_DIAG_DEVIATES = 3 };
+typedef struct fb_an_rec {
+    double path_sum;     /*  0: sum of the leaf values over the trees                                    */
+    uint32_t diag;       /*  8: fb_an_diag codes                                                         */
+    uint8_t level;       /* 12: fb_an_level; 0 with the other fields 0: no pass has seen the flow        */
+    uint8_t reserved[3]; /* 13 */
+} fb_an_rec;             /* 16 bytes */
+typedef struct fb_an_stats {
+    uint64_t flows;           /* flows in the table                                                      */
+    uint64_t normal;          /* level after the call                                                    */
+    uint64_t suspicious;
+    uint64_t abnormal;
+    uint64_t changed;         /* the record differs from before the call                                 */
+    uint64_t newly_anomalous; /* level < 2 before, >= 2 after                                            */
+    uint64_t cleared;         /* level >= 2 before, < 2 after                                            */
+    uint64_t reserved;
+} fb_an_stats; /* 64 bytes */
+/* FB_OK iff the forest is one fb_set_anomaly_model installs: 1 <= n_trees <= FB_IF_MAX_TREES, first[]
+ * as above with 1 <= nodes per tree <= FB_IF_MAX_TREE_NODES, every child index above its parent's and
+ * inside the tree, every leaf at most FB_IF_MAX_DEPTH below the root, every value and normal finite.
+ * These rules bound the device's walk.  Host only: needs no device. */
+int fb_if_validate(const fb_if_node* nodes, uint64_t n_nodes, const uint32_t* first, uint32_t n_trees);
+/* The service codes alone (HOST pointer, copied): uint32[65536] indexed by port, each <
+ * FB_AN_MAX_SERVICE_CODE; NULL = zeros, the state of a new context.  They are what feature 7 reads, in
+ * fb_flow_features_dev too, so training data can be exported before there is a model. */
+int fb_set_service_codes(fb_ctx* ctx, const uint32_t* service_code);
+/* Install the model (HOST pointers, copied): the forest, its parameters and the service codes (as
+ * fb_set_service_codes; NULL = zeros).  FB_ERR_INVAL -- and the installed model and codes stay as they
+ * were -- for a forest fb_if_validate rejects, a non-finite mean / std, a NaN cut, has_stats > 1 or a
+ * service code out of range.  The plane keeps its records. */
+int fb_set_anomaly_model(fb_ctx* ctx, const fb_if_node* nodes, uint64_t n_nodes, const uint32_t* first,
+                         uint32_t n_trees, const fb_an_params* params, const uint32_t* service_code);
+/* No model installed (the service codes stay); every record back to zero (as fb_clear_whitelist does
+ * with its states). */
+int fb_clear_anomaly_model(fb_ctx* ctx);
+/* One pass over every flow with the installed model.  Synchronous: waits for the updates in flight, like
+ * fb_flow_blacklist; timed and untimed contexts.  `flags` must be 0; `out` may be NULL.  FB_ERR_INVAL
+ * without a flow table or without a model. */
+int fb_flow_anomaly(fb_ctx* ctx, uint32_t flags, fb_an_stats* out, void* stream);
+/* The record of every table slot (min(cap, capacity) records, slot order; zeros before the first pass)
+ * into DEVICE memory.  Asynchronous.  Records follow their flows through a growth and a purge, and
+ * fb_flow_clear zeroes them. */
+int fb_flow_anomaly_dev(fb_ctx* ctx, fb_an_rec* d_out, uint64_t cap, void* stream);
+/* The fb_flow_rec of the flows whose level is >= min_level (1..3), and beside each its record in
+ * d_recs[cap] (may be NULL); order as fb_flow_export_blacklisted_dev.  *d_n (device u64) = the matching
+ * flows (only the first `cap` are written).  DEVICE pointers, asynchronous. */
+int fb_flow_export_anomalous_dev(fb_ctx* ctx, uint32_t min_level, fb_flow_rec* d_out, fb_an_rec* d_recs,
+                                 uint64_t cap, uint64_t* d_n, void* stream);
+/* Every flow's feature vector (the training data): d_feat[cap][FB_AN_FEATURES] and beside each its table
+ * slot in d_slot[cap]; *d_n = the flows.  Needs no model (feature 7 reads the installed service codes).
+ * DEVICE pointers, asynchronous. */
+int fb_flow_features_dev(fb_ctx* ctx, double* d_feat, uint32_t* d_slot, uint64_t cap, uint64_t* d_n,
+                         void* stream);
+/* The walk over n caller-supplied vectors d_feat[n][FB_AN_FEATURES] -> d_path_sum[n], with the installed
+ * forest and the pass's own device function.  FB_ERR_INVAL without a model.  DEVICE pointers,
+ * asynchronous. */
+int fb_if_score_dev(fb_ctx* ctx, const double* d_feat, uint64_t n, double* d_path_sum, void* stream);
+
 /* ---- multi-GPU session table (BASELINE configs[4]) ------------------------------
  * The reference runs one capture task per interface into ONE shared DashMap (src/capture.rs:946-1016,
  * src/packets.rs:329-535); W ranks that each parse a contiguous packet-index shard into their own
