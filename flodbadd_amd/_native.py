@@ -102,6 +102,16 @@ AN_STATS_DTYPE = np.dtype([(f, "<u8") for f in AN_STATS_FIELDS] + [("reserved", 
 assert (IF_NODE_DTYPE.itemsize, AN_PARAMS_DTYPE.itemsize, AN_REC_DTYPE.itemsize, AN_STATS_DTYPE.itemsize) == (96, 184, 16, 64)
 FB_AN_UNSEEN, FB_AN_NORMAL, FB_AN_SUSPICIOUS, FB_AN_ABNORMAL = 0, 1, 2, 3
 FB_AN_DIAG_HIGH, FB_AN_DIAG_LOW, FB_AN_DIAG_DEVIATES = 1, 2, 3
+# fb_flow_view / fb_view_query (fb_flow_export_view: one joined record per selected flow; the incremental
+# getters, src/capture.rs:1578-1760): last_modified_ns = max(time.last_activity_ns, stamp_ns)
+FLOW_VIEW_DTYPE = np.dtype([("rec", FLOW_REC_DTYPE), ("time", FLOW_TIME_DTYPE), ("last_modified_ns", "<u8"),
+                            ("stamp_ns", "<u8"), ("bl_mask", "<u8"), ("an", AN_REC_DTYPE), ("status", "u1"),
+                            ("wl_state", "u1"), ("reserved", "u1", (14,))])
+VIEW_QUERY_DTYPE = np.dtype([("since_ns", "<u8"), ("set", "<u4"), ("filter", "<u4"), ("flags", "<u4"),
+                             ("reserved", "<u4")])
+assert FLOW_VIEW_DTYPE.itemsize == 256 and VIEW_QUERY_DTYPE.itemsize == 24
+FB_VIEW_ALL, FB_VIEW_CURRENT, FB_VIEW_BLACKLISTED, FB_VIEW_WL_EXCEPTIONS, FB_VIEW_ANOMALOUS = 0, 1, 2, 3, 4
+FB_VIEW_MODIFIED_SINCE = 1
 FB_SEGMENT_TIMEOUT_MS = 5000
 FB_CFG_TIMED = 2
 FB_QUEUE_SHARED = 1
@@ -210,7 +220,7 @@ class FbError(RuntimeError):
 # Every symbol include/flodbadd_gpu.h declares: (name, restype, argtypes).
 _P, _U32, _U64, _I = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 _PU32, _PU64 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
-FB_DEBUG_DENSE_STEAL_POLLS, FB_DEBUG_DENSE_OFFSET_SKEW = 1, 2
+FB_DEBUG_DENSE_STEAL_POLLS, FB_DEBUG_DENSE_OFFSET_SKEW, FB_DEBUG_VIEW_DIRECT = 1, 2, 3
 
 GPU_SYMBOLS = [
     ("fb_abi_version", _U32, []),
@@ -317,6 +327,10 @@ GPU_SYMBOLS = [
     ("fb_flow_export_anomalous_dev", _I, [_P, _U32, _P, _P, _U64, _P, _P]),
     ("fb_flow_features_dev", _I, [_P, _P, _P, _U64, _P, _P]),
     ("fb_if_score_dev", _I, [_P, _P, _U64, _P, _P]),
+    ("fb_set_pass_time", _I, [_P, _U64]),
+    ("fb_flow_modified_dev", _I, [_P, _P, _U64, _P]),
+    ("fb_flow_export_view_dev", _I, [_P, _P, _P, _U64, _P, _P]),
+    ("fb_flow_export_view", _I, [_P, _P, _P, _U64, _PU64, _P]),
 ]
 
 _gpu = None

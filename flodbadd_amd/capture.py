@@ -15,7 +15,8 @@ import ipaddress
 import numpy as np
 
 from . import _native as N
-from .sessions import Session, SessionFilter, WhitelistState, flows_to_sessions, ip_to_words, is_lan_ip
+from .sessions import (Session, SessionFilter, WhitelistState, flows_to_sessions, ip_to_words, is_lan_ip,
+                       views_to_sessions)
 from .enrich import Blacklists
 from .analyzer import SessionAnalyzer, anomaly_tag_of, default_service_codes, merge_criticality, path_cut
 from .whitelists import Whitelists, is_session_in_whitelist, no_match_reason
@@ -115,6 +116,10 @@ class FlodbaddGpuCapture:
         self._an_model = None
         self._an_mode = None
         self._an_codes = False  # the device holds service codes (analyzer.default_service_codes, or a model's)
+        # incremental queries (src/capture.rs:411-426): the time of each getter's last full fetch (0: the
+        # reference's epoch), and whether a pass time was ever set (the stamp plane may then hold stamps)
+        self._fetch_ts = dict.fromkeys(("sessions", "current", "blacklisted", "exceptions"), 0)
+        self._stamped = False
 
     # ---- configuration -------------------------------------------------------------------
     def set_filter(self, flt):
@@ -337,6 +342,51 @@ class FlodbaddGpuCapture:
             d.download(out, cap)
         return out[:cap]
 
+    # ---- incremental queries (src/capture.rs:411-426, 1578-1760) -------------------------------------
+    def set_pass_time(self, now_ns):
+        """fb_set_pass_time: the time -- on the capture timestamps' clock -- that the blacklist, whitelist and
+        anomaly passes write into the sessions they change (SessionInfo.last_modified_ns); 0: no stamps."""
+        N.check(N.gpu_lib().fb_set_pass_time(self.ctx, int(now_ns)))
+        self._stamped = self._stamped or int(now_ns) != 0
+
+    def reset_fetch_timestamps(self):
+        """reset_fetch_timestamps (src/capture.rs:411-426): every getter's next incremental fetch is full."""
+        self._fetch_ts = dict.fromkeys(self._fetch_ts, 0)
+
+    def modified_stamps(self):
+        """fb_flow_modified_dev: the stamp of every table slot (index = fb_flow_rec.slot); all zero while no
+        pass has run under a pass time."""
+        cap = int(self.table_info()["capacity"])
+        out = np.zeros(max(cap, 1), dtype=np.uint64)
+        if cap:
+            d = N.DeviceBuffer(cap * 8)
+            N.check(N.gpu_lib().fb_flow_modified_dev(self.ctx, d.ptr, cap, None))
+            d.download(out, cap * 8)
+        return out[:cap]
+
+    def export_view(self, view_set=N.FB_VIEW_ALL, since_ns=None, session_filter=None):
+        """fb_flow_export_view: the FLOW_VIEW_DTYPE records of the flows of `view_set` (N.FB_VIEW_*) that pass
+        session_filter evaluated now (None: every flow) and, with since_ns, whose last_modified_ns is later
+        than it (timed captures)."""
+        q = np.zeros(1, dtype=N.VIEW_QUERY_DTYPE)
+        q[0]["set"] = int(view_set)
+        q[0]["filter"] = int(SessionFilter.All if session_filter is None else session_filter)
+        if since_ns is not None:
+            q[0]["flags"], q[0]["since_ns"] = N.FB_VIEW_MODIFIED_SINCE, int(since_ns)
+        cnt = self.flow_count() if self.flow_capacity else 1
+        out = np.zeros(max(cnt, 1), dtype=N.FLOW_VIEW_DTYPE)
+        n = C.c_uint64(0)
+        N.check(N.gpu_lib().fb_flow_export_view(self.ctx, N.ptr(q), N.ptr(out), cnt, C.byref(n), None))
+        return out[: n.value]
+
+    def _incremental(self, which):
+        if not self.timed:
+            raise ValueError("incremental fetches need a timed capture (timed=True): last_modified has no clock")
+        return self._fetch_ts[which]
+
+    def _modified(self):
+        return self.modified_stamps() if self._stamped else None
+
     def update_sessions_status(self, now_ns, purge=True, activity_s=60, current_s=180, retention_s=86400):
         """update_sessions_status (src/capture.rs:1497-1551) at `now_ns` on the capture timestamps'
         clock (timed captures): every session's status and current_sessions membership recomputed, and
@@ -354,38 +404,62 @@ class FlodbaddGpuCapture:
             self._follow_growth()
         return {k: int(st[0][k]) for k in N.AGE_STATS_FIELDS}
 
-    def get_sessions(self, now_ns=None):
+    def get_sessions(self, now_ns=None, incremental=False):
         """get_sessions (src/capture.rs:1578-1612): the sessions that pass the CURRENT filter,
         is_local_session! evaluated at query time on the GPU (capture.rs:1603-1608), sorted by the
         derived Ord of Session (integer counters + derived f64s).  With now_ns (timed captures) the
-        table is aged first, as the reference does on every query (capture.rs:1581)."""
+        table is aged first, as the reference does on every query (capture.rs:1581).  incremental
+        (capture.rs:1583-1621): only the sessions modified since this getter's last full fetch with a
+        now_ns, from one view export; a full fetch with now_ns moves that timestamp, nothing else does."""
+        since = self._incremental("sessions") if incremental else None
         if now_ns is not None:
             self.update_sessions_status(now_ns)
+        if incremental:
+            views = self.export_view(N.FB_VIEW_ALL, since, self.filter)
+            out = views_to_sessions(views, self.histories if self.track_history else None, self._bl_names,
+                                    whitelist=bool(self._wl_name or self._bl_marked), blacklist=self._bl_ran)
+            return self._merge_anomaly(self._overlay_host_ok(out), views["rec"], views)
+        if now_ns is not None:
+            self._fetch_ts["sessions"] = int(now_ns)
         flows = self.export_flows(self.filter)
         out = flows_to_sessions(flows, self.histories if self.track_history else None,
                                 times=self.export_times() if self.timed else None,
                                 status=self.status_bytes() if self.timed else None,
                                 whitelist=self.whitelist_bytes() if (self._wl_name or self._bl_marked) else None,
-                                blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None)
+                                blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None,
+                                modified=self._modified())
+        return self._merge_anomaly(self._overlay_host_ok(out), flows)
+
+    def _overlay_host_ok(self, out):
         for info in out if self._wl_host_ok else ():  # the host's verdict for the flows the pass left to it
             if info.session in self._wl_host_ok and info.is_whitelisted is WhitelistState.NonConforming:
                 info.is_whitelisted = WhitelistState.Conforming
-        return self._merge_anomaly(out, flows)
+        return out
 
-    def get_current_sessions(self, now_ns=None):
+    def get_current_sessions(self, now_ns=None, incremental=False):
         """get_current_sessions (src/capture.rs:1624-1670): the members of current_sessions -- activity
         within the current span at the last aging, or inserted since (src/packets.rs:532) -- that pass
-        the current filter.  With now_ns the table is aged first."""
+        the current filter.  With now_ns the table is aged first.  incremental: as get_sessions, with this
+        getter's own fetch timestamp (capture.rs:1629-1666)."""
         if not self.timed:
             raise ValueError("current sessions need a timed capture (timed=True)")
+        since = self._incremental("current") if incremental else None
         if now_ns is not None:
             self.update_sessions_status(now_ns)
+        if incremental:
+            views = self.export_view(N.FB_VIEW_CURRENT, since, self.filter)
+            out = views_to_sessions(views, self.histories if self.track_history else None, self._bl_names,
+                                    whitelist=False, blacklist=self._bl_ran)
+            return self._merge_anomaly(out, views["rec"], views)
+        if now_ns is not None:
+            self._fetch_ts["current"] = int(now_ns)
         flows, status = self.export_flows(self.filter), self.status_bytes()
         b = status[flows["slot"]] if len(flows) else np.zeros(0, dtype=np.uint8)
         flows = flows[(b == 0) | ((b & N.STATUS_CURRENT) != 0)]
         out = flows_to_sessions(flows, self.histories if self.track_history else None, times=self.export_times(),
                                 status=status,
-                                blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None)
+                                blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None,
+                                modified=self._modified())
         return self._merge_anomaly(out, flows)
 
     # ---- new-session enrichment (src/packets.rs:429-485) -------------------------------------
@@ -476,11 +550,20 @@ class FlodbaddGpuCapture:
         return (d_out.download(np.zeros(cap, dtype=N.FLOW_REC_DTYPE))[:m],
                 d_m.download(np.zeros(cap, dtype=np.uint64))[:m])
 
-    def get_blacklisted_sessions(self, now_ns=None):
+    def get_blacklisted_sessions(self, now_ns=None, incremental=False):
         """get_blacklisted_sessions(false) (src/capture.rs:1680-1719): after an update, the sessions of
         the blacklisted list as SessionInfo, in the order new_blacklisted_sessions.sort() leaves the
-        keys (src/blacklists.rs:693)."""
+        keys (src/blacklists.rs:693).  incremental: as get_sessions, with this getter's own fetch timestamp
+        (capture.rs:1688-1715)."""
+        since = self._incremental("blacklisted") if incremental else None
         self.update_sessions(now_ns, *self._wl_inputs)
+        if incremental:
+            views = self.export_view(N.FB_VIEW_BLACKLISTED, since)
+            out = views_to_sessions(views, self.histories if self.track_history else None, self._bl_names,
+                                    timed=self.timed, whitelist=bool(self._wl_name or self._bl_marked))
+            return self._merge_anomaly(out, views["rec"], views)
+        if now_ns is not None:
+            self._fetch_ts["blacklisted"] = int(now_ns)
         flows, masks = self.export_blacklisted_flows()
         if not len(flows):
             return []
@@ -489,7 +572,7 @@ class FlodbaddGpuCapture:
                                 times=self.export_times() if self.timed else None,
                                 status=self.status_bytes() if self.timed else None,
                                 whitelist=self.whitelist_bytes() if (self._wl_name or self._bl_marked) else None,
-                                blacklist=(by_slot, self._bl_names))
+                                blacklist=(by_slot, self._bl_names), modified=self._modified())
         return self._merge_anomaly(out, flows)
 
     def get_blacklisted_status(self, now_ns=None):
@@ -500,7 +583,10 @@ class FlodbaddGpuCapture:
         """update_sessions_internal's per-session passes in the reference's order (src/capture.rs:
         1811-1882): the status (timed captures, when now_ns is given), the blacklist pass with its
         whitelist fallback, then the whitelist pass when a list is active.  Returns the three calls'
-        counters ({"status", "blacklist", "whitelist"}; None for a pass that did not run)."""
+        counters ({"status", "blacklist", "whitelist"}; None for a pass that did not run).  With now_ns
+        the passes stamp the sessions they change with it (set_pass_time)."""
+        if now_ns is not None:
+            self.set_pass_time(now_ns)
         age = self.update_sessions_status(now_ns) if (self.timed and now_ns is not None) else None
         bl = self.update_blacklist(mark_whitelist=True)
         wl = self.update_whitelist(dns_resolutions, process_names)
@@ -576,7 +662,10 @@ class FlodbaddGpuCapture:
         order); during the warm-up (30 s of the caller's clock from the first call) the model is trained and
         sessions without a tag read "anomaly:normal/warming_up"; after it the model is trained if there is
         none ("anomaly:normal/no_model" while fewer than two distinct vectors exist), installed, and one
-        device pass scores every flow.  Returns the pass's counters, or None when no pass ran."""
+        device pass scores every flow.  Returns the pass's counters, or None when no pass ran.  With now_ns
+        the pass stamps the sessions whose tag it changes with it (set_pass_time)."""
+        if now_ns is not None:
+            self.set_pass_time(now_ns)
         a = self.analyzer
         feats, slots = self.export_features()
         flows = self.export_flows()
@@ -599,13 +688,14 @@ class FlodbaddGpuCapture:
         self._an_mode = "model"
         return self.anomaly_pass()
 
-    def _merge_anomaly(self, infos, flows):
+    def _merge_anomaly(self, infos, flows, views=None):
         """The anomaly: tag of the last analysis merged into each SessionInfo's criticality; before any
-        analysis nothing changes.  A flow no pass has seen (inserted since) keeps what it has."""
+        analysis nothing changes.  A flow no pass has seen (inserted since) keeps what it has.  views: the
+        fb_flow_view records `flows` came from (their anomaly records are used instead of the plane's copy)."""
         if self._an_mode is None or not infos:
             return infos
         if self._an_mode == "model":
-            recs = self.anomaly_records()
+            recs = self.anomaly_records() if views is None else {int(v["rec"]["slot"]): v["an"] for v in views}
             slot = {Session.from_key(r): int(r["slot"]) for r in flows}
             for i in infos:
                 rec = recs[slot[i.session]]
@@ -762,12 +852,27 @@ class FlodbaddGpuCapture:
         self.update_whitelist(*self._wl_inputs)
         return self._wl_conformance
 
-    def get_whitelist_exceptions(self):
+    def get_whitelist_exceptions(self, now_ns=None, incremental=False):
         """get_whitelist_exceptions(false) (src/capture.rs:1721-1760): the NonConforming sessions as
         SessionInfo, sorted by Session as new_exceptions.sort() leaves the keys (whitelists.rs:951),
-        each with the reference's whitelist_reason."""
+        each with the reference's whitelist_reason.  With now_ns the pass stamps the sessions it changes
+        with it; incremental: as get_sessions, with this getter's own fetch timestamp (capture.rs:1729-1756).
+        The host's verdict for a host-check flow (process names) applies in both paths and stamps nothing."""
+        since = self._incremental("exceptions") if incremental else None
+        if now_ns is not None:
+            self.set_pass_time(now_ns)
         self.update_whitelist(*self._wl_inputs)
-        exc = self._wl_exceptions
+        views = None
+        if incremental:
+            views = self.export_view(N.FB_VIEW_WL_EXCEPTIONS, since) if self._wl_name \
+                else np.zeros(0, dtype=N.FLOW_VIEW_DTYPE)
+            if self._wl_host_ok and len(views):
+                views = views[np.array([Session.from_key(r) not in self._wl_host_ok for r in views["rec"]], dtype=bool)]
+            exc = np.ascontiguousarray(views["rec"])
+        else:
+            if now_ns is not None:
+                self._fetch_ts["exceptions"] = int(now_ns)
+            exc = self._wl_exceptions
         if not len(exc):
             return []
         dns, proc = self._wl_inputs[0] or {}, self._wl_inputs[1] or {}
@@ -779,9 +884,13 @@ class FlodbaddGpuCapture:
             # (an exception is a session no endpoint matched: the reason needs no second scan of the list)
             reasons[s] = no_match_reason(comp.endpoints, comp.name, dns.get(str(s.dst_ip)), str(s.dst_ip), s.dst_port,
                                          s.protocol.name, a[0], a[1], a[2], proc.get(s))
-        out = flows_to_sessions(exc, self.histories if self.track_history else None,
-                                times=self.export_times() if self.timed else None,
-                                status=self.status_bytes() if self.timed else None)
+        if views is not None:
+            out = views_to_sessions(views, self.histories if self.track_history else None, whitelist=False,
+                                    blacklist=False)
+        else:
+            out = flows_to_sessions(exc, self.histories if self.track_history else None,
+                                    times=self.export_times() if self.timed else None,
+                                    status=self.status_bytes() if self.timed else None, modified=self._modified())
         for info in out:
             info.is_whitelisted = WhitelistState.NonConforming
             info.whitelist_reason = reasons[info.session]

@@ -168,9 +168,14 @@ __device__ __forceinline__ uint32_t an_diag(const fb_an_params& p, const double 
 // Per occupied slot the 128-B table line, the 64-B time record (timed contexts) and the 16-B record, read
 // and -- when it changed -- written; the forest comes from L2, staged once per step of 256 slots.  A step
 // without an occupied slot stages nothing.  Counters: PassCounters, fb_an_stats' first seven fields.
+// kStamp (a pass time is set, fb_set_pass_time): the flows whose level or diagnostic codes changed -- the two
+// fields the criticality string shows -- get `now` in the stamp plane; a new path_sum alone does not stamp
+// (DESIGN.md 7).  The unstamped instance holds no such store.
+template <bool kStamp>
 __global__ __launch_bounds__(256) void k_flow_anomaly(const AnModel m, const FlowSlot* T, const FlowTime* plane,
                                                       unsigned long long cap, fb_an_rec* recs,
-                                                      unsigned long long* stats) {
+                                                      unsigned long long* stats, unsigned long long* mod,
+                                                      unsigned long long now) {
     PassCounters<kAnCounters> cnt;
     const unsigned long long stride = (unsigned long long)gridDim.x * 256u;
     for (unsigned long long base = (unsigned long long)blockIdx.x * 256u; base < cap; base += stride) {
@@ -197,6 +202,7 @@ __global__ __launch_bounds__(256) void k_flow_anomaly(const AnModel m, const Flo
                 nw.reserved[0] = nw.reserved[1] = nw.reserved[2] = 0u;
                 recs[i] = nw;
             }
+            if (kStamp && (old.diag != diag || old.level != level)) mod[i] = now;
         }
         cnt.add(0, occ);
         cnt.add(1, level == FB_AN_NORMAL);
@@ -269,10 +275,11 @@ static AnModel model_of(const AnForest& f) {
 }
 
 hipError_t launch_flow_anomaly(const AnForest& f, const FlowSlot* table, const FlowTime* plane, unsigned long long cap,
-                               fb_an_rec* recs, unsigned long long* stats, hipStream_t s) {
+                               fb_an_rec* recs, unsigned long long* stats, hipStream_t s, unsigned long long* mod,
+                               unsigned long long now) {
     if (!f.nodes || !f.first || !f.n_trees || !table || !recs || !stats || cap == 0ull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_flow_anomaly, dim3(sweep_grid(cap, FB_AN_GRID)), dim3(256), 0, s, model_of(f), table, plane, cap,
-                       recs, stats);
+    hipLaunchKernelGGL(mod ? k_flow_anomaly<true> : k_flow_anomaly<false>, dim3(sweep_grid(cap, FB_AN_GRID)), dim3(256), 0,
+                       s, model_of(f), table, plane, cap, recs, stats, mod, now);
     return hipGetLastError();
 }
 

@@ -22,11 +22,15 @@ namespace fbk {
 // (flow_lookups of fb_enrich.hip without its ASN half).  The word is stored only when it changed.
 // kMark (FB_BL_MARK_WHITELIST): a flow with a non-zero mask whose whitelist state byte is 0 (Unknown)
 // gets FB_WL_NONCONFORMING | FB_WL_BLACKLISTED; no other byte of that plane is read or written.
+// kStamp (a pass time is set, fb_set_pass_time): the flows whose word changed, and those the fallback
+// marked, get `now` in the stamp plane -- the reference's last_modified bumps (src/blacklists.rs:655-689,
+// src/capture.rs:1867-1868).  The unstamped instances hold no such store.
 // Counters: PassCounters (fb_internal.h).
-template <bool kMark>
+template <bool kMark, bool kStamp>
 __global__ __launch_bounds__(256) void k_flow_blacklist(const EnrichTables t, const FlowSlot* T, unsigned long long cap,
                                                         unsigned long long* mask, uint8_t* wl,
-                                                        unsigned long long* stats) {
+                                                        unsigned long long* stats, unsigned long long* mod,
+                                                        unsigned long long now) {
     PassCounters<kBlCounters> cnt;
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < cap; base += stride) {
@@ -59,6 +63,7 @@ __global__ __launch_bounds__(256) void k_flow_blacklist(const EnrichTables t, co
                 wl[i] = (uint8_t)(FB_WL_NONCONFORMING | FB_WL_BLACKLISTED);
                 marked = true;
             }
+            if (kStamp && (nw != old || marked)) mod[i] = now;
         }
         cnt.add(0, occ);
         cnt.add(1, nw != 0ull);
@@ -90,14 +95,14 @@ __global__ __launch_bounds__(256) void k_flow_export_blacklisted(const FlowSlot*
                             // atomics on the same six words ("Blacklist pass")
 #endif
 hipError_t launch_flow_blacklist(const EnrichTables& t, const FlowSlot* table, unsigned long long cap,
-                                 unsigned long long* mask, uint8_t* wl, unsigned long long* stats, hipStream_t s) {
+                                 unsigned long long* mask, uint8_t* wl, unsigned long long* stats, hipStream_t s,
+                                 unsigned long long* mod, unsigned long long now) {
     if (!table || !mask || !stats || cap == 0ull) return hipErrorInvalidValue;
     if ((t.m4 && (!t.bl4_pos || !t.bl4_mask)) || (t.m6 && (!t.bl6_pos || !t.bl6_mask))) return hipErrorInvalidValue;
     const dim3 g(sweep_grid(cap, FB_BL_GRID));
-    if (wl)
-        hipLaunchKernelGGL(k_flow_blacklist<true>, g, dim3(256), 0, s, t, table, cap, mask, wl, stats);
-    else
-        hipLaunchKernelGGL(k_flow_blacklist<false>, g, dim3(256), 0, s, t, table, cap, mask, wl, stats);
+    const auto k = wl ? (mod ? k_flow_blacklist<true, true> : k_flow_blacklist<true, false>)
+                      : (mod ? k_flow_blacklist<false, true> : k_flow_blacklist<false, false>);
+    hipLaunchKernelGGL(k, g, dim3(256), 0, s, t, table, cap, mask, wl, stats, mod, now);
     return hipGetLastError();
 }
 

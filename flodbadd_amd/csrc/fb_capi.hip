@@ -57,7 +57,7 @@ struct UpdScratch {
 // Per-slot planes: arrays beside the table, one element per slot, that a flow's element follows through
 // every slot move.  Described once here; the functions below (plane_ensure .. plane_copy_out) are the
 // only code that allocates, moves, clears or frees one, so a new plane is one entry and its pass.
-enum PlaneId : uint32_t { kPlaneTime, kPlaneStatus, kPlaneWl, kPlaneBl, kPlaneAn, kPlanes };
+enum PlaneId : uint32_t { kPlaneTime, kPlaneStatus, kPlaneWl, kPlaneBl, kPlaneAn, kPlaneMod, kPlanes };
 struct PlaneDesc {
     size_t elem;       // bytes per slot
     const char* name;  // in error text
@@ -74,6 +74,8 @@ static const PlaneDesc kPlaneDesc[kPlanes] = {
     {1, "whitelist plane", true, false, launch_plane_remap<uint8_t>},                   // fb_whitelist.hip, FB_WL_*
     {8, "blacklist plane", true, false, launch_plane_remap<unsigned long long>},        // fb_blacklist.hip
     {sizeof(fb_an_rec), "anomaly plane", true, false, launch_plane_remap<fb_an_rec>},   // fb_anomaly.hip
+    // the passes' last_modified stamps (fb_set_pass_time; read by fb_view.hip): made by the first stamped pass
+    {8, "stamp plane", true, false, launch_plane_remap<unsigned long long>},
 };
 // the counter words of one synchronous pass over the table (pass_begin / pass_end)
 constexpr uint32_t kPassStatWords = std::max({kAgeStatWords, kWlCounters, kBlCounters, kAnCounters});
@@ -132,6 +134,8 @@ struct fb_ctx {
     template <typename T>
     T* plane(PlaneId p) const { return static_cast<T*>(d_plane[p]); }
     unsigned long long* d_pass_stats = nullptr;  // [kPassStatWords]
+    uint64_t pass_time = 0;         // fb_set_pass_time: what the passes stamp the flows they change with (0: no stamps)
+    bool view_direct = false;       // FB_DEBUG_VIEW_DIRECT: the view export's one-lane-per-record copy-out
     // timed contexts (FB_CFG_TIMED, fb_time.hip): the next update's frame times, the capture-time pass's
     // scratch (its last use: ev_tscratch)
     bool timed = false;
@@ -345,6 +349,16 @@ static int pass_end(fb_ctx* c, unsigned long long* h, uint32_t words, hipStream_
     HIP_TRY(hipMemcpyAsync(h, c->d_pass_stats, words * 8ull, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return FB_OK;
+}
+
+// The stamp plane a pass writes when a pass time is set (made on first use), else null: the pass then runs
+// its unstamped kernel instance.
+static int pass_stamps(fb_ctx* c, hipStream_t s, unsigned long long** mod) {
+    *mod = nullptr;
+    if (c->pass_time == 0) return FB_OK;
+    const int rc = plane_ensure(c, kPlaneMod, s);
+    if (!rc) *mod = c->plane<unsigned long long>(kPlaneMod);
+    return rc;
 }
 
 // The host form of a compacting export: a device buffer of `cap` records of `rec` bytes, the _dev export
@@ -792,6 +806,9 @@ int fb_debug_set(fb_ctx* c, uint32_t knob, uint64_t value) {
             c->dn_skew = value;
             if (value) fprintf(stderr, "flodbadd_gpu: FB_DEBUG_DENSE_OFFSET_SKEW %llu active on this context (fault injection)\n",
                                (unsigned long long)value);
+            return FB_OK;
+        case FB_DEBUG_VIEW_DIRECT:
+            c->view_direct = value != 0;
             return FB_OK;
         default:
             return set_err(FB_ERR_INVAL, "unknown debug knob %u", knob);
@@ -2149,6 +2166,8 @@ int fb_flow_whitelist(fb_ctx* c, uint32_t flags, fb_wl_stats* out, void* stream)
     int rc = pass_begin(c, kWlCounters, s);
     if (!rc) rc = upload_cfg(c, s);  // the LAN configuration as of now
     if (!rc) rc = plane_ensure(c, kPlaneWl, s);
+    unsigned long long* mod = nullptr;
+    if (!rc) rc = pass_stamps(c, s, &mod);
     if (rc) return rc;
     WlTables w;
     w.a4 = c->d_wl_a4;
@@ -2166,7 +2185,7 @@ int fb_flow_whitelist(fb_ctx* c, uint32_t flags, fb_wl_stats* out, void* stream)
     w.nr = c->wl_nr;
     w.n_records = c->wl_records;
     HIP_TRY(launch_flow_whitelist(w, enrich_tables(c), c->d_cfg, c->d_table, c->table_cap, c->plane<uint8_t>(kPlaneWl),
-                                  c->d_pass_stats, s));
+                                  c->d_pass_stats, s, mod, c->pass_time));
     unsigned long long h[kWlCounters] = {};
     rc = pass_end(c, h, kWlCounters, s);
     if (rc) return rc;
@@ -2215,9 +2234,11 @@ int fb_flow_blacklist(fb_ctx* c, uint32_t flags, fb_bl_stats* out, void* stream)
     if (!rc) rc = plane_ensure(c, kPlaneBl, s);
     // the fallback writes the whitelist plane, which no whitelist pass may have made yet
     if (!rc && mark) rc = plane_ensure(c, kPlaneWl, s);
+    unsigned long long* mod = nullptr;
+    if (!rc) rc = pass_stamps(c, s, &mod);
     if (rc) return rc;
     HIP_TRY(launch_flow_blacklist(enrich_tables(c), c->d_table, c->table_cap, c->plane<unsigned long long>(kPlaneBl),
-                                  mark ? c->plane<uint8_t>(kPlaneWl) : nullptr, c->d_pass_stats, s));
+                                  mark ? c->plane<uint8_t>(kPlaneWl) : nullptr, c->d_pass_stats, s, mod, c->pass_time));
     unsigned long long h[kBlCounters] = {};
     rc = pass_end(c, h, kBlCounters, s);
     if (rc) return rc;
@@ -2344,9 +2365,11 @@ int fb_flow_anomaly(fb_ctx* c, uint32_t flags, fb_an_stats* out, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     int rc = pass_begin(c, kAnCounters, s);
     if (!rc) rc = plane_ensure(c, kPlaneAn, s);
+    unsigned long long* mod = nullptr;
+    if (!rc) rc = pass_stamps(c, s, &mod);
     if (rc) return rc;
     HIP_TRY(launch_flow_anomaly(an_forest(c), c->d_table, c->plane<FlowTime>(kPlaneTime), c->table_cap,
-                                c->plane<fb_an_rec>(kPlaneAn), c->d_pass_stats, s));
+                                c->plane<fb_an_rec>(kPlaneAn), c->d_pass_stats, s, mod, c->pass_time));
     unsigned long long h[kAnCounters] = {};
     rc = pass_end(c, h, kAnCounters, s);
     if (rc) return rc;
@@ -2402,6 +2425,76 @@ int fb_if_score_dev(fb_ctx* c, const double* d_feat, uint64_t n, double* d_path_
     DeviceGuard g(c->device);
     HIP_TRY(launch_if_score(an_forest(c), d_feat, n, d_path_sum, (hipStream_t)stream));
     return FB_OK;
+}
+
+// ---- incremental queries: the pass clock, the stamp plane, the view export (fb_view.hip) ----------------
+int fb_set_pass_time(fb_ctx* c, uint64_t now_ns) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    c->pass_time = now_ns;
+    return FB_OK;
+}
+
+int fb_flow_modified_dev(fb_ctx* c, uint64_t* d_out, uint64_t cap, void* stream) {
+    return plane_copy_out(c, kPlaneMod, d_out, cap, stream);
+}
+
+static int view_query_check(const fb_ctx* c, const fb_view_query* q) {
+    if (!q) return set_err(FB_ERR_INVAL, "query is NULL");
+    if (q->set > FB_VIEW_ANOMALOUS) return set_err(FB_ERR_INVAL, "unknown set %u", q->set);
+    if (q->filter > FB_FILTER_ALL) return set_err(FB_ERR_INVAL, "unknown filter %u", q->filter);
+    if (q->flags & ~FB_VIEW_MODIFIED_SINCE) return set_err(FB_ERR_INVAL, "unknown flags %u", q->flags);
+    if (q->reserved) return set_err(FB_ERR_INVAL, "reserved field is %u", q->reserved);
+    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if ((q->flags & FB_VIEW_MODIFIED_SINCE) && !c->timed)
+        return set_err(FB_ERR_INVAL, "FB_VIEW_MODIFIED_SINCE needs FB_CFG_TIMED (last_modified has no packet clock)");
+    return FB_OK;
+}
+
+int fb_flow_export_view_dev(fb_ctx* c, const fb_view_query* q, fb_flow_view* d_out, uint64_t cap, uint64_t* d_n,
+                            void* stream) {
+    if (!c || !d_n || (cap && !d_out) || (reinterpret_cast<uintptr_t>(d_out) & 15u))
+        return set_err(FB_ERR_INVAL, "ctx and d_n are required, d_out (16-B aligned) unless cap is 0");
+    int rc = view_query_check(c, q);
+    if (rc) return rc;
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
+    rc = join_updates(c, s);
+    if (!rc && q->filter != FB_FILTER_ALL) rc = upload_cfg(c, s);  // the LAN configuration as of now
+    if (rc) return rc;
+    ViewArgs a;
+    a.table = c->d_table;
+    a.time = c->plane<FlowTime>(kPlaneTime);
+    a.status = c->plane<uint8_t>(kPlaneStatus);
+    a.wl = c->plane<uint8_t>(kPlaneWl);
+    a.bl = c->plane<unsigned long long>(kPlaneBl);
+    a.an = c->plane<fb_an_rec>(kPlaneAn);
+    a.mod = c->plane<unsigned long long>(kPlaneMod);
+    a.cfg = c->d_cfg;
+    a.cap = c->table_cap;
+    a.since = q->since_ns;
+    a.set = q->set;
+    a.filter = q->filter;
+    a.flags = q->flags;
+    HIP_TRY(launch_flow_view(a, d_out, cap, (unsigned long long*)d_n, !c->view_direct, s));
+    return FB_OK;
+}
+
+int fb_flow_export_view(fb_ctx* c, const fb_view_query* q, fb_flow_view* out, uint64_t cap, uint64_t* n, void* stream) {
+    if (!c || !n || (cap && !out)) return set_err(FB_ERR_INVAL, "bad arguments");
+    *n = 0;
+    int rc = view_query_check(c, q);
+    if (rc) return rc;
+    if (cap == 0) return FB_OK;
+    DeviceGuard g(c->device);
+    uint64_t total = 0;
+    rc = fb_flow_count(c, &total, stream);
+    if (rc) return rc;
+    const uint64_t m = std::min(total, cap);
+    if (m == 0) return FB_OK;
+    return export_to_host(c, out, m, sizeof(fb_flow_view), n, (hipStream_t)stream, "view export", [&](void* d_out) {
+        return fb_flow_export_view_dev(c, q, (fb_flow_view*)d_out, m, reinterpret_cast<uint64_t*>(c->d_n), stream);
+    });
 }
 
 // ---- multi-GPU merge (fb_merge.hip) ---------------------------------------------------------------

@@ -1382,14 +1382,6 @@ __global__ __launch_bounds__(kFlowSlots) void k_flow_grow(const FlowSlot* old, u
     remap[(size_t)p * kFlowSlots + i] = dst;
 }
 
-// is_local_session! (src/sessions.rs:660-666) of a slot's key under the current configuration.
-__device__ __forceinline__ bool slot_local(const DevConfig* cfg, const FlowSlot& t) {
-    const uint32_t fam = (t.key[9] >> 8) & 0xFFu;
-    if (fam == 2u) return lan_v4(t.key[0]) && lan_v4(t.key[4]);
-    const uint32_t s[4] = {t.key[0], t.key[1], t.key[2], t.key[3]}, d[4] = {t.key[4], t.key[5], t.key[6], t.key[7]};
-    return lan_v6(cfg, cfg, s) && lan_v6(cfg, cfg, d);
-}
-
 __global__ __launch_bounds__(256) void k_flow_export(const FlowSlot* T, unsigned long long cap,
                                                      fb_flow_rec* out, unsigned long long out_cap,
                                                      unsigned long long* d_n, uint32_t filter, const DevConfig* cfg,

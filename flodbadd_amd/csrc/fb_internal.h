@@ -345,6 +345,14 @@ __device__ __forceinline__ fb_flow_rec flow_rec_at(const FlowSlot* T, const Flow
     return r;
 }
 
+// is_local_session! (src/sessions.rs:660-666) of a slot's key under the current configuration (the exports' read-time filter).
+__device__ __forceinline__ bool slot_local(const DevConfig* cfg, const FlowSlot& t) {
+    const uint32_t fam = (t.key[9] >> 8) & 0xFFu;
+    if (fam == 2u) return lan_v4(t.key[0]) && lan_v4(t.key[4]);
+    const uint32_t s[4] = {t.key[0], t.key[1], t.key[2], t.key[3]}, d[4] = {t.key[4], t.key[5], t.key[6], t.key[7]};
+    return lan_v6(cfg, cfg, s) && lan_v6(cfg, cfg, d);
+}
+
 // The sweeps over the table (exports, enrichment, the whitelist / blacklist passes, the flow count)
 // run 256-thread workgroups that stride over the slots: the grid for `slots` slots, at most max_grid
 // workgroups and at least one.
@@ -800,8 +808,11 @@ __device__ __forceinline__ unsigned long long bl_lookup(const EnrichTables& t, c
 constexpr uint32_t kBlCounters = 6;
 constexpr uint32_t kStateLocalSrc = 1u << 20, kStateLocalDst = 1u << 21;  // hist_state: FB_SESSION_LOCAL_SRC / _DST
 // wl: the whitelist state plane with FB_BL_MARK_WHITELIST (the "Session is blacklisted" fallback), else null
+// mod / now (every pass launcher): the stamp plane and the pass time (fb_set_pass_time) written into the
+// flows the pass changes; mod null: the unstamped instance of the kernel, which holds no such store
 hipError_t launch_flow_blacklist(const EnrichTables& t, const FlowSlot* table, unsigned long long cap,
-                                 unsigned long long* mask, uint8_t* wl, unsigned long long* stats, hipStream_t s);
+                                 unsigned long long* mask, uint8_t* wl, unsigned long long* stats, hipStream_t s,
+                                 unsigned long long* mod = nullptr, unsigned long long now = 0ull);
 hipError_t launch_flow_export_blacklisted(const FlowSlot* table, const unsigned long long* mask, unsigned long long cap,
                                           fb_flow_rec* out, unsigned long long* out_masks, unsigned long long out_cap,
                                           unsigned long long* d_n, const FlowTime* plane, hipStream_t s);
@@ -823,7 +834,8 @@ struct AnForest {  // the installed model (device pointers)
 bool forest_valid(const fb_if_node* nodes, uint64_t n_nodes, const uint32_t* first, uint32_t n_trees);
 // plane: the time plane of a timed context (features 1 and 4), else null
 hipError_t launch_flow_anomaly(const AnForest& f, const FlowSlot* table, const FlowTime* plane, unsigned long long cap,
-                               fb_an_rec* recs, unsigned long long* stats, hipStream_t s);
+                               fb_an_rec* recs, unsigned long long* stats, hipStream_t s,
+                               unsigned long long* mod = nullptr, unsigned long long now = 0ull);
 hipError_t launch_if_score(const AnForest& f, const double* feat, unsigned long long n, double* path_sum, hipStream_t s);
 hipError_t launch_flow_features(const FlowSlot* table, const FlowTime* plane, const uint32_t* service_code,
                                 unsigned long long cap, double* feat, uint32_t* slot, unsigned long long out_cap,
@@ -879,10 +891,31 @@ struct WlIndex {  // host form
 // false: an endpoint with a bad family / prefix / protocol, or more than FB_WL_MAX_EXACT / _OTHER
 bool build_whitelist_index(const fb_wl_endpoint* eps, uint64_t n, WlIndex& ix);
 hipError_t launch_flow_whitelist(const WlTables& w, const EnrichTables& t, const DevConfig* cfg, const FlowSlot* table,
-                                 unsigned long long cap, uint8_t* state, unsigned long long* stats, hipStream_t s);
+                                 unsigned long long cap, uint8_t* state, unsigned long long* stats, hipStream_t s,
+                                 unsigned long long* mod = nullptr, unsigned long long now = 0ull);
 hipError_t launch_flow_export_whitelist(const FlowSlot* table, const uint8_t* state, unsigned long long cap,
                                         uint32_t state_mask, fb_flow_rec* out, unsigned long long out_cap,
                                         unsigned long long* d_n, const FlowTime* plane, hipStream_t s);
+
+// View export (fb_view.hip, fb_flow_export_view_dev): the table and every per-slot plane (null: not made,
+// reads as zeros), the query, and the copy-out shape (staged: through LDS, whole 16-B columns; else one
+// lane per record -- kept for the measurement, fb_debug_set FB_DEBUG_VIEW_DIRECT).
+struct ViewArgs {
+    const FlowSlot* table;
+    const FlowTime* time;
+    const uint8_t* status;
+    const uint8_t* wl;
+    const unsigned long long* bl;
+    const fb_an_rec* an;
+    const unsigned long long* mod;
+    const DevConfig* cfg;
+    unsigned long long cap;
+    unsigned long long since;
+    uint32_t set, filter, flags;
+};
+static_assert(sizeof(fb_flow_view) == 256 && sizeof(fb_view_query) == 24, "view ABI");
+hipError_t launch_flow_view(const ViewArgs& a, fb_flow_view* out, unsigned long long out_cap, unsigned long long* d_n,
+                            bool staged, hipStream_t s);
 
 hipError_t launch_dns_parse(const uint8_t* frames, unsigned long long frames_bytes, const fb_dns_out* dns, uint32_t n,
                             const fb_batch_stats* stats, fb_dns_msg* msgs, char* names, fb_ip* addrs, hipStream_t s);

@@ -141,11 +141,14 @@ __device__ __forceinline__ uint32_t wl_eval(const WlTables& W, const EnrichTable
 // kStaged: the group table and the rules fit kWlLdsGroups / kWlLdsRules and every workgroup copies them
 // into LDS once (coalesced), so the per-lane group searches and rule scans -- divergent addresses --
 // stay on the CU.  Otherwise they are read from global memory (L2).
+// kStamp (a pass time is set, fb_set_pass_time): the flows whose byte changed get `now` in the stamp plane
+// (src/whitelists.rs:975-982); the unstamped instances hold no such store.
 // Counters: PassCounters (fb_internal.h).
-template <bool kStaged>
+template <bool kStaged, bool kStamp>
 __global__ __launch_bounds__(256) void k_flow_whitelist(const WlTables W, const EnrichTables E, const DevConfig* cfg,
                                                         const FlowSlot* T, unsigned long long cap, uint8_t* state,
-                                                        unsigned long long* stats) {
+                                                        unsigned long long* stats, unsigned long long* mod,
+                                                        unsigned long long now) {
     __shared__ uint32_t s_gkey[kStaged ? kWlLdsGroups : 1u];
     __shared__ uint32_t s_gbeg[kStaged ? kWlLdsGroups + 1u : 1u];
     __shared__ uint4 s_rules[kStaged ? kWlLdsRules * 3u : 1u];
@@ -169,6 +172,7 @@ __global__ __launch_bounds__(256) void k_flow_whitelist(const WlTables W, const 
             else
                 nb = wl_eval(W, E, cfg, W.gkey, W.gbeg, W.rules, T[i].key);
             if (nb != old) state[i] = (uint8_t)nb;
+            if (kStamp && nb != old) mod[i] = now;
         }
         cnt.add(0, occ);
         cnt.add(1, (nb & FB_WL_CONFORMING) != 0u);
@@ -198,16 +202,17 @@ __global__ __launch_bounds__(256) void k_flow_export_whitelist(const FlowSlot* T
 #define FB_WL_GRID 2048ull  // the staging copy (<= 28 KiB per workgroup) is paid once per workgroup
 #endif
 hipError_t launch_flow_whitelist(const WlTables& w, const EnrichTables& t, const DevConfig* cfg, const FlowSlot* table,
-                                 unsigned long long cap, uint8_t* state, unsigned long long* stats, hipStream_t s) {
+                                 unsigned long long cap, uint8_t* state, unsigned long long* stats, hipStream_t s,
+                                 unsigned long long* mod, unsigned long long now) {
     if (!table || !state || !stats || !cfg || cap == 0ull) return hipErrorInvalidValue;
     if ((w.ng && (!w.gkey || !w.gbeg)) || (w.nr && !w.rules) || (w.n4 && (!w.a4 || !w.k4)) ||
         (w.n6 && (!w.a6 || !w.k6)) || (w.n_records && (!w.rec_owner || !w.rec_country)))
         return hipErrorInvalidValue;
     const dim3 g(sweep_grid(cap, FB_WL_GRID));
-    if (w.ng <= kWlLdsGroups && w.nr <= kWlLdsRules && w.ng)
-        hipLaunchKernelGGL(k_flow_whitelist<true>, g, dim3(256), 0, s, w, t, cfg, table, cap, state, stats);
-    else
-        hipLaunchKernelGGL(k_flow_whitelist<false>, g, dim3(256), 0, s, w, t, cfg, table, cap, state, stats);
+    const bool staged = w.ng <= kWlLdsGroups && w.nr <= kWlLdsRules && w.ng;
+    const auto k = staged ? (mod ? k_flow_whitelist<true, true> : k_flow_whitelist<true, false>)
+                          : (mod ? k_flow_whitelist<false, true> : k_flow_whitelist<false, false>);
+    hipLaunchKernelGGL(k, g, dim3(256), 0, s, w, t, cfg, table, cap, state, stats, mod, now);
     return hipGetLastError();
 }
 

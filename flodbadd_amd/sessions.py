@@ -16,7 +16,7 @@ from typing import List, Optional
 
 from ._native import (CONN_STATES, FB_FILTER_ALL, FB_FILTER_GLOBAL_ONLY, FB_FILTER_LOCAL_ONLY, FB_SEEN_NONE,
                       FB_WL_BLACKLISTED, FB_WL_CONFORMING, FB_WL_NONCONFORMING,
-                      FLOW_REC_DTYPE, SESSION_DST_SERVICE, SESSION_LOCAL_DST, SESSION_LOCAL_SRC, SESSION_SELF_DST,
+                      FLOW_REC_DTYPE, FLOW_VIEW_DTYPE, SESSION_DST_SERVICE, SESSION_LOCAL_DST, SESSION_LOCAL_SRC, SESSION_SELF_DST,
                       SESSION_SELF_SRC, STATUS_ACTIVATED, STATUS_ACTIVE, STATUS_ADDED, STATUS_DEACTIVATED,
                       META_DST_SERVICE, META_HAS_FLAGS, META_LOCAL_DST, META_LOCAL_SRC, META_ORIGINATOR,
                       META_SELF_DST, META_SELF_SRC, META_SWAP, PARSED_DTYPE, PKT_OUT_DTYPE)
@@ -199,7 +199,10 @@ class SessionInfo:
     NonConforming / "Session is blacklisted" where the blacklist pass found the session Unknown
     (src/capture.rs:1858-1871); criticality holds the sorted "blacklist:<name>" tags of the last
     blacklist pass (src/blacklists.rs:612-631; "" before it) and, once FlodbaddGpuCapture.analyze_sessions
-    has run, the merged "anomaly:<level>[/<diagnostic>]" tag (src/analyzer.rs:630-653)."""
+    has run, the merged "anomaly:<level>[/<diagnostic>]" tag (src/analyzer.rs:630-653).  last_modified_ns
+    (src/sessions.rs: last_modified, on the capture clock): the later of the session's last packet (timed
+    captures) and the last pass that changed it under a pass time (FlodbaddGpuCapture.set_pass_time); 0 when
+    neither exists."""
     session: Session
     stats: SessionStats = field(default_factory=SessionStats)
     is_local_src: bool = False
@@ -211,6 +214,7 @@ class SessionInfo:
     is_whitelisted: WhitelistState = WhitelistState.Unknown
     whitelist_reason: Optional[str] = None
     criticality: str = ""
+    last_modified_ns: int = 0
 
 
 _SERVICE_NAMES = None
@@ -315,7 +319,7 @@ def histories_from_records(recs):
     return {k: (h, state.get(k)) for k, h in hist.items()}
 
 
-def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=None, blacklist=None):
+def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=None, blacklist=None, modified=None):
     """fb_flow_rec records -> SessionInfo list sorted by the derived Ord of Session.  `histories`
     ({table slot: str}, FlodbaddGpuCapture.histories) supplies the history strings; the locality
     flags and dst_service come from fb_flow_rec.session_flags (stored at insert, src/packets.rs:
@@ -327,7 +331,9 @@ def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=
     `whitelist`: the whitelist state byte of every table slot (fb_flow_whitelist_dev), decoded into
     SessionInfo.is_whitelisted; without it every session is Unknown.  A byte with FB_WL_BLACKLISTED
     carries the reason "Session is blacklisted".  `blacklist`: (the mask word of every table slot,
-    fb_flow_blacklist_dev; the list names), decoded into SessionInfo.criticality."""
+    fb_flow_blacklist_dev; the list names), decoded into SessionInfo.criticality.  `modified`: the stamp
+    of every table slot (fb_flow_modified_dev); SessionInfo.last_modified_ns is the later of it and the
+    flow's last_activity_ns.  The per-slot arguments may be arrays indexed by slot or {slot: value}."""
     from .enrich import criticality_of  # (enrich imports this module)
     if flows.dtype != FLOW_REC_DTYPE:
         raise TypeError("expected fb_flow_rec records (FLOW_REC_DTYPE), got %s" % flows.dtype)
@@ -369,9 +375,29 @@ def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=
                 info.whitelist_reason = "Session is blacklisted"
         if blacklist is not None:
             info.criticality = criticality_of(blacklist[0][int(r["slot"])], blacklist[1])
+        info.last_modified_ns = max(st.last_activity_ns or 0, int(modified[int(r["slot"])]) if modified is not None else 0)
         out.append(info)
     out.sort(key=lambda i: i.session.sort_key())
     return out
+
+
+def views_to_sessions(views, histories=None, bl_names=None, timed=True, status=True, whitelist=True, blacklist=True):
+    """fb_flow_view records (fb_flow_export_view) -> the SessionInfo list flows_to_sessions builds from the
+    separate exports: each view carries its flow's record, time record and per-slot plane elements, so no
+    other export is needed.  timed: the capture is timed (else the time records are zero and left out);
+    status / whitelist / blacklist: decode that plane's element (a getter that does not hand
+    flows_to_sessions a plane passes False here); bl_names: the list names of the blacklist masks."""
+    views = np.ascontiguousarray(views)
+    if views.dtype != FLOW_VIEW_DTYPE:
+        raise TypeError("expected fb_flow_view records (FLOW_VIEW_DTYPE), got %s" % views.dtype)
+    flows = np.ascontiguousarray(views["rec"])
+    slots = flows["slot"].tolist()
+    by_slot = lambda f: dict(zip(slots, views[f].tolist()))  # noqa: E731
+    return flows_to_sessions(flows, histories, times=np.ascontiguousarray(views["time"]) if timed else None,
+                             status=by_slot("status") if (status and timed) else None,
+                             whitelist=by_slot("wl_state") if whitelist else None,
+                             blacklist=(by_slot("bl_mask"), bl_names or []) if blacklist else None,
+                             modified=by_slot("stamp_ns"))
 
 
 def filter_sessions(sessions: List[SessionInfo], flt: SessionFilter, lan_v6=()) -> List[SessionInfo]:
@@ -386,7 +412,8 @@ def filter_sessions(sessions: List[SessionInfo], flt: SessionFilter, lan_v6=()) 
 
 __all__ = ["Protocol", "SessionFilter", "Session", "SessionPacketData", "SessionStats", "SessionStatus", "SessionInfo",
            "WhitelistState",
-           "ip_to_words", "words_to_ip", "service_name", "records_to_packets", "flows_to_sessions", "filter_sessions",
+           "ip_to_words", "words_to_ip", "service_name", "records_to_packets", "flows_to_sessions", "views_to_sessions",
+           "filter_sessions",
            "packets_to_parsed", "determine_conn_state", "histories_from_records", "is_lan_ip", "is_local_session",
            "META_HAS_FLAGS", "META_SWAP", "META_ORIGINATOR", "META_LOCAL_SRC", "META_LOCAL_DST",
            "META_SELF_SRC", "META_SELF_DST", "META_DST_SERVICE"]

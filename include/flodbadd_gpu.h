@@ -335,8 +335,10 @@ int fb_set_frame_times(fb_ctx* ctx, const uint64_t* d_ts);
  * next call): FB_DEBUG_DENSE_STEAL_POLLS -- the polls a dense look-back waits for a predecessor's
  * word before computing that tile's sums itself (default 4096; 0 forces the fallback path);
  * FB_DEBUG_DENSE_OFFSET_SKEW -- fault injection, added (mod 2^32) to the session half of every
- * dense tile offset, as a corrupted look-back word would be (< 2^32; logged on stderr when set). */
-enum fb_debug_knob { FB_DEBUG_DENSE_STEAL_POLLS = 1, FB_DEBUG_DENSE_OFFSET_SKEW = 2 };
+ * dense tile offset, as a corrupted look-back word would be (< 2^32; logged on stderr when set);
+ * FB_DEBUG_VIEW_DIRECT -- non-zero: fb_flow_export_view_dev stores one record per lane instead of staging
+ * a step's records in LDS (same result; the shape the staged copy-out is measured against). */
+enum fb_debug_knob { FB_DEBUG_DENSE_STEAL_POLLS = 1, FB_DEBUG_DENSE_OFFSET_SKEW = 2, FB_DEBUG_VIEW_DIRECT = 3 };
 int fb_debug_set(fb_ctx* ctx, uint32_t knob, uint64_t value);
 /* Whether the fused parse + upsert calls (fb_process_seg_dev, fb_process_seg_async_dev) store the
  * SESSION records in d_out (default 1).  With 0 the session table is their only per-packet output,
@@ -980,6 +982,75 @@ int fb_flow_features_dev(fb_ctx* ctx, double* d_feat, uint32_t* d_slot, uint64_t
  * forest and the pass's own device function.  FB_ERR_INVAL without a model.  DEVICE pointers,
  * asynchronous. */
 int fb_if_score_dev(fb_ctx* ctx, const double* d_feat, uint64_t n, double* d_path_sum, void* stream);
+
+/* ---- incremental queries: last_modified and the view export (src/capture.rs:411-426, 1578-1760) -------
+ * The reference's getters take an `incremental` flag and then return only the sessions whose
+ * last_modified is newer than the getter's last full fetch.  It sets last_modified = now at a packet
+ * (src/packets.rs:342, 524), at a blacklist change (src/blacklists.rs:655-689, src/capture.rs:1867-1868)
+ * and at a whitelist change (src/whitelists.rs:975-982), and when the analyzer re-tags a session
+ * (src/analyzer.rs:655-676); the status update leaves it alone (src/capture.rs:1497-1551).
+ * Here a flow's last_modified is max(last_activity_ns, stamp): the packet part is the time plane's
+ * last_activity_ns (timed contexts; nothing is stored on the packet path), the stamp is one uint64 per
+ * table slot that the passes write -- the pass time of fb_set_pass_time, on the clock of the frame
+ * times -- into exactly the flows they changed:
+ *   fb_flow_blacklist  the flows counted as `changed`, and those FB_BL_MARK_WHITELIST marks (`wl_marked`);
+ *   fb_flow_whitelist  the flows counted as `changed`;
+ *   fb_flow_anomaly    the flows whose level or diagnostic codes differ from before the call (a new
+ *                      path_sum alone does not show in the criticality string and does not stamp);
+ *   fb_flow_age        never.
+ * A zero stamp: no pass has modified the flow.  The stamps follow their flows through a growth and a
+ * purge (a purged flow that returns starts at 0), and fb_flow_clear zeroes them.
+ *
+ * fb_set_pass_time: the stamp later passes write.  0 -- the state of a new context -- means "do not
+ * stamp": no stamp plane is allocated and every pass runs the code it ran before there were stamps. */
+int fb_set_pass_time(fb_ctx* ctx, uint64_t now_ns);
+/* The raw stamp of every table slot (min(cap, capacity) words, slot order; zeros while no stamped pass
+ * has run) into DEVICE memory.  Asynchronous. */
+int fb_flow_modified_dev(fb_ctx* ctx, uint64_t* d_out, uint64_t cap, void* stream);
+
+/* One record per selected flow: everything the separate exports and per-slot planes hold about it,
+ * joined on the device.  A plane no pass has made yet contributes zeros; on an untimed context `time`
+ * is zero except its slot. */
+typedef struct fb_flow_view {
+    fb_flow_rec rec;           /*   0: as fb_flow_export_sessions writes it                              */
+    fb_flow_time time;         /* 136: as fb_flow_export_times writes it (slot set)                      */
+    uint64_t last_modified_ns; /* 200: max(time.last_activity_ns, stamp_ns); untimed: stamp_ns           */
+    uint64_t stamp_ns;         /* 208: the stamp plane's element (fb_flow_modified_dev)                  */
+    uint64_t bl_mask;          /* 216: fb_flow_blacklist_dev's word                                      */
+    fb_an_rec an;              /* 224: fb_flow_anomaly_dev's record                                      */
+    uint8_t status;            /* 240: fb_flow_status_dev's byte                                         */
+    uint8_t wl_state;          /* 241: fb_flow_whitelist_dev's byte                                      */
+    uint8_t reserved[14];      /* 242: zeros                                                             */
+} fb_flow_view;                /* 256 bytes; an output array starts at a 16-byte boundary                */
+enum fb_view_set {
+    FB_VIEW_ALL = 0,           /* every flow                                                             */
+    FB_VIEW_CURRENT = 1,       /* status byte 0, or FB_STATUS_CURRENT set (get_current_sessions)         */
+    FB_VIEW_BLACKLISTED = 2,   /* mask != 0                                                              */
+    FB_VIEW_WL_EXCEPTIONS = 3, /* FB_WL_NONCONFORMING set                                                */
+    FB_VIEW_ANOMALOUS = 4      /* level >= FB_AN_SUSPICIOUS                                              */
+};
+#define FB_VIEW_MODIFIED_SINCE 1u /* fb_view_query.flags: and last_modified_ns > since_ns (strict, as the
+                                     reference skips last_modified <= last_fetch_ts)                     */
+typedef struct fb_view_query {
+    uint64_t since_ns; /*  0: read with FB_VIEW_MODIFIED_SINCE                                           */
+    uint32_t set;      /*  8: fb_view_set; a set whose plane no pass has made selects nothing -- except
+                              FB_VIEW_CURRENT, which then selects every flow (a zero byte is current)    */
+    uint32_t filter;   /* 12: fb_filter, evaluated now against the current LAN configuration, as
+                              fb_flow_export_sessions does                                               */
+    uint32_t flags;    /* 16: FB_VIEW_MODIFIED_SINCE or 0                                                */
+    uint32_t reserved; /* 20: 0                                                                          */
+} fb_view_query;       /* 24 bytes */
+/* The fb_flow_view of the flows the query selects; order as fb_flow_export_blacklisted_dev.  *d_n (device
+ * u64) = the matching flows (only the first `cap` are written; cap may be 0).  One sweep: per slot the
+ * predicate reads the table line, 8 B of the time record, the stamp and one plane element; the selected
+ * records of a step are staged in LDS and written out by the whole workgroup in 16-B columns.  DEVICE
+ * pointers (d_out 16-B aligned), asynchronous; the host variant is synchronous, *n = records written.
+ * FB_ERR_INVAL for an unknown set, filter or flag bit, a non-zero `reserved`, FB_VIEW_MODIFIED_SINCE on a
+ * context without FB_CFG_TIMED (no packet clock), or a context without a flow table. */
+int fb_flow_export_view_dev(fb_ctx* ctx, const fb_view_query* query, fb_flow_view* d_out, uint64_t cap, uint64_t* d_n,
+                            void* stream);
+int fb_flow_export_view(fb_ctx* ctx, const fb_view_query* query, fb_flow_view* out, uint64_t cap, uint64_t* n,
+                        void* stream);
 
 /* ---- multi-GPU session table (BASELINE configs[4]) ------------------------------
  * The reference runs one capture task per interface into ONE shared DashMap (src/capture.rs:946-1016,
