@@ -330,6 +330,16 @@ __global__ __launch_bounds__(64) void k_dns_parse(const uint8_t* frames, unsigne
 #pragma unroll
         for (uint32_t u = 0; u < 32u; ++u) s_msg[j0 + u][lane] = v[u];
     }
+    // the range check is per dword: when frames_bytes is no multiple of 4 the buffer's last,
+    // partial dword reads as 0 above.  A lane whose stage covers it refills it from byte loads
+    // (each range-checked, so still nothing past frames_bytes), after the wave's writes to its row.
+    const uint32_t tail = fb & ~3u;
+    if ((fb & 3u) != 0u && len != 0u && tail >= base && tail - base < kStage) {
+        const uint32_t w = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rf, tail, 0, 0) |
+                           (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rf, tail + 1u, 0, 0) << 8 |
+                           (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rf, tail + 2u, 0, 0) << 16;
+        s_msg[lane][(tail - base) >> 2] = w;
+    }
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (!live) return;

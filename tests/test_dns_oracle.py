@@ -77,6 +77,32 @@ def test_many_answers_truncate_addr_list():
     assert st == "ok" and len(ad) == N.FB_DNS_MAX_ADDRS and int(r["flags"]) & N.DNS_ADDRS_TRUNCATED
 
 
+def test_long_name_truncates_at_255_bytes():
+    """The stored name is the first 255 bytes of the Display; the flag says that more followed, and
+    the reverse-lookup flag looks at the whole name, not at what is stored."""
+    def q(n, tail=""):
+        labs, left = [], n - len(tail) + 1  # each label and the dot behind it; the last dot is not written
+        while left > 0:
+            k = min(63, left - 1)
+            k -= left - (k + 1) == 1  # never leave room for a dot alone
+            labs.append("abcdefgh"[len(labs)] * k)
+            left -= k + 1
+        name = ".".join(labs) + tail
+        assert len(name) == n
+        return G.query(5, name, edns=False)
+
+    for n, cut in ((254, False), (255, False), (256, True), (300, True)):
+        st, r, nm, _ = parse(q(n))
+        assert st == "ok" and len(nm) == min(n, 255) == int(r["name_len"])
+        assert bool(int(r["flags"]) & N.DNS_NAME_TRUNCATED) == cut and not int(r["flags"]) & N.DNS_REVERSE
+        assert nm.startswith(b"a" * 63 + b".b") and b".." not in nm
+    st, r, nm, _ = parse(q(255, ".in-addr.arpa"))      # fits: flagged as reverse, not truncated
+    assert st == "ok" and int(r["flags"]) & N.DNS_REVERSE and not int(r["flags"]) & N.DNS_NAME_TRUNCATED
+    st, r, nm, _ = parse(q(270, ".in-addr.arpa"))      # the suffix lies past byte 255
+    assert st == "ok" and len(nm) == 255 and b"arpa" not in nm
+    assert int(r["flags"]) & N.DNS_REVERSE and int(r["flags"]) & N.DNS_NAME_TRUNCATED
+
+
 def test_resolver_bookkeeping():
     msgs = [G.query(10, "a.example"), G.query(11, "1.0.0.10.in-addr.arpa", qtype=12),
             G.response(10, "a.example", [("A", "1.1.1.1"), ("AAAA", "2001:db8::1")]),
