@@ -142,6 +142,22 @@ DNS_STATUS = ["ok", "header_too_short", "unexpected_eof", "bad_pointer", "unknow
 ENRICH_LOCAL_SRC, ENRICH_LOCAL_DST, ENRICH_SELF_SRC, ENRICH_SELF_DST = 1, 2, 4, 8
 LAN_V6_DTYPE = np.dtype([("net", "<u4", (4,)), ("prefix", "<u4"), ("reserved", "<u4", (3,))])
 FB_IP_DTYPE = np.dtype([("addr", "<u4", (4,)), ("family", "<u4"), ("reserved", "<u4", (3,))])
+# the DNS tracker (fb_dns_track_*: DnsPacketProcessor, src/dns.rs:16-121) and the domain pass
+# (fb_flow_domains: populate_domain_names, src/capture.rs:1307-1411)
+DNS_TRACK_CONFIG_DTYPE = np.dtype([("name_capacity", "<u8"), ("addr_capacity", "<u8"), ("hash_mask", "<u8"),
+                                   ("flags", "<u4"), ("reserved", "<u4")])
+DNS_TRACK_STATS_FIELDS = ["messages", "queries", "responses", "matched", "resolutions", "names_new", "addrs_new",
+                          "rounds"]
+DNS_TRACK_STATS_DTYPE = np.dtype([(f, "<u8") for f in DNS_TRACK_STATS_FIELDS])
+DNS_TRACK_INFO_FIELDS = ["names", "addrs", "name_capacity", "addr_capacity", "pending", "messages", "writes"]
+DNS_TRACK_INFO_DTYPE = np.dtype([(f, "<u8") for f in DNS_TRACK_INFO_FIELDS] + [("reserved", "<u8")])
+DNS_RESOLUTION_DTYPE = np.dtype([("ip", FB_IP_DTYPE), ("name_id", "<u4"), ("reserved", "<u4"), ("order", "<u8")])
+FLOW_DOMAIN_DTYPE = np.dtype([("src_name_id", "<u4"), ("dst_name_id", "<u4")])
+DOM_STATS_FIELDS = ["flows", "current", "src_set", "dst_set", "changed", "with_domain"]
+DOM_STATS_DTYPE = np.dtype([(f, "<u8") for f in DOM_STATS_FIELDS] + [("reserved", "<u8", (2,))])
+assert (DNS_TRACK_CONFIG_DTYPE.itemsize, DNS_TRACK_STATS_DTYPE.itemsize, DNS_TRACK_INFO_DTYPE.itemsize,
+        DNS_RESOLUTION_DTYPE.itemsize, FLOW_DOMAIN_DTYPE.itemsize, DOM_STATS_DTYPE.itemsize) == (32, 64, 64, 48, 8, 64)
+FB_DNS_IDS, FB_DNS_EXPIRY_NS, FB_DNS_MAX_NAMES, FB_DNS_NO_TIME = 65536, 30 * 10**9, (1 << 24) - 1, (1 << 64) - 1
 
 FB_SEG_FRAMES = 64
 SEG_BYTES = FB_SEG_FRAMES * 56
@@ -331,6 +347,17 @@ GPU_SYMBOLS = [
     ("fb_flow_modified_dev", _I, [_P, _P, _U64, _P]),
     ("fb_flow_export_view_dev", _I, [_P, _P, _P, _U64, _P, _P]),
     ("fb_flow_export_view", _I, [_P, _P, _P, _U64, _PU64, _P]),
+    ("fb_dns_track_enable", _I, [_P, _P]),
+    ("fb_dns_track_clear", _I, [_P]),
+    ("fb_dns_track_dev", _I, [_P, _P, _P, _P, _U32, _P, _P, _P, _P, _P]),
+    ("fb_dns_expire", _I, [_P, _U64, _PU64]),
+    ("fb_dns_track_info_get", _I, [_P, _P]),
+    ("fb_dns_export_resolutions_dev", _I, [_P, _P, _U64, _P, _P]),
+    ("fb_dns_export_pending_dev", _I, [_P, _P, _P, _P]),
+    ("fb_dns_names_dev", _I, [_P, _P, _U64, _P, _P, _P]),
+    ("fb_dns_lookup_dev", _I, [_P, _P, _U64, _P, _P]),
+    ("fb_flow_domains", _I, [_P, _U32, _P, _P]),
+    ("fb_flow_domains_dev", _I, [_P, _P, _U64, _P]),
 ]
 
 _gpu = None

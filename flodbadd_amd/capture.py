@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _native as N
 from .sessions import (Session, SessionFilter, WhitelistState, flows_to_sessions, ip_to_words, is_lan_ip,
-                       views_to_sessions)
+                       views_to_sessions, words_to_ip)
 from .enrich import Blacklists
 from .analyzer import SessionAnalyzer, anomaly_tag_of, default_service_codes, merge_criticality, path_cut
 from .whitelists import Whitelists, is_session_in_whitelist, no_match_reason
@@ -56,10 +56,15 @@ def stats_dict(arr):
 class FlodbaddGpuCapture:
     def __init__(self, device=0, session_filter=SessionFilter.GlobalOnly, flow_capacity=1 << 20,
                  service_bitmap=None, lan_v6=(), own_ips=(), max_batch_packets=1 << 20, track_history=False,
-                 grow=True, timed=False):
+                 grow=True, timed=False, track_dns=False, dns_name_capacity=0, dns_addr_capacity=0, dns_hash_mask=0):
         """timed: capture-time session state (FB_CFG_TIMED): every batch then comes with its frames'
         capture timestamps (`ts`, ns) and the sessions carry start / last / end times and the
-        segment state with the reference's 5-s timeout (src/packets.rs:137-200)."""
+        segment state with the reference's 5-s timeout (src/packets.rs:137-200).
+        track_dns: the context keeps DnsPacketProcessor's state (fb_dns_track_enable): process_frames then
+        parses and tracks its batch's DNS records on the device, update_sessions runs the domain pass, and the
+        sessions carry src_domain / dst_domain.  dns_name_capacity / dns_addr_capacity: names and addresses
+        before the first growth (0: the library's defaults); dns_hash_mask: fb_dns_track_config.hash_mask,
+        a testing knob."""
         lib = N.gpu_lib()
         self._keep = []
         cfg = N.FbConfig()
@@ -120,6 +125,17 @@ class FlodbaddGpuCapture:
         # reference's epoch), and whether a pass time was ever set (the stamp plane may then hold stamps)
         self._fetch_ts = dict.fromkeys(("sessions", "current", "blacklisted", "exceptions"), 0)
         self._stamped = False
+        # DNS tracker (src/dns.rs:16-121): names are immutable per id, so the strings are fetched once
+        # ({id: str}); the resolutions are exported again only when the tracker's `writes` has moved
+        self.track_dns = bool(track_dns)
+        self._dns_names = {}
+        self._dns_res = (None, {})  # (writes, {ip: name id})
+        self._dom_ran = False
+        if self.track_dns:
+            tc = np.zeros(1, dtype=N.DNS_TRACK_CONFIG_DTYPE)
+            tc[0]["name_capacity"], tc[0]["addr_capacity"] = int(dns_name_capacity), int(dns_addr_capacity)
+            tc[0]["hash_mask"] = int(dns_hash_mask)
+            N.check(lib.fb_dns_track_enable(self.ctx, N.ptr(tc)))
 
     # ---- configuration -------------------------------------------------------------------
     def set_filter(self, flt):
@@ -225,7 +241,174 @@ class FlodbaddGpuCapture:
             code = N.FB_ERR_TABLE_FULL if e & 4 else N.FB_ERR_INTERNAL
             raise N.FbError(code, "device error word %d" % e)
         self._pull_history(n)
+        if self.track_dns and sd["n_dns"]:  # device to device: neither the names nor the answers come down
+            self._track_dns_dev(d_fr, frames.nbytes, d_dns, sd["n_dns"], d_ts)
         return BatchResult(out, dns, cls, sd)
+
+    # ---- DNS tracker (src/dns.rs:16-121; fb_dns_track_dev) ------------------------------------------
+    def _need_dns(self):
+        if not self.track_dns:
+            raise ValueError("this capture does not track DNS (track_dns=True)")
+
+    def _track_dns_dev(self, d_frames, frames_bytes, d_dns, n, d_ts=None, want_taken=False):
+        """fb_dns_parse_dev + fb_dns_track_dev over n DNS side records in device memory."""
+        lib = N.gpu_lib()
+        d_msg = N.DeviceBuffer(n * N.DNS_MSG_DTYPE.itemsize)
+        d_names = N.DeviceBuffer(n * N.FB_DNS_MAX_NAME)
+        d_addrs = N.DeviceBuffer(n * N.FB_DNS_MAX_ADDRS * N.FB_IP_DTYPE.itemsize)
+        N.check(lib.fb_dns_parse_dev(self.ctx, d_frames.ptr, frames_bytes, d_dns.ptr, n, None, d_msg.ptr, d_names.ptr,
+                                     d_addrs.ptr, None))
+        return self.track_dns_parsed_dev(d_msg, d_names, d_addrs, n, d_ts=d_ts, want_taken=want_taken)
+
+    def track_dns_parsed_dev(self, d_msg, d_names, d_addrs, n, d_stats=None, d_ts=None, want_taken=False):
+        """fb_dns_track_dev over DeviceBuffers as fb_dns_parse_dev wrote them: the call's counters
+        (fb_dns_track_stats) and, with want_taken, the name id each response took."""
+        self._need_dns()
+        st = np.zeros(1, dtype=N.DNS_TRACK_STATS_DTYPE)
+        d_taken = N.DeviceBuffer(max(n, 1) * 4) if want_taken else None
+        N.check(N.gpu_lib().fb_dns_track_dev(self.ctx, d_msg.ptr, d_names.ptr, d_addrs.ptr, n,
+                                             d_stats.ptr if d_stats is not None else None,
+                                             d_ts.ptr if d_ts is not None else None,
+                                             d_taken.ptr if want_taken else None, N.ptr(st), None))
+        out = {k: int(st[0][k]) for k in N.DNS_TRACK_STATS_FIELDS}
+        if want_taken:
+            out["taken"] = d_taken.download(np.zeros(max(n, 1), dtype=np.uint32))[:n]
+        return out
+
+    def track_dns_records(self, frames, dns_records, ts=None):
+        """What process_frames does with its batch's DNS side records, for the callers of parse_classify:
+        the records are parsed and tracked on the device.  ts: the frames' capture timestamps (ns), which
+        the 30-s expiry of the pending queries runs on; without them the queries never expire."""
+        self._need_dns()
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        dns_records = np.ascontiguousarray(dns_records, dtype=N.DNS_OUT_DTYPE)
+        n = len(dns_records)
+        if n == 0:
+            return dict.fromkeys(N.DNS_TRACK_STATS_FIELDS, 0)
+        d_fr = N.DeviceBuffer(max(frames.nbytes, 1))
+        if frames.nbytes:
+            d_fr.upload(frames)
+        d_dns = N.DeviceBuffer(dns_records.nbytes).upload(dns_records)
+        d_ts = None
+        if ts is not None:
+            ts = np.ascontiguousarray(ts, dtype=np.uint64)
+            if ts.size <= int(dns_records["pkt_index"].max()):
+                raise ValueError("%d timestamps, frame %d has a DNS record" % (ts.size, int(dns_records["pkt_index"].max())))
+            d_ts = N.DeviceBuffer(ts.nbytes).upload(ts)
+        return self._track_dns_dev(d_fr, frames.nbytes, d_dns, n, d_ts)
+
+    def dns_track_info(self):
+        """fb_dns_track_info_get: names, addrs, the two capacities, pending, messages, writes."""
+        self._need_dns()
+        t = np.zeros(1, dtype=N.DNS_TRACK_INFO_DTYPE)
+        N.check(N.gpu_lib().fb_dns_track_info_get(self.ctx, N.ptr(t)))
+        return {k: int(t[0][k]) for k in N.DNS_TRACK_INFO_FIELDS}
+
+    def dns_names(self, ids):
+        """{id: str} for the given name ids (fb_dns_names_dev for the ids not fetched before; 0 is left out)."""
+        want = sorted({int(i) for i in ids} - {0} - set(self._dns_names))
+        if want:
+            a = np.array(want, dtype=np.uint32)
+            d_ids = N.DeviceBuffer(a.nbytes).upload(a)
+            d_out, d_len = N.DeviceBuffer(len(a) * N.FB_DNS_MAX_NAME), N.DeviceBuffer(len(a) * 2)
+            N.check(N.gpu_lib().fb_dns_names_dev(self.ctx, d_ids.ptr, len(a), d_out.ptr, d_len.ptr, None))
+            raw = d_out.download(np.zeros((len(a), N.FB_DNS_MAX_NAME), dtype=np.uint8))
+            ln = d_len.download(np.zeros(len(a), dtype=np.uint16))
+            fetched = {i: bytes(r[: int(l)]).decode("ascii") for i, r, l in zip(want, raw, ln)}
+            # (length 0 is also what an id the store does not hold yet gives: not kept)
+            self._dns_names.update({i: s for i, s in fetched.items() if s})
+        else:
+            fetched = {}
+        return {int(i): self._dns_names.get(int(i), fetched.get(int(i), "")) for i in ids if int(i)}
+
+    def dns_resolution_ids(self):
+        """{ip: name id} (fb_dns_export_resolutions_dev), exported again only when a resolution was written."""
+        info = self.dns_track_info()
+        if self._dns_res[0] != info["writes"]:
+            cap = max(info["addrs"], 1)
+            d_out, d_n = N.DeviceBuffer(cap * N.DNS_RESOLUTION_DTYPE.itemsize), N.DeviceBuffer(8)
+            N.check(N.gpu_lib().fb_dns_export_resolutions_dev(self.ctx, d_out.ptr, cap, d_n.ptr, None))
+            m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
+            recs = d_out.download(np.zeros(cap, dtype=N.DNS_RESOLUTION_DTYPE))[:m]
+            self._dns_res = (info["writes"], {words_to_ip(r["ip"]["addr"], int(r["ip"]["family"])): int(r["name_id"])
+                                              for r in recs})
+        return self._dns_res[1]
+
+    def dns_resolutions(self):
+        """dns_resolutions (src/dns.rs:19): {ip: name}."""
+        ids = self.dns_resolution_ids()
+        names = self.dns_names(ids.values())
+        return {ip: names[i] for ip, i in ids.items()}
+
+    def dns_pending_ids(self):
+        """(name id, query time) of every transaction id (fb_dns_export_pending_dev); 0: none pending."""
+        self._need_dns()
+        d_id, d_t = N.DeviceBuffer(N.FB_DNS_IDS * 4), N.DeviceBuffer(N.FB_DNS_IDS * 8)
+        N.check(N.gpu_lib().fb_dns_export_pending_dev(self.ctx, d_id.ptr, d_t.ptr, None))
+        return (d_id.download(np.zeros(N.FB_DNS_IDS, dtype=np.uint32)),
+                d_t.download(np.zeros(N.FB_DNS_IDS, dtype=np.uint64)))
+
+    def dns_pending(self):
+        """pending_dns_queries (src/dns.rs:18): {transaction id: name}."""
+        ids, _ = self.dns_pending_ids()
+        tx = np.nonzero(ids)[0]
+        names = self.dns_names(ids[tx])
+        return {int(t): names[int(ids[t])] for t in tx}
+
+    def expire_dns(self, now_ns):
+        """The cleanup task of src/dns.rs:101-121 at now_ns on the capture clock: the pending queries of
+        30 s and older are dropped; returns their number."""
+        self._need_dns()
+        n = C.c_uint64(0)
+        N.check(N.gpu_lib().fb_dns_expire(self.ctx, int(now_ns), C.byref(n)))
+        return n.value
+
+    def dns_lookup(self, ips):
+        """fb_dns_lookup_dev: the name id each address resolves to (0: none)."""
+        self._need_dns()
+        t = own_ip_table(list(ips))
+        if not len(t):
+            return np.zeros(0, dtype=np.uint32)
+        d_ips, d_out = N.DeviceBuffer(t.nbytes).upload(t), N.DeviceBuffer(len(t) * 4)
+        N.check(N.gpu_lib().fb_dns_lookup_dev(self.ctx, d_ips.ptr, len(t), d_out.ptr, None))
+        return d_out.download(np.zeros(len(t), dtype=np.uint32))
+
+    def clear_dns(self):
+        """fb_dns_track_clear: the tracker's state and the sessions' domains are gone."""
+        self._need_dns()
+        N.check(N.gpu_lib().fb_dns_track_clear(self.ctx))
+        self._dns_names = {}
+        self._dns_res = (None, {})
+
+    # ---- domain pass (src/capture.rs:1307-1411; fb_flow_domains) ----------------------------------
+    def update_domains(self):
+        """populate_domain_names over every current session from the tracked resolutions; returns the
+        pass's counters (fb_dom_stats)."""
+        self._need_dns()
+        st = np.zeros(1, dtype=N.DOM_STATS_DTYPE)
+        N.check(N.gpu_lib().fb_flow_domains(self.ctx, 0, N.ptr(st), None))
+        self._dom_ran = True
+        return {k: int(st[0][k]) for k in N.DOM_STATS_FIELDS}
+
+    def domain_ids(self):
+        """fb_flow_domains_dev: the (src, dst) name ids of every table slot (index = fb_flow_rec.slot)."""
+        cap = int(self.table_info()["capacity"])
+        out = np.zeros(max(cap, 1), dtype=N.FLOW_DOMAIN_DTYPE)
+        if cap:
+            d = N.DeviceBuffer(cap * 8)
+            N.check(N.gpu_lib().fb_flow_domains_dev(self.ctx, d.ptr, cap, None))
+            d.download(out, cap * 8)
+        return out[:cap]
+
+    def _domains(self):
+        """flows_to_sessions' `domains` (None while no domain pass has run)."""
+        if not (self.track_dns and self._dom_ran):
+            return None
+        ids = self.domain_ids()
+        pairs = np.stack([ids["src_name_id"], ids["dst_name_id"]], axis=1)
+        return pairs, self.dns_names(np.unique(pairs))
+
+    process = process_frames
 
     def process_frames_seg(self, frames, offsets, flow=True, ts=None):
         """The segmented streaming path (fb_process_seg_dev / fb_parse_classify_seg_dev): same
@@ -417,7 +600,8 @@ class FlodbaddGpuCapture:
         if incremental:
             views = self.export_view(N.FB_VIEW_ALL, since, self.filter)
             out = views_to_sessions(views, self.histories if self.track_history else None, self._bl_names,
-                                    whitelist=bool(self._wl_name or self._bl_marked), blacklist=self._bl_ran)
+                                    whitelist=bool(self._wl_name or self._bl_marked), blacklist=self._bl_ran,
+                                    domains=self._domains())
             return self._merge_anomaly(self._overlay_host_ok(out), views["rec"], views)
         if now_ns is not None:
             self._fetch_ts["sessions"] = int(now_ns)
@@ -427,7 +611,7 @@ class FlodbaddGpuCapture:
                                 status=self.status_bytes() if self.timed else None,
                                 whitelist=self.whitelist_bytes() if (self._wl_name or self._bl_marked) else None,
                                 blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None,
-                                modified=self._modified())
+                                modified=self._modified(), domains=self._domains())
         return self._merge_anomaly(self._overlay_host_ok(out), flows)
 
     def _overlay_host_ok(self, out):
@@ -449,7 +633,7 @@ class FlodbaddGpuCapture:
         if incremental:
             views = self.export_view(N.FB_VIEW_CURRENT, since, self.filter)
             out = views_to_sessions(views, self.histories if self.track_history else None, self._bl_names,
-                                    whitelist=False, blacklist=self._bl_ran)
+                                    whitelist=False, blacklist=self._bl_ran, domains=self._domains())
             return self._merge_anomaly(out, views["rec"], views)
         if now_ns is not None:
             self._fetch_ts["current"] = int(now_ns)
@@ -459,7 +643,7 @@ class FlodbaddGpuCapture:
         out = flows_to_sessions(flows, self.histories if self.track_history else None, times=self.export_times(),
                                 status=status,
                                 blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None,
-                                modified=self._modified())
+                                modified=self._modified(), domains=self._domains())
         return self._merge_anomaly(out, flows)
 
     # ---- new-session enrichment (src/packets.rs:429-485) -------------------------------------
@@ -560,7 +744,8 @@ class FlodbaddGpuCapture:
         if incremental:
             views = self.export_view(N.FB_VIEW_BLACKLISTED, since)
             out = views_to_sessions(views, self.histories if self.track_history else None, self._bl_names,
-                                    timed=self.timed, whitelist=bool(self._wl_name or self._bl_marked))
+                                    timed=self.timed, whitelist=bool(self._wl_name or self._bl_marked),
+                                    domains=self._domains())
             return self._merge_anomaly(out, views["rec"], views)
         if now_ns is not None:
             self._fetch_ts["blacklisted"] = int(now_ns)
@@ -572,7 +757,7 @@ class FlodbaddGpuCapture:
                                 times=self.export_times() if self.timed else None,
                                 status=self.status_bytes() if self.timed else None,
                                 whitelist=self.whitelist_bytes() if (self._wl_name or self._bl_marked) else None,
-                                blacklist=(by_slot, self._bl_names), modified=self._modified())
+                                blacklist=(by_slot, self._bl_names), modified=self._modified(), domains=self._domains())
         return self._merge_anomaly(out, flows)
 
     def get_blacklisted_status(self, now_ns=None):
@@ -581,16 +766,18 @@ class FlodbaddGpuCapture:
 
     def update_sessions(self, now_ns=None, dns_resolutions=None, process_names=None):
         """update_sessions_internal's per-session passes in the reference's order (src/capture.rs:
-        1811-1882): the status (timed captures, when now_ns is given), the blacklist pass with its
-        whitelist fallback, then the whitelist pass when a list is active.  Returns the three calls'
-        counters ({"status", "blacklist", "whitelist"}; None for a pass that did not run).  With now_ns
-        the passes stamp the sessions they change with it (set_pass_time)."""
+        1811-1882): the status (timed captures, when now_ns is given), the domain pass when the capture
+        tracks DNS (src/capture.rs:1824-1848), the blacklist pass with its whitelist fallback, then the
+        whitelist pass when a list is active -- with the tracked resolutions when the caller hands it
+        none.  Returns the calls' counters ({"status", "blacklist", "whitelist", "domains"}; None for a pass
+        that did not run).  With now_ns the passes stamp the sessions they change with it (set_pass_time)."""
         if now_ns is not None:
             self.set_pass_time(now_ns)
         age = self.update_sessions_status(now_ns) if (self.timed and now_ns is not None) else None
+        dom = self.update_domains() if (self.track_dns and self.flow_capacity) else None
         bl = self.update_blacklist(mark_whitelist=True)
         wl = self.update_whitelist(dns_resolutions, process_names)
-        return {"status": age, "blacklist": bl, "whitelist": wl}
+        return {"status": age, "blacklist": bl, "whitelist": wl, "domains": dom}
 
     # ---- anomaly pass (src/analyzer.rs; fb_flow_anomaly) ------------------------------------------
     def set_anomaly_model(self, forest, stats, thresholds, service_codes=None):
@@ -820,10 +1007,13 @@ class FlodbaddGpuCapture:
         domains of dns_resolutions {ip: domain} expanded to addresses -- is installed if it is not yet
         and the table is evaluated in one pass.  process_names {Session: process name}: the flows the
         pass marks for a host check are then decided by the full endpoint_matches with their domain
-        and process.  Returns the pass's counters, or None."""
+        and process.  A capture that tracks DNS uses its own resolutions when dns_resolutions is None.
+        Returns the pass's counters, or None."""
         self._wl_inputs = (dns_resolutions, process_names)
         if not self._wl_name:
             return None
+        if dns_resolutions is None and self.track_dns:  # the capture's own passive resolutions
+            dns_resolutions = {str(ip): name for ip, name in self.dns_resolutions().items()}
         want = dict(dns_resolutions or {})
         if self._wl_installed is None or self._wl_installed[1] != want:
             comp = self._whitelists.compile(self._wl_name, self._asn_records, want)
@@ -875,8 +1065,8 @@ class FlodbaddGpuCapture:
             exc = self._wl_exceptions
         if not len(exc):
             return []
-        dns, proc = self._wl_inputs[0] or {}, self._wl_inputs[1] or {}
-        comp = self._wl_installed[0]
+        proc = self._wl_inputs[1] or {}
+        comp, dns = self._wl_installed  # (the resolutions the installed list was compiled with)
         reasons = {}
         for r, asn in zip(exc, self._dst_asn(exc)):
             s = Session.from_key(r)
@@ -886,11 +1076,12 @@ class FlodbaddGpuCapture:
                                          s.protocol.name, a[0], a[1], a[2], proc.get(s))
         if views is not None:
             out = views_to_sessions(views, self.histories if self.track_history else None, whitelist=False,
-                                    blacklist=False)
+                                    blacklist=False, domains=self._domains())
         else:
             out = flows_to_sessions(exc, self.histories if self.track_history else None,
                                     times=self.export_times() if self.timed else None,
-                                    status=self.status_bytes() if self.timed else None, modified=self._modified())
+                                    status=self.status_bytes() if self.timed else None, modified=self._modified(),
+                                    domains=self._domains())
         for info in out:
             info.is_whitelisted = WhitelistState.NonConforming
             info.whitelist_reason = reasons[info.session]
@@ -910,6 +1101,7 @@ class FlodbaddGpuCapture:
         self._wl_host_ok = set()
         self._wl_exceptions = np.zeros(0, dtype=N.FLOW_REC_DTYPE)
         self._bl_marked = False
+        self._dom_ran = False
 
     def close(self):
         if getattr(self, "ctx", None):

@@ -57,7 +57,7 @@ struct UpdScratch {
 // Per-slot planes: arrays beside the table, one element per slot, that a flow's element follows through
 // every slot move.  Described once here; the functions below (plane_ensure .. plane_copy_out) are the
 // only code that allocates, moves, clears or frees one, so a new plane is one entry and its pass.
-enum PlaneId : uint32_t { kPlaneTime, kPlaneStatus, kPlaneWl, kPlaneBl, kPlaneAn, kPlaneMod, kPlanes };
+enum PlaneId : uint32_t { kPlaneTime, kPlaneStatus, kPlaneWl, kPlaneBl, kPlaneAn, kPlaneMod, kPlaneDom, kPlanes };
 struct PlaneDesc {
     size_t elem;       // bytes per slot
     const char* name;  // in error text
@@ -76,9 +76,11 @@ static const PlaneDesc kPlaneDesc[kPlanes] = {
     {sizeof(fb_an_rec), "anomaly plane", true, false, launch_plane_remap<fb_an_rec>},   // fb_anomaly.hip
     // the passes' last_modified stamps (fb_set_pass_time; read by fb_view.hip): made by the first stamped pass
     {8, "stamp plane", true, false, launch_plane_remap<unsigned long long>},
+    {sizeof(fb_flow_domain), "domain plane", true, false, launch_plane_remap<uint2>},   // fb_domains.hip
 };
+static_assert(sizeof(fb_flow_domain) == sizeof(uint2), "one name-id pair per slot");
 // the counter words of one synchronous pass over the table (pass_begin / pass_end)
-constexpr uint32_t kPassStatWords = std::max({kAgeStatWords, kWlCounters, kBlCounters, kAnCounters});
+constexpr uint32_t kPassStatWords = std::max({kAgeStatWords, kWlCounters, kBlCounters, kAnCounters, kDomCounters});
 
 struct fb_ctx {
     int device = 0;
@@ -162,6 +164,8 @@ struct fb_ctx {
     uint32_t* d_an_service = nullptr;  // [65536]; null: every code 0
     uint32_t an_trees = 0;
     fb_an_params an_prm = {};
+    // DNS tracker (fb_dns_track_enable, fb_dnstrack.hip); null: tracking is off
+    DnsTrack* dns = nullptr;
     void* d_mscratch = nullptr;   // multi-GPU merge scratch (export owner counts / merge tables)
     hipEvent_t ev_mscratch = nullptr;  // after the last export / merge that used d_mscratch (either may
                                        // run on any stream: the next use waits for it)
@@ -718,6 +722,7 @@ int fb_destroy(fb_ctx* c) {
     hipFree(c->d_an_nodes);
     hipFree(c->d_an_first);
     hipFree(c->d_an_service);
+    dnstrack_free(c->dns);
     hipFree(c->d_mscratch);
     if (c->ev_mscratch) hipEventDestroy(c->ev_mscratch);
     if (c->h_mbox) hipHostFree(c->h_mbox);
@@ -2271,6 +2276,128 @@ int fb_flow_export_blacklisted_dev(fb_ctx* c, fb_flow_rec* d_out, uint64_t* d_ma
                                            (unsigned long long*)d_masks, cap, (unsigned long long*)d_n,
                                            c->plane<FlowTime>(kPlaneTime), s));
     return FB_OK;
+}
+
+// ---- DNS tracker (fb_dnstrack.hip) and the domain pass (fb_domains.hip) -------------------------------
+static int dns_ready(const fb_ctx* c) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    if (!c->dns) return set_err(FB_ERR_INVAL, "DNS tracking is not enabled (fb_dns_track_enable)");
+    return FB_OK;
+}
+
+int fb_dns_track_enable(fb_ctx* c, const fb_dns_track_config* cfg) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    if (c->dns) return set_err(FB_ERR_INVAL, "DNS tracking is already enabled");
+    DeviceGuard g(c->device);
+    return dnstrack_create(&c->dns, cfg);
+}
+
+int fb_dns_track_clear(fb_ctx* c) {
+    int rc = dns_ready(c);
+    if (rc) return rc;
+    DeviceGuard g(c->device);
+    rc = drain_updates(c);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    rc = dnstrack_clear(c->dns, nullptr);
+    if (rc) return rc;
+    HIP_TRY(plane_zero(c, kPlaneDom, nullptr));  // the ids died with the store
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return FB_OK;
+}
+
+int fb_dns_track_dev(fb_ctx* c, const fb_dns_msg* d_msgs, const char* d_names, const fb_ip* d_addrs, uint32_t n,
+                     const fb_batch_stats* d_stats, const uint64_t* d_ts, uint32_t* d_taken, fb_dns_track_stats* out,
+                     void* stream) {
+    const int rc = dns_ready(c);
+    if (rc) return rc;
+    if (n && (!d_msgs || !d_names || !d_addrs)) return set_err(FB_ERR_INVAL, "bad arguments");
+    if (reinterpret_cast<uintptr_t>(d_names) & 3u) return set_err(FB_ERR_INVAL, "d_names must be 4-byte aligned");
+    DeviceGuard g(c->device);
+    return dnstrack_track(c->dns, d_msgs, d_names, d_addrs, n, d_stats, (const unsigned long long*)d_ts, d_taken, out,
+                          (hipStream_t)stream);
+}
+
+int fb_dns_expire(fb_ctx* c, uint64_t now_ns, uint64_t* dropped) {
+    const int rc = dns_ready(c);
+    if (rc) return rc;
+    DeviceGuard g(c->device);
+    return dnstrack_expire(c->dns, now_ns, dropped, nullptr);
+}
+
+int fb_dns_track_info_get(fb_ctx* c, fb_dns_track_info* out) {
+    const int rc = dns_ready(c);
+    if (rc) return rc;
+    if (!out) return set_err(FB_ERR_INVAL, "out is NULL");
+    DeviceGuard g(c->device);
+    return dnstrack_info(c->dns, out, nullptr);
+}
+
+int fb_dns_export_resolutions_dev(fb_ctx* c, fb_dns_resolution* d_out, uint64_t cap, uint64_t* d_n, void* stream) {
+    const int rc = dns_ready(c);
+    if (rc) return rc;
+    if (!d_n || (cap && !d_out)) return set_err(FB_ERR_INVAL, "bad arguments");
+    DeviceGuard g(c->device);
+    return dnstrack_export_resolutions(c->dns, d_out, cap, d_n, (hipStream_t)stream);
+}
+
+int fb_dns_export_pending_dev(fb_ctx* c, uint32_t* d_name_id, uint64_t* d_time, void* stream) {
+    const int rc = dns_ready(c);
+    if (rc) return rc;
+    if (!d_name_id) return set_err(FB_ERR_INVAL, "d_name_id is NULL");
+    DeviceGuard g(c->device);
+    return dnstrack_export_pending(c->dns, d_name_id, d_time, (hipStream_t)stream);
+}
+
+int fb_dns_names_dev(fb_ctx* c, const uint32_t* d_ids, uint64_t n, char* d_out, uint16_t* d_len, void* stream) {
+    const int rc = dns_ready(c);
+    if (rc) return rc;
+    if (n && (!d_ids || !d_out || !d_len)) return set_err(FB_ERR_INVAL, "bad arguments");
+    if (reinterpret_cast<uintptr_t>(d_out) & 3u) return set_err(FB_ERR_INVAL, "d_out must be 4-byte aligned");
+    DeviceGuard g(c->device);
+    return dnstrack_names(c->dns, d_ids, n, d_out, d_len, (hipStream_t)stream);
+}
+
+int fb_dns_lookup_dev(fb_ctx* c, const fb_ip* d_ips, uint64_t n, uint32_t* d_name_id, void* stream) {
+    const int rc = dns_ready(c);
+    if (rc) return rc;
+    if (n && (!d_ips || !d_name_id)) return set_err(FB_ERR_INVAL, "bad arguments");
+    DeviceGuard g(c->device);
+    return dnstrack_lookup(c->dns, d_ips, n, d_name_id, (hipStream_t)stream);
+}
+
+// Synchronous, like fb_flow_blacklist: drains the updates in flight, one pass, the counters read back.
+int fb_flow_domains(fb_ctx* c, uint32_t flags, fb_dom_stats* out, void* stream) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->dns) return set_err(FB_ERR_INVAL, "DNS tracking is not enabled (fb_dns_track_enable)");
+    if (flags) return set_err(FB_ERR_INVAL, "unknown flags %u", flags);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = pass_begin(c, kDomCounters, s);
+    if (!rc) rc = plane_ensure(c, kPlaneDom, s);
+    unsigned long long* mod = nullptr;
+    if (!rc) rc = pass_stamps(c, s, &mod);
+    if (rc) return rc;
+    HIP_TRY(launch_flow_domains(dnstrack_tables(c->dns), c->d_table, c->table_cap, c->plane<uint8_t>(kPlaneStatus),
+                                c->plane<uint2>(kPlaneDom), c->d_pass_stats, s, mod, c->pass_time));
+    unsigned long long h[kDomCounters] = {};
+    rc = pass_end(c, h, kDomCounters, s);
+    if (rc) return rc;
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        out->flows = h[0];
+        out->current = h[1];
+        out->src_set = h[2];
+        out->dst_set = h[3];
+        out->changed = h[4];
+        out->with_domain = h[5];
+    }
+    return FB_OK;
+}
+
+int fb_flow_domains_dev(fb_ctx* c, fb_flow_domain* d_out, uint64_t cap, void* stream) {
+    return plane_copy_out(c, kPlaneDom, d_out, cap, stream);
 }
 
 // ---- anomaly pass (fb_anomaly.hip) -------------------------------------------------------------------

@@ -920,4 +920,73 @@ hipError_t launch_flow_view(const ViewArgs& a, fb_flow_view* out, unsigned long 
 hipError_t launch_dns_parse(const uint8_t* frames, unsigned long long frames_bytes, const fb_dns_out* dns, uint32_t n,
                             const fb_batch_stats* stats, fb_dns_msg* msgs, char* names, fb_ip* addrs, hipStream_t s);
 
+// DNS tracker (fb_dnstrack.hip, fb_dns_track_*): the device-resident state of
+// DnsPacketProcessor (src/dns.rs:16-99).  Name store: names[id * FB_DNS_MAX_NAME] (the bytes past the
+// length zeroed) and name_len[id], ids 1-based; resolutions: an open-addressing table over (4 address
+// words, family) -- atag[slot] (0: empty, else the masked 64-bit hash | kDnsTagUsed), akey[slot * 5],
+// aval[slot] = order << kDnsIdBits | name_id, the largest order (the last writer in packet order) kept by
+// a 64-bit atomicMax.  DnsTables is what a reader needs: the domain pass and fb_dns_lookup_dev.
+constexpr uint32_t kDnsIdBits = 24, kDnsIdMask = (1u << kDnsIdBits) - 1u;
+constexpr unsigned long long kDnsTagUsed = 1ull << 63;
+constexpr unsigned long long kDnsMaxOrder = 1ull << 40;  // orders below this fit beside an id
+struct DnsTables {
+    const unsigned long long* atag;
+    const uint32_t* akey;
+    const unsigned long long* aval;
+    unsigned long long aslots;  // a power of two
+    unsigned long long hash_mask;
+    const uint32_t* names;      // dwords: FB_DNS_MAX_NAME / 4 per id
+    const uint16_t* name_len;
+    uint32_t n_names;
+};
+__host__ __device__ inline unsigned long long dns_addr_tag(const uint32_t w[4], uint32_t family,
+                                                           unsigned long long hash_mask) {
+    unsigned long long h = 0x9E3779B97F4A7C15ull ^ family;
+    for (int j = 0; j < 4; j += 2) {
+        h ^= (unsigned long long)w[j] | ((unsigned long long)w[j + 1] << 32);
+        h *= 0xBF58476D1CE4E5B9ull;
+        h ^= h >> 31;
+    }
+    h *= 0xFF51AFD7ED558CCDull;
+    h ^= h >> 33;
+    return (h & hash_mask) | kDnsTagUsed;
+}
+// dns_resolutions.get(ip): the name id the address resolves to, 0 for none.  Read-only: no tracking call
+// runs beside it (the tracking call is synchronous).
+__device__ __forceinline__ uint32_t dns_lookup(const DnsTables& t, const uint32_t w[4], uint32_t family) {
+    const unsigned long long tag = dns_addr_tag(w, family, t.hash_mask), mask = t.aslots - 1ull;
+    unsigned long long pos = tag & mask;
+    for (unsigned long long step = 0; step < t.aslots; ++step, pos = (pos + 1ull) & mask) {
+        const unsigned long long g = t.atag[pos];
+        if (g == 0ull) return 0u;
+        if (g != tag) continue;
+        const uint32_t* k = t.akey + pos * 5ull;
+        if (k[0] == w[0] && k[1] == w[1] && k[2] == w[2] && k[3] == w[3] && k[4] == family)
+            return (uint32_t)t.aval[pos] & kDnsIdMask;
+    }
+    return 0u;
+}
+struct DnsTrack;  // the host's handle (fb_dnstrack.hip); every function below returns an fb_err
+int dnstrack_create(DnsTrack** t, const fb_dns_track_config* cfg);
+void dnstrack_free(DnsTrack* t);
+int dnstrack_clear(DnsTrack* t, hipStream_t s);
+int dnstrack_track(DnsTrack* t, const fb_dns_msg* msgs, const char* names, const fb_ip* addrs, uint32_t n,
+                   const fb_batch_stats* stats, const unsigned long long* ts, uint32_t* taken, fb_dns_track_stats* out,
+                   hipStream_t s);
+int dnstrack_expire(DnsTrack* t, unsigned long long now, uint64_t* dropped, hipStream_t s);
+int dnstrack_info(DnsTrack* t, fb_dns_track_info* out, hipStream_t s);
+int dnstrack_export_resolutions(DnsTrack* t, fb_dns_resolution* out, uint64_t cap, uint64_t* d_n, hipStream_t s);
+int dnstrack_export_pending(DnsTrack* t, uint32_t* name_id, uint64_t* time, hipStream_t s);
+int dnstrack_names(DnsTrack* t, const uint32_t* ids, uint64_t n, char* out, uint16_t* len, hipStream_t s);
+int dnstrack_lookup(DnsTrack* t, const fb_ip* ips, uint64_t n, uint32_t* name_id, hipStream_t s);
+DnsTables dnstrack_tables(const DnsTrack* t);
+
+// Domain pass over the table (fb_domains.hip, fb_flow_domains): populate_domain_names (src/capture.rs:
+// 1307-1411) restricted to the passive resolutions.  dom: two name ids per slot (0: none); status: the
+// status plane or null (every flow current).  The call's device counters are fb_dom_stats' first six fields.
+constexpr uint32_t kDomCounters = 6;
+hipError_t launch_flow_domains(const DnsTables& t, const FlowSlot* table, unsigned long long cap, const uint8_t* status,
+                               uint2* dom, unsigned long long* stats, hipStream_t s,
+                               unsigned long long* mod = nullptr, unsigned long long now = 0ull);
+
 }  // namespace fbk

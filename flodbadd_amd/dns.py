@@ -8,6 +8,9 @@ in packet order, what DnsPacketProcessor::process_dns_packet does with each pars
 Packets DnsPacket::parse rejects are skipped (the reference logs a warning).  The expiry of
 pending queries (30 s, src/dns.rs:101-121) is wall-clock bookkeeping left to the caller
 (`expire`).
+
+A capture made with track_dns=True keeps the same state on the device (fb_dns_track_dev, DESIGN.md
+3.14); `DnsResolver` is the host restatement its tests compare with.
 """
 import numpy as np
 

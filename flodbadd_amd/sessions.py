@@ -215,6 +215,11 @@ class SessionInfo:
     whitelist_reason: Optional[str] = None
     criticality: str = ""
     last_modified_ns: int = 0
+    # populate_domain_names (src/capture.rs:1307-1411): the names the domain pass gave the two addresses from
+    # the passively captured DNS resolutions (FlodbaddGpuCapture(track_dns=True)); None before it, and always
+    # on a capture that does not track DNS
+    src_domain: Optional[str] = None
+    dst_domain: Optional[str] = None
 
 
 _SERVICE_NAMES = None
@@ -319,7 +324,8 @@ def histories_from_records(recs):
     return {k: (h, state.get(k)) for k, h in hist.items()}
 
 
-def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=None, blacklist=None, modified=None):
+def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=None, blacklist=None, modified=None,
+                      domains=None):
     """fb_flow_rec records -> SessionInfo list sorted by the derived Ord of Session.  `histories`
     ({table slot: str}, FlodbaddGpuCapture.histories) supplies the history strings; the locality
     flags and dst_service come from fb_flow_rec.session_flags (stored at insert, src/packets.rs:
@@ -333,7 +339,9 @@ def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=
     carries the reason "Session is blacklisted".  `blacklist`: (the mask word of every table slot,
     fb_flow_blacklist_dev; the list names), decoded into SessionInfo.criticality.  `modified`: the stamp
     of every table slot (fb_flow_modified_dev); SessionInfo.last_modified_ns is the later of it and the
-    flow's last_activity_ns.  The per-slot arguments may be arrays indexed by slot or {slot: value}."""
+    flow's last_activity_ns.  `domains`: (the name-id pair of every table slot, fb_flow_domains_dev; {name id:
+    str}), decoded into SessionInfo.src_domain / dst_domain (id 0: None).  The per-slot arguments may be arrays
+    indexed by slot or {slot: value}."""
     from .enrich import criticality_of  # (enrich imports this module)
     if flows.dtype != FLOW_REC_DTYPE:
         raise TypeError("expected fb_flow_rec records (FLOW_REC_DTYPE), got %s" % flows.dtype)
@@ -376,17 +384,23 @@ def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=
         if blacklist is not None:
             info.criticality = criticality_of(blacklist[0][int(r["slot"])], blacklist[1])
         info.last_modified_ns = max(st.last_activity_ns or 0, int(modified[int(r["slot"])]) if modified is not None else 0)
+        if domains is not None:
+            ids = domains[0][int(r["slot"])]
+            info.src_domain = domains[1][int(ids[0])] if int(ids[0]) else None
+            info.dst_domain = domains[1][int(ids[1])] if int(ids[1]) else None
         out.append(info)
     out.sort(key=lambda i: i.session.sort_key())
     return out
 
 
-def views_to_sessions(views, histories=None, bl_names=None, timed=True, status=True, whitelist=True, blacklist=True):
+def views_to_sessions(views, histories=None, bl_names=None, timed=True, status=True, whitelist=True, blacklist=True,
+                      domains=None):
     """fb_flow_view records (fb_flow_export_view) -> the SessionInfo list flows_to_sessions builds from the
     separate exports: each view carries its flow's record, time record and per-slot plane elements, so no
     other export is needed.  timed: the capture is timed (else the time records are zero and left out);
     status / whitelist / blacklist: decode that plane's element (a getter that does not hand
-    flows_to_sessions a plane passes False here); bl_names: the list names of the blacklist masks."""
+    flows_to_sessions a plane passes False here); bl_names: the list names of the blacklist masks; domains: as
+    flows_to_sessions takes it, joined by slot (the view record itself carries no domain)."""
     views = np.ascontiguousarray(views)
     if views.dtype != FLOW_VIEW_DTYPE:
         raise TypeError("expected fb_flow_view records (FLOW_VIEW_DTYPE), got %s" % views.dtype)
@@ -397,7 +411,7 @@ def views_to_sessions(views, histories=None, bl_names=None, timed=True, status=T
                              status=by_slot("status") if (status and timed) else None,
                              whitelist=by_slot("wl_state") if whitelist else None,
                              blacklist=(by_slot("bl_mask"), bl_names or []) if blacklist else None,
-                             modified=by_slot("stamp_ns"))
+                             modified=by_slot("stamp_ns"), domains=domains)
 
 
 def filter_sessions(sessions: List[SessionInfo], flt: SessionFilter, lan_v6=()) -> List[SessionInfo]:

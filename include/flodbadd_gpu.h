@@ -647,10 +647,122 @@ typedef struct fb_dns_msg {
  * the first d_stats->n_dns (read on the device) are parsed.  d_names: n * FB_DNS_MAX_NAME bytes,
  * 4-byte aligned (the name is written a dword at a time; bytes past name_len are unspecified),
  * d_addrs: n * FB_DNS_MAX_ADDRS fb_ip.  DEVICE pointers, asynchronous.  The ordered bookkeeping
- * (pending queries by id, resolutions) stays on the host: a few operations per DNS packet. */
+ * (pending queries by id, resolutions) runs on the device too, over these arrays where they lie:
+ * fb_dns_track_dev below. */
 int fb_dns_parse_dev(fb_ctx* ctx, const uint8_t* d_frames, uint64_t frames_bytes, const fb_dns_out* d_dns,
                      uint32_t n, const fb_batch_stats* d_stats, fb_dns_msg* d_msgs, char* d_names,
                      fb_ip* d_addrs, void* stream);
+
+/* ---- DNS tracker: DnsPacketProcessor's state on the device (src/dns.rs:16-121) -------------------
+ * pending_dns_queries (transaction id -> name) and dns_resolutions (address -> name) kept in device
+ * memory and brought forward, in packet order, from what fb_dns_parse_dev wrote.  Names are interned:
+ * every distinct first-question name (the exact bytes, case-sensitive) gets a name id, 1-based, that
+ * never changes or disappears until fb_dns_track_clear; 0 means "none" everywhere. */
+#define FB_DNS_EXPIRY_NS 30000000000ull /* pending queries this old are dropped (src/dns.rs:115-117) */
+#define FB_DNS_MAX_NAMES ((1u << 24) - 1u) /* name ids are 24 bits */
+typedef struct fb_dns_track_config {
+    uint64_t name_capacity; /*  0: distinct names before the first growth (0 = 65,536)                  */
+    uint64_t addr_capacity; /*  8: resolved addresses before the first growth (0 = 262,144)             */
+    uint64_t hash_mask;     /* 16: testing knob: the bits of the 64-bit hashes that are used (0 = all);
+                                   a narrow mask forces tag collisions and many insert rounds          */
+    uint32_t flags;         /* 24: 0                                                                    */
+    uint32_t reserved;      /* 28: 0                                                                    */
+} fb_dns_track_config; /* 32 bytes */
+typedef struct fb_dns_track_stats {
+    uint64_t messages;    /*  0: messages read (min(n, d_stats->n_dns))                                 */
+    uint64_t queries;     /*  8: queries accepted (status ok, a question, no reverse lookup)            */
+    uint64_t responses;   /* 16: responses with status ok                                               */
+    uint64_t matched;     /* 24: responses that took a pending name                                     */
+    uint64_t resolutions; /* 32: address -> name writes (the kept answers of the matched responses)     */
+    uint64_t names_new;   /* 40: names first seen in this call                                          */
+    uint64_t addrs_new;   /* 48: addresses first seen in this call                                      */
+    uint64_t rounds;      /* 56: insert rounds (kernel launches) of the longer of the two insert loops  */
+} fb_dns_track_stats; /* 64 bytes */
+typedef struct fb_dns_track_info {
+    uint64_t names;         /*  0: names stored                                                         */
+    uint64_t addrs;         /*  8: addresses stored                                                     */
+    uint64_t name_capacity; /* 16: names / addresses the tables take before they grow                   */
+    uint64_t addr_capacity; /* 24                                                                       */
+    uint64_t pending;       /* 32: transaction ids with a pending query                                 */
+    uint64_t messages;      /* 40: messages handed to fb_dns_track_dev so far (the next call's first order) */
+    uint64_t writes;        /* 48: changes whenever a resolution is written, or the state is cleared    */
+    uint64_t reserved;      /* 56                                                                       */
+} fb_dns_track_info; /* 64 bytes */
+typedef struct fb_dns_resolution {
+    fb_ip ip;          /*  0                                                                            */
+    uint32_t name_id;  /* 32                                                                            */
+    uint32_t reserved; /* 36                                                                            */
+    uint64_t order;    /* 40: the running message number of the response that wrote it                  */
+} fb_dns_resolution; /* 48 bytes */
+/* Make the tracker's state (cfg NULL: the defaults).  Works on a context without a flow table, as
+ * fb_dns_parse_dev does; a context that never calls it allocates nothing and runs no tracker code.
+ * FB_ERR_INVAL for non-zero flags / reserved, capacities above FB_DNS_MAX_NAMES / 2^28, or when
+ * tracking is already enabled. */
+int fb_dns_track_enable(fb_ctx* ctx, const fb_dns_track_config* cfg);
+/* Empty the state (names, pending, resolutions, the message count); the domain plane of
+ * fb_flow_domains is zeroed, since its ids die with the store.  FB_ERR_INVAL without tracking. */
+int fb_dns_track_clear(fb_ctx* ctx);
+/* Apply n parsed messages, in order, exactly as process_dns_packet does (src/dns.rs:35-99):
+ *   status != FB_DNS_OK               skipped
+ *   query, a question, not reverse    pending[id] = name
+ *   any other query                   nothing
+ *   response                          name = pending.remove(id); if there was one, every kept A / AAAA
+ *                                     answer address -> name (the later packet wins)
+ * d_msgs / d_names / d_addrs: DEVICE arrays as fb_dns_parse_dev writes them (d_names 4-byte aligned;
+ * the bytes past name_len are ignored).  d_stats (may be NULL): only the first d_stats->n_dns messages
+ * are read.  d_ts (may be NULL): frame times indexed by fb_dns_msg.pkt_index (fb_set_frame_times'
+ * array); a query accepted without it never expires.  d_taken (may be NULL): n words, the name id each
+ * response took, 0 for none and for non-responses.  `out` (HOST, may be NULL): the call's counters.
+ * SYNCHRONOUS: the insert rounds read a device counter between launches, and the tables grow before a
+ * call that could fill them.  FB_ERR_TABLE_FULL (state unchanged) when they cannot grow, FB_ERR_INVAL
+ * (state unchanged) without tracking, for a misaligned d_names, or when the message count would pass 2^40. */
+int fb_dns_track_dev(fb_ctx* ctx, const fb_dns_msg* d_msgs, const char* d_names, const fb_ip* d_addrs, uint32_t n,
+                     const fb_batch_stats* d_stats, const uint64_t* d_ts, uint32_t* d_taken,
+                     fb_dns_track_stats* out, void* stream);
+/* Drop the pending queries whose capture time t has now_ns - t >= FB_DNS_EXPIRY_NS (the reference keeps
+ * the younger ones, src/dns.rs:115-117); queries stored without a time stay.  *dropped (HOST, may be
+ * NULL).  Synchronous. */
+int fb_dns_expire(fb_ctx* ctx, uint64_t now_ns, uint64_t* dropped);
+int fb_dns_track_info_get(fb_ctx* ctx, fb_dns_track_info* out); /* synchronous (counts pending) */
+/* Every resolution, in no particular order; *d_n (device u64) receives their number, the first
+ * min(cap, *d_n) are stored.  DEVICE pointers, asynchronous. */
+int fb_dns_export_resolutions_dev(fb_ctx* ctx, fb_dns_resolution* d_out, uint64_t cap, uint64_t* d_n, void* stream);
+/* pending, indexed by transaction id: d_name_id[65536] (0: none) and d_time[65536] (may be NULL;
+ * UINT64_MAX: stored without a time).  DEVICE pointers, asynchronous. */
+int fb_dns_export_pending_dev(fb_ctx* ctx, uint32_t* d_name_id, uint64_t* d_time, void* stream);
+/* The strings of n ids: d_out[n * FB_DNS_MAX_NAME] (zero-filled past the length), d_len[n]; an
+ * unknown id gives length 0.  DEVICE pointers, asynchronous. */
+int fb_dns_names_dev(fb_ctx* ctx, const uint32_t* d_ids, uint64_t n, char* d_out, uint16_t* d_len, void* stream);
+/* dns_resolutions.get(ip) for n addresses: the name id, 0 for none -- the domain pass's own device
+ * function.  DEVICE pointers, asynchronous. */
+int fb_dns_lookup_dev(fb_ctx* ctx, const fb_ip* d_ips, uint64_t n, uint32_t* d_name_id, void* stream);
+
+/* ---- domain pass: populate_domain_names (src/capture.rs:1307-1411) over the tracked resolutions --
+ * For every CURRENT flow (FB_VIEW_CURRENT's predicate: status byte 0, or FB_STATUS_CURRENT set; without
+ * a status plane every flow) each side whose address has a resolution, whose name is neither "Unknown"
+ * nor "Resolving" and whose id differs from the stored one is written; nothing is ever unset.  A flow
+ * with either side written counts as `changed` and gets the pass time (fb_set_pass_time).  The ids live
+ * in a per-slot plane made by the first pass; they follow their flows through a growth and a purge, and
+ * fb_flow_clear / fb_dns_track_clear zero them. */
+typedef struct fb_flow_domain {
+    uint32_t src_name_id; /* 0 */
+    uint32_t dst_name_id; /* 4 */
+} fb_flow_domain; /* 8 bytes */
+typedef struct fb_dom_stats {
+    uint64_t flows;       /*  0: flows in the table                                                     */
+    uint64_t current;     /*  8: of them current (the ones looked up)                                   */
+    uint64_t src_set;     /* 16: source ids written                                                     */
+    uint64_t dst_set;     /* 24: destination ids written                                                */
+    uint64_t changed;     /* 32: flows with either side written                                         */
+    uint64_t with_domain; /* 40: flows with either id non-zero after the pass                           */
+    uint64_t reserved[2]; /* 48                                                                         */
+} fb_dom_stats; /* 64 bytes */
+/* Synchronous: waits for the updates in flight, like fb_flow_blacklist; timed and untimed contexts.
+ * `flags` must be 0; `out` may be NULL.  FB_ERR_INVAL without a flow table or without tracking. */
+int fb_flow_domains(fb_ctx* ctx, uint32_t flags, fb_dom_stats* out, void* stream);
+/* The ids of every table slot (min(cap, capacity) records, slot order; zeros before the first pass)
+ * into DEVICE memory.  Asynchronous. */
+int fb_flow_domains_dev(fb_ctx* ctx, fb_flow_domain* d_out, uint64_t cap, void* stream);
 
 int fb_flow_count(fb_ctx* ctx, uint64_t* n_flows, void* stream); /* synchronous */
 /* Copy every flow (slot order) to host memory; *n = flows written (<= cap). Synchronous. */
@@ -997,6 +1109,7 @@ int fb_if_score_dev(fb_ctx* ctx, const double* d_feat, uint64_t n, double* d_pat
  *   fb_flow_whitelist  the flows counted as `changed`;
  *   fb_flow_anomaly    the flows whose level or diagnostic codes differ from before the call (a new
  *                      path_sum alone does not show in the criticality string and does not stamp);
+ *   fb_flow_domains    the flows counted as `changed` (src/capture.rs:1397-1399);
  *   fb_flow_age        never.
  * A zero stamp: no pass has modified the flow.  The stamps follow their flows through a growth and a
  * purge (a purged flow that returns starts at 0), and fb_flow_clear zeroes them.
