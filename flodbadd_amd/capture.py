@@ -49,8 +49,9 @@ class BatchResult:
         self.stats = stats      # dict of fb_batch_stats
 
 
-def stats_dict(arr):
-    return {k: int(arr[0][k]) for k in N.STATS_FIELDS if not k.startswith("reserved")}
+def stats_dict(arr, fields=N.STATS_FIELDS):
+    """A one-record counters array (fb_batch_stats, or the record `fields` names) -> {field: int}."""
+    return {k: int(arr[0][k]) for k in fields if not k.startswith("reserved")}
 
 
 class FlodbaddGpuCapture:
@@ -108,7 +109,6 @@ class FlodbaddGpuCapture:
         self._wl_inputs = (None, None)  # the last update's dns_resolutions / process_names
         self._wl_host_ok = set()    # the Sessions the host resolved to Conforming (process names)
         self._wl_conformance = True
-        self._wl_exceptions = np.zeros(0, dtype=N.FLOW_REC_DTYPE)
         # blacklist pass (src/blacklists.rs:456-731): the custom model, the name of every installed
         # list (bit l of a mask), whether a pass has run and whether one has marked whitelist bytes
         self._blacklists = Blacklists()
@@ -122,9 +122,8 @@ class FlodbaddGpuCapture:
         self._an_mode = None
         self._an_codes = False  # the device holds service codes (analyzer.default_service_codes, or a model's)
         # incremental queries (src/capture.rs:411-426): the time of each getter's last full fetch (0: the
-        # reference's epoch), and whether a pass time was ever set (the stamp plane may then hold stamps)
+        # reference's epoch)
         self._fetch_ts = dict.fromkeys(("sessions", "current", "blacklisted", "exceptions"), 0)
-        self._stamped = False
         # DNS tracker (src/dns.rs:16-121): names are immutable per id, so the strings are fetched once
         # ({id: str}); the resolutions are exported again only when the tracker's `writes` has moved
         self.track_dns = bool(track_dns)
@@ -270,7 +269,7 @@ class FlodbaddGpuCapture:
                                              d_stats.ptr if d_stats is not None else None,
                                              d_ts.ptr if d_ts is not None else None,
                                              d_taken.ptr if want_taken else None, N.ptr(st), None))
-        out = {k: int(st[0][k]) for k in N.DNS_TRACK_STATS_FIELDS}
+        out = stats_dict(st, N.DNS_TRACK_STATS_FIELDS)
         if want_taken:
             out["taken"] = d_taken.download(np.zeros(max(n, 1), dtype=np.uint32))[:n]
         return out
@@ -302,7 +301,7 @@ class FlodbaddGpuCapture:
         self._need_dns()
         t = np.zeros(1, dtype=N.DNS_TRACK_INFO_DTYPE)
         N.check(N.gpu_lib().fb_dns_track_info_get(self.ctx, N.ptr(t)))
-        return {k: int(t[0][k]) for k in N.DNS_TRACK_INFO_FIELDS}
+        return stats_dict(t, N.DNS_TRACK_INFO_FIELDS)
 
     def dns_names(self, ids):
         """{id: str} for the given name ids (fb_dns_names_dev for the ids not fetched before; 0 is left out)."""
@@ -388,20 +387,14 @@ class FlodbaddGpuCapture:
         st = np.zeros(1, dtype=N.DOM_STATS_DTYPE)
         N.check(N.gpu_lib().fb_flow_domains(self.ctx, 0, N.ptr(st), None))
         self._dom_ran = True
-        return {k: int(st[0][k]) for k in N.DOM_STATS_FIELDS}
+        return stats_dict(st, N.DOM_STATS_FIELDS)
 
     def domain_ids(self):
         """fb_flow_domains_dev: the (src, dst) name ids of every table slot (index = fb_flow_rec.slot)."""
-        cap = int(self.table_info()["capacity"])
-        out = np.zeros(max(cap, 1), dtype=N.FLOW_DOMAIN_DTYPE)
-        if cap:
-            d = N.DeviceBuffer(cap * 8)
-            N.check(N.gpu_lib().fb_flow_domains_dev(self.ctx, d.ptr, cap, None))
-            d.download(out, cap * 8)
-        return out[:cap]
+        return self._plane("fb_flow_domains_dev", N.FLOW_DOMAIN_DTYPE)
 
     def _domains(self):
-        """flows_to_sessions' `domains` (None while no domain pass has run)."""
+        """views_to_sessions' `domains` (None while no domain pass has run)."""
         if not (self.track_dns and self._dom_ran):
             return None
         ids = self.domain_ids()
@@ -517,20 +510,34 @@ class FlodbaddGpuCapture:
     def status_bytes(self):
         """fb_flow_status_dev: the status byte of every table slot (index = fb_flow_rec.slot); all
         zero before the first update_sessions_status."""
+        return self._plane("fb_flow_status_dev", np.uint8)
+
+    def _plane(self, copy_fn, dtype):
+        """One per-slot plane at whole table capacity (index = fb_flow_rec.slot) through its fb_flow_*_dev copy."""
         cap = int(self.table_info()["capacity"])
-        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        out = np.zeros(max(cap, 1), dtype=dtype)
         if cap:
-            d = N.DeviceBuffer(cap)
-            N.check(N.gpu_lib().fb_flow_status_dev(self.ctx, d.ptr, cap, None))
-            d.download(out, cap)
+            d = N.DeviceBuffer(cap * out.itemsize)
+            N.check(getattr(N.gpu_lib(), copy_fn)(self.ctx, d.ptr, cap, None))
+            d.download(out, cap * out.itemsize)
         return out[:cap]
+
+    def _compact_export(self, export_fn, dtypes, *lead):
+        """A compacting export -- export_fn(ctx, *lead, one output per dtype, cap, d_n, stream) -- with room for
+        every flow: the count is read back and each output trimmed to it -> one array per dtype."""
+        cap = max(self.flow_count(), 1)
+        outs = [np.zeros(cap, dtype=t) for t in dtypes]
+        bufs = [N.DeviceBuffer(o.nbytes) for o in outs]
+        d_n = N.DeviceBuffer(8)
+        N.check(getattr(N.gpu_lib(), export_fn)(self.ctx, *lead, *(b.ptr for b in bufs), cap, d_n.ptr, None))
+        m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
+        return tuple(b.download(o)[:m] for b, o in zip(bufs, outs))
 
     # ---- incremental queries (src/capture.rs:411-426, 1578-1760) -------------------------------------
     def set_pass_time(self, now_ns):
         """fb_set_pass_time: the time -- on the capture timestamps' clock -- that the blacklist, whitelist and
         anomaly passes write into the sessions they change (SessionInfo.last_modified_ns); 0: no stamps."""
         N.check(N.gpu_lib().fb_set_pass_time(self.ctx, int(now_ns)))
-        self._stamped = self._stamped or int(now_ns) != 0
 
     def reset_fetch_timestamps(self):
         """reset_fetch_timestamps (src/capture.rs:411-426): every getter's next incremental fetch is full."""
@@ -539,13 +546,7 @@ class FlodbaddGpuCapture:
     def modified_stamps(self):
         """fb_flow_modified_dev: the stamp of every table slot (index = fb_flow_rec.slot); all zero while no
         pass has run under a pass time."""
-        cap = int(self.table_info()["capacity"])
-        out = np.zeros(max(cap, 1), dtype=np.uint64)
-        if cap:
-            d = N.DeviceBuffer(cap * 8)
-            N.check(N.gpu_lib().fb_flow_modified_dev(self.ctx, d.ptr, cap, None))
-            d.download(out, cap * 8)
-        return out[:cap]
+        return self._plane("fb_flow_modified_dev", np.uint64)
 
     def export_view(self, view_set=N.FB_VIEW_ALL, since_ns=None, session_filter=None):
         """fb_flow_export_view: the FLOW_VIEW_DTYPE records of the flows of `view_set` (N.FB_VIEW_*) that pass
@@ -562,13 +563,37 @@ class FlodbaddGpuCapture:
         N.check(N.gpu_lib().fb_flow_export_view(self.ctx, N.ptr(q), N.ptr(out), cnt, C.byref(n), None))
         return out[: n.value]
 
-    def _incremental(self, which):
+    def _since(self, which, incremental):
+        """What a getter call selects by: an incremental fetch, the flows modified since the getter's last full
+        fetch with a now_ns (timed captures); a full fetch, every flow (None)."""
+        if not incremental:
+            return None
         if not self.timed:
             raise ValueError("incremental fetches need a timed capture (timed=True): last_modified has no clock")
         return self._fetch_ts[which]
 
-    def _modified(self):
-        return self.modified_stamps() if self._stamped else None
+    def _fetched(self, which, now_ns, incremental):
+        """A full fetch with a now_ns moves the getter's fetch timestamp; nothing else does."""
+        if now_ns is not None and not incremental:
+            self._fetch_ts[which] = int(now_ns)
+
+    def _view_sessions(self, view_set, since=None, session_filter=None, whitelist=True, blacklist=True, keep=None,
+                       overlay_host_ok=False):
+        """The SessionInfo list of every getter, from one view export: the flows of view_set that pass
+        session_filter and changed since `since` (None: all of them), without the rows keep(views) drops, joined by
+        views_to_sessions -- status and time fields on a timed capture only, the whitelist byte / blacklist mask
+        decoded as asked -- then the host's whitelist verdicts and the anomaly tags merged in."""
+        if not self.flow_capacity:  # no table (the view export refuses such a context): no sessions
+            return []
+        views = self.export_view(view_set, since, session_filter)
+        if keep is not None and len(views):
+            views = views[keep(views)]
+        out = views_to_sessions(views, self.histories if self.track_history else None, self._bl_names, timed=self.timed,
+                                whitelist=whitelist, blacklist=blacklist, domains=self._domains())
+        for info in out if (overlay_host_ok and self._wl_host_ok) else ():  # the flows the pass left to the host
+            if info.session in self._wl_host_ok and info.is_whitelisted is WhitelistState.NonConforming:
+                info.is_whitelisted = WhitelistState.Conforming
+        return self._merge_anomaly(out, views["rec"], views["an"])
 
     def update_sessions_status(self, now_ns, purge=True, activity_s=60, current_s=180, retention_s=86400):
         """update_sessions_status (src/capture.rs:1497-1551) at `now_ns` on the capture timestamps'
@@ -585,7 +610,7 @@ class FlodbaddGpuCapture:
                                         None))
         if self.track_history:
             self._follow_growth()
-        return {k: int(st[0][k]) for k in N.AGE_STATS_FIELDS}
+        return stats_dict(st, N.AGE_STATS_FIELDS)
 
     def get_sessions(self, now_ns=None, incremental=False):
         """get_sessions (src/capture.rs:1578-1612): the sessions that pass the CURRENT filter,
@@ -594,31 +619,12 @@ class FlodbaddGpuCapture:
         table is aged first, as the reference does on every query (capture.rs:1581).  incremental
         (capture.rs:1583-1621): only the sessions modified since this getter's last full fetch with a
         now_ns, from one view export; a full fetch with now_ns moves that timestamp, nothing else does."""
-        since = self._incremental("sessions") if incremental else None
+        since = self._since("sessions", incremental)
         if now_ns is not None:
             self.update_sessions_status(now_ns)
-        if incremental:
-            views = self.export_view(N.FB_VIEW_ALL, since, self.filter)
-            out = views_to_sessions(views, self.histories if self.track_history else None, self._bl_names,
-                                    whitelist=bool(self._wl_name or self._bl_marked), blacklist=self._bl_ran,
-                                    domains=self._domains())
-            return self._merge_anomaly(self._overlay_host_ok(out), views["rec"], views)
-        if now_ns is not None:
-            self._fetch_ts["sessions"] = int(now_ns)
-        flows = self.export_flows(self.filter)
-        out = flows_to_sessions(flows, self.histories if self.track_history else None,
-                                times=self.export_times() if self.timed else None,
-                                status=self.status_bytes() if self.timed else None,
-                                whitelist=self.whitelist_bytes() if (self._wl_name or self._bl_marked) else None,
-                                blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None,
-                                modified=self._modified(), domains=self._domains())
-        return self._merge_anomaly(self._overlay_host_ok(out), flows)
-
-    def _overlay_host_ok(self, out):
-        for info in out if self._wl_host_ok else ():  # the host's verdict for the flows the pass left to it
-            if info.session in self._wl_host_ok and info.is_whitelisted is WhitelistState.NonConforming:
-                info.is_whitelisted = WhitelistState.Conforming
-        return out
+        self._fetched("sessions", now_ns, incremental)
+        return self._view_sessions(N.FB_VIEW_ALL, since, self.filter, whitelist=bool(self._wl_name or self._bl_marked),
+                                   blacklist=self._bl_ran, overlay_host_ok=True)
 
     def get_current_sessions(self, now_ns=None, incremental=False):
         """get_current_sessions (src/capture.rs:1624-1670): the members of current_sessions -- activity
@@ -627,24 +633,11 @@ class FlodbaddGpuCapture:
         getter's own fetch timestamp (capture.rs:1629-1666)."""
         if not self.timed:
             raise ValueError("current sessions need a timed capture (timed=True)")
-        since = self._incremental("current") if incremental else None
+        since = self._since("current", incremental)
         if now_ns is not None:
             self.update_sessions_status(now_ns)
-        if incremental:
-            views = self.export_view(N.FB_VIEW_CURRENT, since, self.filter)
-            out = views_to_sessions(views, self.histories if self.track_history else None, self._bl_names,
-                                    whitelist=False, blacklist=self._bl_ran, domains=self._domains())
-            return self._merge_anomaly(out, views["rec"], views)
-        if now_ns is not None:
-            self._fetch_ts["current"] = int(now_ns)
-        flows, status = self.export_flows(self.filter), self.status_bytes()
-        b = status[flows["slot"]] if len(flows) else np.zeros(0, dtype=np.uint8)
-        flows = flows[(b == 0) | ((b & N.STATUS_CURRENT) != 0)]
-        out = flows_to_sessions(flows, self.histories if self.track_history else None, times=self.export_times(),
-                                status=status,
-                                blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None,
-                                modified=self._modified(), domains=self._domains())
-        return self._merge_anomaly(out, flows)
+        self._fetched("current", now_ns, incremental)
+        return self._view_sessions(N.FB_VIEW_CURRENT, since, self.filter, whitelist=False, blacklist=self._bl_ran)
 
     # ---- new-session enrichment (src/packets.rs:429-485) -------------------------------------
     def set_asn_tables(self, v4, v6, records=None):
@@ -680,11 +673,7 @@ class FlodbaddGpuCapture:
 
     def enrich(self, new_only=False):
         """fb_flow_enrich_dev -> FLOW_ENRICH_DTYPE records (slot-keyed; join with export_flows)."""
-        cap = max(self.flow_count(), 1)
-        d_out, d_n = N.DeviceBuffer(cap * N.FLOW_ENRICH_DTYPE.itemsize), N.DeviceBuffer(8)
-        N.check(N.gpu_lib().fb_flow_enrich_dev(self.ctx, 1 if new_only else 0, d_out.ptr, cap, d_n.ptr, None))
-        m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
-        return d_out.download(np.zeros(cap, dtype=N.FLOW_ENRICH_DTYPE))[:m]
+        return self._compact_export("fb_flow_enrich_dev", [N.FLOW_ENRICH_DTYPE], 1 if new_only else 0)[0]
 
     # ---- blacklist pass (src/blacklists.rs:404-437, 456-731; src/capture.rs:1680-1783, 1850-1871) ---
     def set_custom_blacklists(self, blacklist_json):
@@ -709,7 +698,7 @@ class FlodbaddGpuCapture:
         st = np.zeros(1, dtype=N.BL_STATS_DTYPE)
         N.check(N.gpu_lib().fb_flow_blacklist(self.ctx, N.FB_BL_MARK_WHITELIST if mark_whitelist else 0, N.ptr(st),
                                               None))
-        out = {k: int(st[0][k]) for k in N.BL_STATS_FIELDS}
+        out = stats_dict(st, N.BL_STATS_FIELDS)
         self._bl_ran = True
         self._bl_marked = self._bl_marked or out["wl_marked"] > 0
         return out
@@ -717,48 +706,21 @@ class FlodbaddGpuCapture:
     def blacklist_masks(self):
         """fb_flow_blacklist_dev: the blacklist mask of every table slot (index = fb_flow_rec.slot,
         bit l = list l); all zero before the first pass."""
-        cap = int(self.table_info()["capacity"])
-        out = np.zeros(max(cap, 1), dtype=np.uint64)
-        if cap:
-            d = N.DeviceBuffer(cap * 8)
-            N.check(N.gpu_lib().fb_flow_blacklist_dev(self.ctx, d.ptr, cap, None))
-            d.download(out, cap * 8)
-        return out[:cap]
+        return self._plane("fb_flow_blacklist_dev", np.uint64)
 
     def export_blacklisted_flows(self):
         """fb_flow_export_blacklisted_dev: (the flows with a non-zero mask, their masks), slot order."""
-        cap = max(self.flow_count(), 1)
-        d_out, d_m, d_n = N.DeviceBuffer(cap * N.FLOW_REC_DTYPE.itemsize), N.DeviceBuffer(cap * 8), N.DeviceBuffer(8)
-        N.check(N.gpu_lib().fb_flow_export_blacklisted_dev(self.ctx, d_out.ptr, d_m.ptr, cap, d_n.ptr, None))
-        m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
-        return (d_out.download(np.zeros(cap, dtype=N.FLOW_REC_DTYPE))[:m],
-                d_m.download(np.zeros(cap, dtype=np.uint64))[:m])
+        return self._compact_export("fb_flow_export_blacklisted_dev", [N.FLOW_REC_DTYPE, np.uint64])
 
     def get_blacklisted_sessions(self, now_ns=None, incremental=False):
         """get_blacklisted_sessions(false) (src/capture.rs:1680-1719): after an update, the sessions of
         the blacklisted list as SessionInfo, in the order new_blacklisted_sessions.sort() leaves the
         keys (src/blacklists.rs:693).  incremental: as get_sessions, with this getter's own fetch timestamp
         (capture.rs:1688-1715)."""
-        since = self._incremental("blacklisted") if incremental else None
+        since = self._since("blacklisted", incremental)
         self.update_sessions(now_ns, *self._wl_inputs)
-        if incremental:
-            views = self.export_view(N.FB_VIEW_BLACKLISTED, since)
-            out = views_to_sessions(views, self.histories if self.track_history else None, self._bl_names,
-                                    timed=self.timed, whitelist=bool(self._wl_name or self._bl_marked),
-                                    domains=self._domains())
-            return self._merge_anomaly(out, views["rec"], views)
-        if now_ns is not None:
-            self._fetch_ts["blacklisted"] = int(now_ns)
-        flows, masks = self.export_blacklisted_flows()
-        if not len(flows):
-            return []
-        by_slot = {int(r["slot"]): m for r, m in zip(flows, masks)}
-        out = flows_to_sessions(flows, self.histories if self.track_history else None,
-                                times=self.export_times() if self.timed else None,
-                                status=self.status_bytes() if self.timed else None,
-                                whitelist=self.whitelist_bytes() if (self._wl_name or self._bl_marked) else None,
-                                blacklist=(by_slot, self._bl_names), modified=self._modified(), domains=self._domains())
-        return self._merge_anomaly(out, flows)
+        self._fetched("blacklisted", now_ns, incremental)
+        return self._view_sessions(N.FB_VIEW_BLACKLISTED, since, whitelist=bool(self._wl_name or self._bl_marked))
 
     def get_blacklisted_status(self, now_ns=None):
         """get_blacklisted_status (src/capture.rs:1762-1770): after an update, some session is blacklisted."""
@@ -808,40 +770,23 @@ class FlodbaddGpuCapture:
         """fb_flow_anomaly with the installed model -> the pass's counters (fb_an_stats)."""
         st = np.zeros(1, dtype=N.AN_STATS_DTYPE)
         N.check(N.gpu_lib().fb_flow_anomaly(self.ctx, 0, N.ptr(st), None))
-        return {k: int(st[0][k]) for k in N.AN_STATS_FIELDS}
+        return stats_dict(st, N.AN_STATS_FIELDS)
 
     def anomaly_records(self):
         """fb_flow_anomaly_dev: the AN_REC_DTYPE record of every table slot (index = fb_flow_rec.slot); all
         zero before the first pass."""
-        cap = int(self.table_info()["capacity"])
-        out = np.zeros(max(cap, 1), dtype=N.AN_REC_DTYPE)
-        if cap:
-            d = N.DeviceBuffer(cap * N.AN_REC_DTYPE.itemsize)
-            N.check(N.gpu_lib().fb_flow_anomaly_dev(self.ctx, d.ptr, cap, None))
-            d.download(out, cap * N.AN_REC_DTYPE.itemsize)
-        return out[:cap]
+        return self._plane("fb_flow_anomaly_dev", N.AN_REC_DTYPE)
 
     def export_features(self):
         """fb_flow_features_dev: (float64 [flows][10], their table slots) -- the training data."""
         if not self._an_codes:  # feature 7 reads the device's service codes: the defaults, unless a model brought its own
             N.check(N.gpu_lib().fb_set_service_codes(self.ctx, N.ptr(default_service_codes())))
             self._an_codes = True
-        cap = max(self.flow_count(), 1)
-        d_f, d_s, d_n = N.DeviceBuffer(cap * 8 * N.FB_AN_FEATURES), N.DeviceBuffer(cap * 4), N.DeviceBuffer(8)
-        N.check(N.gpu_lib().fb_flow_features_dev(self.ctx, d_f.ptr, d_s.ptr, cap, d_n.ptr, None))
-        m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
-        return (d_f.download(np.zeros((cap, N.FB_AN_FEATURES), dtype=np.float64))[:m],
-                d_s.download(np.zeros(cap, dtype=np.uint32))[:m])
+        return self._compact_export("fb_flow_features_dev", [(np.float64, (N.FB_AN_FEATURES,)), np.uint32])
 
     def export_anomalous_flows(self, min_level=N.FB_AN_SUSPICIOUS):
         """fb_flow_export_anomalous_dev: (the flows at min_level or above, their records)."""
-        cap = max(self.flow_count(), 1)
-        d_out, d_r, d_n = (N.DeviceBuffer(cap * N.FLOW_REC_DTYPE.itemsize), N.DeviceBuffer(cap * N.AN_REC_DTYPE.itemsize),
-                           N.DeviceBuffer(8))
-        N.check(N.gpu_lib().fb_flow_export_anomalous_dev(self.ctx, int(min_level), d_out.ptr, d_r.ptr, cap, d_n.ptr, None))
-        m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
-        return (d_out.download(np.zeros(cap, dtype=N.FLOW_REC_DTYPE))[:m],
-                d_r.download(np.zeros(cap, dtype=N.AN_REC_DTYPE))[:m])
+        return self._compact_export("fb_flow_export_anomalous_dev", [N.FLOW_REC_DTYPE, N.AN_REC_DTYPE], int(min_level))
 
     def analyze_sessions(self, now_ns=None):
         """SessionAnalyzer::analyze_sessions (src/analyzer.rs:1200-1570) over every session -- the consumer's
@@ -875,17 +820,16 @@ class FlodbaddGpuCapture:
         self._an_mode = "model"
         return self.anomaly_pass()
 
-    def _merge_anomaly(self, infos, flows, views=None):
+    def _merge_anomaly(self, infos, flows, recs):
         """The anomaly: tag of the last analysis merged into each SessionInfo's criticality; before any
-        analysis nothing changes.  A flow no pass has seen (inserted since) keeps what it has.  views: the
-        fb_flow_view records `flows` came from (their anomaly records are used instead of the plane's copy)."""
+        analysis nothing changes.  A flow no pass has seen (inserted since) keeps what it has.  flows: the
+        fb_flow_rec records the infos were made from; recs: their AN_REC_DTYPE records, recs[k] that of flows[k]."""
         if self._an_mode is None or not infos:
             return infos
         if self._an_mode == "model":
-            recs = self.anomaly_records() if views is None else {int(v["rec"]["slot"]): v["an"] for v in views}
-            slot = {Session.from_key(r): int(r["slot"]) for r in flows}
+            rec_of = {Session.from_key(r): rec for r, rec in zip(flows, recs)}
             for i in infos:
-                rec = recs[slot[i.session]]
+                rec = rec_of[i.session]
                 if rec["level"]:
                     i.criticality = merge_criticality(i.criticality, *anomaly_tag_of(rec))
         elif self._an_mode == "warming_up":
@@ -900,18 +844,11 @@ class FlodbaddGpuCapture:
 
     def get_anomalous_sessions(self, now_ns=None):
         """get_anomalous_sessions: the suspicious and abnormal sessions of the last analysis as SessionInfo,
-        in Session order."""
+        in Session order, each as get_sessions reports it."""
         if self._an_mode != "model":
             return []
-        flows, _ = self.export_anomalous_flows(N.FB_AN_SUSPICIOUS)
-        if not len(flows):
-            return []
-        out = flows_to_sessions(flows, self.histories if self.track_history else None,
-                                times=self.export_times() if self.timed else None,
-                                status=self.status_bytes() if self.timed else None,
-                                whitelist=self.whitelist_bytes() if (self._wl_name or self._bl_marked) else None,
-                                blacklist=(self.blacklist_masks(), self._bl_names) if self._bl_ran else None)
-        return self._merge_anomaly(out, flows)
+        return self._view_sessions(N.FB_VIEW_ANOMALOUS, whitelist=bool(self._wl_name or self._bl_marked),
+                                   blacklist=self._bl_ran)
 
     def get_anomalous_status(self):
         """get_anomalous_status: some session of the last analysis is suspicious or abnormal."""
@@ -958,25 +895,14 @@ class FlodbaddGpuCapture:
         self._wl_installed = None
         self._wl_host_ok = set()
         self._wl_conformance = True
-        self._wl_exceptions = np.zeros(0, dtype=N.FLOW_REC_DTYPE)
 
     def whitelist_bytes(self):
         """fb_flow_whitelist_dev: the whitelist state byte of every table slot (index = fb_flow_rec.slot)."""
-        cap = int(self.table_info()["capacity"])
-        out = np.zeros(max(cap, 1), dtype=np.uint8)
-        if cap:
-            d = N.DeviceBuffer(cap)
-            N.check(N.gpu_lib().fb_flow_whitelist_dev(self.ctx, d.ptr, cap, None))
-            d.download(out, cap)
-        return out[:cap]
+        return self._plane("fb_flow_whitelist_dev", np.uint8)
 
     def export_whitelist_flows(self, state_mask):
         """fb_flow_export_whitelist_dev: the flows whose state byte has a bit of state_mask, slot order."""
-        cap = max(self.flow_count(), 1)
-        d_out, d_n = N.DeviceBuffer(cap * N.FLOW_REC_DTYPE.itemsize), N.DeviceBuffer(8)
-        N.check(N.gpu_lib().fb_flow_export_whitelist_dev(self.ctx, int(state_mask), d_out.ptr, cap, d_n.ptr, None))
-        m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
-        return d_out.download(np.zeros(cap, dtype=N.FLOW_REC_DTYPE))[:m]
+        return self._compact_export("fb_flow_export_whitelist_dev", [N.FLOW_REC_DTYPE], int(state_mask))[0]
 
     def install_whitelist(self, compiled):
         """fb_set_whitelist with a CompiledWhitelist (or bare WL_ENDPOINT_DTYPE rows)."""
@@ -991,12 +917,11 @@ class FlodbaddGpuCapture:
         """fb_flow_whitelist: one pass over the table -> the call's counters (fb_wl_stats)."""
         st = np.zeros(1, dtype=N.WL_STATS_DTYPE)
         N.check(N.gpu_lib().fb_flow_whitelist(self.ctx, 0, N.ptr(st), None))
-        return {k: int(st[0][k]) for k in N.WL_STATS_FIELDS}
+        return stats_dict(st, N.WL_STATS_FIELDS)
 
-    def _dst_asn(self, flows):
-        """SessionInfo.dst_asn of flow records (src/packets.rs:468-485): Db::lookup of the destination
-        on the GPU unless it is a LAN address -> [(as_number, country, owner) or None]."""
-        ips = [Session.from_key(r).dst_ip for r in flows]
+    def _dst_asn(self, ips):
+        """SessionInfo.dst_asn of destination addresses (src/packets.rs:468-485): Db::lookup on the GPU
+        unless it is a LAN address -> [(as_number, country, owner) or None]."""
         rec = self.ip_lookup(ips)[0] if ips else []
         return [None if (int(k) < 0 or int(k) >= len(self._asn_records) or is_lan_ip(ip, self._lan_v6))
                 else self._asn_records[int(k)] for ip, k in zip(ips, rec)]
@@ -1023,18 +948,14 @@ class FlodbaddGpuCapture:
         stats = self.whitelist_pass()
         self._wl_host_ok = set()
         if process_names and stats["host_check"]:
-            marked = self.export_whitelist_flows(N.FB_WL_HOST_CHECK)
-            for r, asn in zip(marked, self._dst_asn(marked)):
-                s = Session.from_key(r)
+            marked = [Session.from_key(r) for r in self.export_whitelist_flows(N.FB_WL_HOST_CHECK)]
+            for s, asn in zip(marked, self._dst_asn([s.dst_ip for s in marked])):
                 a = asn or (None, None, None)
                 if is_session_in_whitelist(comp.endpoints, comp.name, want.get(str(s.dst_ip)), str(s.dst_ip), s.dst_port,
                                            s.protocol.name, a[0], a[1], a[2], process_names.get(s))[0]:
                     self._wl_host_ok.add(s)
         exc = self.export_whitelist_flows(N.FB_WL_NONCONFORMING)
-        if self._wl_host_ok and len(exc):
-            exc = exc[np.array([Session.from_key(r) not in self._wl_host_ok for r in exc], dtype=bool)]
-        self._wl_exceptions = exc
-        self._wl_conformance = len(exc) == 0
+        self._wl_conformance = not any(Session.from_key(r) not in self._wl_host_ok for r in exc)
         return stats
 
     def get_whitelist_conformance(self):
@@ -1047,44 +968,26 @@ class FlodbaddGpuCapture:
         SessionInfo, sorted by Session as new_exceptions.sort() leaves the keys (whitelists.rs:951),
         each with the reference's whitelist_reason.  With now_ns the pass stamps the sessions it changes
         with it; incremental: as get_sessions, with this getter's own fetch timestamp (capture.rs:1729-1756).
-        The host's verdict for a host-check flow (process names) applies in both paths and stamps nothing."""
-        since = self._incremental("exceptions") if incremental else None
+        The host's verdict for a host-check flow (process names) applies to full and incremental fetches alike
+        and stamps nothing."""
+        since = self._since("exceptions", incremental)
         if now_ns is not None:
             self.set_pass_time(now_ns)
         self.update_whitelist(*self._wl_inputs)
-        views = None
-        if incremental:
-            views = self.export_view(N.FB_VIEW_WL_EXCEPTIONS, since) if self._wl_name \
-                else np.zeros(0, dtype=N.FLOW_VIEW_DTYPE)
-            if self._wl_host_ok and len(views):
-                views = views[np.array([Session.from_key(r) not in self._wl_host_ok for r in views["rec"]], dtype=bool)]
-            exc = np.ascontiguousarray(views["rec"])
-        else:
-            if now_ns is not None:
-                self._fetch_ts["exceptions"] = int(now_ns)
-            exc = self._wl_exceptions
-        if not len(exc):
+        self._fetched("exceptions", now_ns, incremental)
+        if not self._wl_name:  # no list is active: no exceptions, whatever the blacklist fallback marked
             return []
+        host_ok = self._wl_host_ok  # (the sessions the host resolved to Conforming are no exceptions)
+        keep = (lambda v: np.array([Session.from_key(r) not in host_ok for r in v["rec"]], dtype=bool)) if host_ok else None
+        out = self._view_sessions(N.FB_VIEW_WL_EXCEPTIONS, since, whitelist=False, blacklist=False, keep=keep)
         proc = self._wl_inputs[1] or {}
         comp, dns = self._wl_installed  # (the resolutions the installed list was compiled with)
-        reasons = {}
-        for r, asn in zip(exc, self._dst_asn(exc)):
-            s = Session.from_key(r)
-            a = asn or (None, None, None)
+        for info, asn in zip(out, self._dst_asn([i.session.dst_ip for i in out])):
+            s, a = info.session, asn or (None, None, None)
             # (an exception is a session no endpoint matched: the reason needs no second scan of the list)
-            reasons[s] = no_match_reason(comp.endpoints, comp.name, dns.get(str(s.dst_ip)), str(s.dst_ip), s.dst_port,
-                                         s.protocol.name, a[0], a[1], a[2], proc.get(s))
-        if views is not None:
-            out = views_to_sessions(views, self.histories if self.track_history else None, whitelist=False,
-                                    blacklist=False, domains=self._domains())
-        else:
-            out = flows_to_sessions(exc, self.histories if self.track_history else None,
-                                    times=self.export_times() if self.timed else None,
-                                    status=self.status_bytes() if self.timed else None, modified=self._modified(),
-                                    domains=self._domains())
-        for info in out:
             info.is_whitelisted = WhitelistState.NonConforming
-            info.whitelist_reason = reasons[info.session]
+            info.whitelist_reason = no_match_reason(comp.endpoints, comp.name, dns.get(str(s.dst_ip)), str(s.dst_ip),
+                                                    s.dst_port, s.protocol.name, a[0], a[1], a[2], proc.get(s))
         return out
 
     def create_custom_whitelists(self, dns_resolutions=None, process_names=None):
@@ -1099,7 +1002,6 @@ class FlodbaddGpuCapture:
         N.check(N.gpu_lib().fb_stream_sync(None))
         self.histories = {}
         self._wl_host_ok = set()
-        self._wl_exceptions = np.zeros(0, dtype=N.FLOW_REC_DTYPE)
         self._bl_marked = False
         self._dom_ran = False
 

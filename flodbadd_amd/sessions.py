@@ -324,6 +324,62 @@ def histories_from_records(recs):
     return {k: (h, state.get(k)) for k, h in hist.items()}
 
 
+def _per_record(plane, slots):
+    """A per-slot argument of flows_to_sessions -- an array indexed by slot or {slot: value}; None stays None --
+    as one value per record: row k is that of the flow in slots[k]."""
+    if plane is None:
+        return None
+    if isinstance(plane, dict):
+        return [plane[s] for s in slots.tolist()]
+    return np.asarray(plane)[slots].tolist()
+
+
+def _join(flows, histories, times=None, status=None, whitelist=None, masks=None, bl_names=(), stamps=None,
+          dom_ids=None, dom_names=None):
+    """The join behind flows_to_sessions and views_to_sessions, over per-record columns: row k of every column
+    that is not None belongs to flows[k].  times: FLOW_TIME_DTYPE records; status / whitelist: bytes; masks:
+    blacklist mask words of the lists bl_names; stamps: fb_flow_modified_dev stamps; dom_ids: (src, dst) name-id
+    pairs into dom_names."""
+    from .enrich import criticality_of  # (enrich imports this module)
+    none = lambda v: None if int(v) == FB_SEEN_NONE else int(v)  # noqa: E731
+    out = []
+    for k, r in enumerate(flows):
+        st = SessionStats(int(r["inbound_bytes"]), int(r["outbound_bytes"]), int(r["orig_pkts"]),
+                          int(r["resp_pkts"]), int(r["orig_ip_bytes"]), int(r["resp_ip_bytes"]),
+                          histories.get(int(r["slot"]), "") if histories is not None else "",
+                          CONN_STATES[int(r["conn_state"])], int(r["first_seen"]), int(r["last_seen"]),
+                          none(r["end_seen"]), int(r["hist_len"]), int(r["segment_count"]), bool(r["in_segment"]))
+        if times is not None:
+            t = times[k]
+            st.start_time_ns, st.last_activity_ns = int(t["start_time_ns"]), int(t["last_activity_ns"])
+            st.end_time_ns, st.last_segment_end_ns = none(t["end_time_ns"]), none(t["last_segment_end_ns"])
+            st.current_segment_start_ns = int(t["current_segment_start_ns"])
+            st.total_segment_interarrival_ms = int(t["total_segment_interarrival_ms"])
+            st.segment_interarrival_div = int(t["segment_interarrival_div"])
+        s = Session.from_key(r)
+        f = int(r["session_flags"])
+        svc = (service_name(s.dst_port) or str(s.dst_port)) if f & SESSION_DST_SERVICE else None
+        info = SessionInfo(s, st, bool(f & SESSION_LOCAL_SRC), bool(f & SESSION_LOCAL_DST),
+                           bool(f & SESSION_SELF_SRC), bool(f & SESSION_SELF_DST), svc)
+        if status is not None:
+            info.status = SessionStatus.from_byte(status[k])
+        if whitelist is not None:
+            b = int(whitelist[k])
+            info.is_whitelisted = WhitelistState.from_byte(b)
+            if b & FB_WL_BLACKLISTED:
+                info.whitelist_reason = "Session is blacklisted"
+        if masks is not None:
+            info.criticality = criticality_of(masks[k], bl_names)
+        info.last_modified_ns = max(st.last_activity_ns or 0, int(stamps[k]) if stamps is not None else 0)
+        if dom_ids is not None:
+            src, dst = int(dom_ids[k][0]), int(dom_ids[k][1])
+            info.src_domain = dom_names[src] if src else None
+            info.dst_domain = dom_names[dst] if dst else None
+        out.append(info)
+    out.sort(key=lambda i: i.session.sort_key())
+    return out
+
+
 def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=None, blacklist=None, modified=None,
                       domains=None):
     """fb_flow_rec records -> SessionInfo list sorted by the derived Ord of Session.  `histories`
@@ -341,77 +397,35 @@ def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=
     of every table slot (fb_flow_modified_dev); SessionInfo.last_modified_ns is the later of it and the
     flow's last_activity_ns.  `domains`: (the name-id pair of every table slot, fb_flow_domains_dev; {name id:
     str}), decoded into SessionInfo.src_domain / dst_domain (id 0: None).  The per-slot arguments may be arrays
-    indexed by slot or {slot: value}."""
-    from .enrich import criticality_of  # (enrich imports this module)
+    indexed by slot or {slot: value}.  Each argument's shape is decided here, once; the join itself (_join) runs
+    over per-record columns."""
     if flows.dtype != FLOW_REC_DTYPE:
         raise TypeError("expected fb_flow_rec records (FLOW_REC_DTYPE), got %s" % flows.dtype)
-    tmap = None
-    if times is not None:
-        if len(times) == len(flows) and (len(times) == 0 or not times["slot"].any()):
-            tmap = {i: t for i, t in enumerate(times)}
-        else:
-            tmap = {int(t["slot"]): t for t in times}
-    out = []
-    for idx, r in enumerate(flows):
-        end = int(r["end_seen"])
-        st = SessionStats(int(r["inbound_bytes"]), int(r["outbound_bytes"]), int(r["orig_pkts"]),
-                          int(r["resp_pkts"]), int(r["orig_ip_bytes"]), int(r["resp_ip_bytes"]),
-                          histories.get(int(r["slot"]), "") if histories is not None else "",
-                          CONN_STATES[int(r["conn_state"])], int(r["first_seen"]), int(r["last_seen"]),
-                          None if end == FB_SEEN_NONE else end, int(r["hist_len"]), int(r["segment_count"]),
-                          bool(r["in_segment"]))
-        if tmap is not None:
-            t = tmap[idx] if (len(times) == len(flows) and (len(times) == 0 or not times["slot"].any())) \
-                else tmap[int(r["slot"])]
-            none = lambda v: None if int(v) == FB_SEEN_NONE else int(v)  # noqa: E731
-            st.start_time_ns, st.last_activity_ns = int(t["start_time_ns"]), int(t["last_activity_ns"])
-            st.end_time_ns, st.last_segment_end_ns = none(t["end_time_ns"]), none(t["last_segment_end_ns"])
-            st.current_segment_start_ns = int(t["current_segment_start_ns"])
-            st.total_segment_interarrival_ms = int(t["total_segment_interarrival_ms"])
-            st.segment_interarrival_div = int(t["segment_interarrival_div"])
-        s = Session.from_key(r)
-        f = int(r["session_flags"])
-        svc = (service_name(s.dst_port) or str(s.dst_port)) if f & SESSION_DST_SERVICE else None
-        info = SessionInfo(s, st, bool(f & SESSION_LOCAL_SRC), bool(f & SESSION_LOCAL_DST),
-                           bool(f & SESSION_SELF_SRC), bool(f & SESSION_SELF_DST), svc)
-        if status is not None:
-            info.status = SessionStatus.from_byte(status[int(r["slot"])])
-        if whitelist is not None:
-            b = int(whitelist[int(r["slot"])])
-            info.is_whitelisted = WhitelistState.from_byte(b)
-            if b & FB_WL_BLACKLISTED:
-                info.whitelist_reason = "Session is blacklisted"
-        if blacklist is not None:
-            info.criticality = criticality_of(blacklist[0][int(r["slot"])], blacklist[1])
-        info.last_modified_ns = max(st.last_activity_ns or 0, int(modified[int(r["slot"])]) if modified is not None else 0)
-        if domains is not None:
-            ids = domains[0][int(r["slot"])]
-            info.src_domain = domains[1][int(ids[0])] if int(ids[0]) else None
-            info.dst_domain = domains[1][int(ids[1])] if int(ids[1]) else None
-        out.append(info)
-    out.sort(key=lambda i: i.session.sort_key())
-    return out
+    slots = flows["slot"]
+    if times is not None and not (len(times) == len(flows) and not times["slot"].any()):
+        row = {s: k for k, s in enumerate(times["slot"].tolist())}
+        times = times[np.array([row[s] for s in slots.tolist()], dtype=np.intp)]
+    bl_masks, bl_names = blacklist if blacklist is not None else (None, ())
+    dom_ids, dom_names = domains if domains is not None else (None, None)
+    return _join(flows, histories, times, _per_record(status, slots), _per_record(whitelist, slots),
+                 _per_record(bl_masks, slots), bl_names, _per_record(modified, slots), _per_record(dom_ids, slots), dom_names)
 
 
 def views_to_sessions(views, histories=None, bl_names=None, timed=True, status=True, whitelist=True, blacklist=True,
                       domains=None):
     """fb_flow_view records (fb_flow_export_view) -> the SessionInfo list flows_to_sessions builds from the
-    separate exports: each view carries its flow's record, time record and per-slot plane elements, so no
-    other export is needed.  timed: the capture is timed (else the time records are zero and left out);
-    status / whitelist / blacklist: decode that plane's element (a getter that does not hand
-    flows_to_sessions a plane passes False here); bl_names: the list names of the blacklist masks; domains: as
+    separate exports: each view carries its flow's record, time record and per-slot plane elements -- a view row
+    is the per-record join already -- so no other export is needed.  timed: the capture is timed (else the time
+    records are zero and left out); status / whitelist / blacklist: decode that plane's element (a getter that
+    does not decode a plane passes False here); bl_names: the list names of the blacklist masks; domains: as
     flows_to_sessions takes it, joined by slot (the view record itself carries no domain)."""
-    views = np.ascontiguousarray(views)
     if views.dtype != FLOW_VIEW_DTYPE:
         raise TypeError("expected fb_flow_view records (FLOW_VIEW_DTYPE), got %s" % views.dtype)
-    flows = np.ascontiguousarray(views["rec"])
-    slots = flows["slot"].tolist()
-    by_slot = lambda f: dict(zip(slots, views[f].tolist()))  # noqa: E731
-    return flows_to_sessions(flows, histories, times=np.ascontiguousarray(views["time"]) if timed else None,
-                             status=by_slot("status") if (status and timed) else None,
-                             whitelist=by_slot("wl_state") if whitelist else None,
-                             blacklist=(by_slot("bl_mask"), bl_names or []) if blacklist else None,
-                             modified=by_slot("stamp_ns"), domains=domains)
+    col = lambda f, on=True: views[f].tolist() if on else None  # noqa: E731
+    dom_ids, dom_names = domains if domains is not None else (None, None)
+    return _join(views["rec"], histories, views["time"] if timed else None, col("status", status and timed),
+                 col("wl_state", whitelist), col("bl_mask", blacklist), bl_names or [], col("stamp_ns"),
+                 _per_record(dom_ids, views["rec"]["slot"]), dom_names)
 
 
 def filter_sessions(sessions: List[SessionInfo], flt: SessionFilter, lan_v6=()) -> List[SessionInfo]:

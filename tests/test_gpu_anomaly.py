@@ -11,6 +11,7 @@ import pytest
 
 import anforests as F
 import anref
+import joinref
 from flodbadd_amd import _native as N
 from flodbadd_amd import analyzer as A
 from flodbadd_amd.capture import FlodbaddGpuCapture
@@ -413,6 +414,11 @@ def test_analyze_sessions_end_to_end():
         assert st == res["stats"] and min(st["normal"], st["suspicious"], st["abnormal"]) > 0
         anomalous = cap.get_anomalous_sessions()
         assert [i.session for i in anomalous] == res["anomalous"] and cap.get_anomalous_status() is True
+        # each one as get_sessions reports it, field for field; every flow's tag changed in the pass at now + 30 s
+        # (the packets are near T0), so that pass's stamp -- or a later one's -- is its last_modified
+        everyone = {i.session: i for i in cap.get_sessions()}
+        assert anomalous and all(joinref.info_fields(i) == joinref.info_fields(everyone[i.session]) for i in anomalous)
+        assert all(i.last_modified_ns >= now + 30 * S for i in anomalous)
         assert [i.criticality for i in anomalous] == [res["criticality"][s] for s in res["anomalous"]]
         assert all(("anomaly:suspicious/" in i.criticality) or ("anomaly:abnormal/" in i.criticality) for i in anomalous)
         assert {i.session: i.criticality for i in cap.get_current_sessions()} == res["criticality"]

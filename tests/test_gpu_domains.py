@@ -13,6 +13,7 @@ import dnsgen as G
 import dnstrackgen as T
 import domref
 import framegen as fg
+import joinref
 from flodbadd_amd import _native as N
 from flodbadd_amd.capture import FlodbaddGpuCapture
 from flodbadd_amd.dns import DnsResolver
@@ -172,6 +173,13 @@ def test_current_only_and_incremental_sessions():
         assert all(i.dst_domain == "one.example" and i.src_domain is None and i.last_modified_ns == t1 + S for i in inc)
         cur = cap.get_current_sessions(incremental=True)
         assert len(cur) == 20 and sum(1 for i in cur if i.dst_domain) == 10
+        # the full fetches against the separate exports joined on the host, domains included
+        full = cap.get_sessions()
+        joinref.assert_same(full, joinref.sessions(cap, "sessions"), "sessions")
+        assert len(full) == 40 and sum(1 for i in full if i.dst_domain) == 10
+        full = cap.get_current_sessions()
+        joinref.assert_same(full, joinref.sessions(cap, "current"), "current")
+        assert [info.__dict__ for info in full] == [info.__dict__ for info in cur]
     finally:
         cap.close()
 

@@ -3,7 +3,8 @@ flodbadd_amd/csrc/fb_view.hip and the stamped instances of the three pass kernel
 
 The view is compared, byte for byte and for every flow, with the join by slot of the exports that existed
 before it (flow records, time records, the status / whitelist / blacklist / anomaly planes) plus the raw
-stamps; the stamps with what the passes report as changed; the Python getters with tests/modref.py.  No
+stamps; the stamps with what the passes report as changed; the Python getters with tests/modref.py and, field
+for field, with tests/joinref.py -- the same join done on the host from the separate exports.  No
 tolerance applies anywhere: every value is an integer or a copied record.  Tables are 2^12 slots with about
 700 flows, so the sweep's 256-slot steps are partly selected."""
 import ctypes as C
@@ -14,6 +15,7 @@ import json
 import numpy as np
 import pytest
 
+import joinref
 import modref
 from flodbadd_amd import _native as N
 from flodbadd_amd import analyzer as AN
@@ -544,11 +546,17 @@ def test_reference_incremental_scenarios(getter):
         w.cap.close()
 
 
-def info_fields(i):
-    d = dict(i.__dict__)
-    d["stats"] = dict(i.stats.__dict__)
-    d["status"] = None if i.status is None else dict(i.status.__dict__)
-    return d
+info_fields = joinref.info_fields
+
+
+def wl_doc(eps):
+    return json.dumps({"date": "today", "signature": None, "whitelists": [
+        {"name": "custom_whitelist", "extends": None, "endpoints": eps}]})
+
+
+def exact_endpoints(rows):
+    return [{"ip": str(Session.from_key(r).dst_ip), "port": int(r["dst_port"]), "protocol": Protocol(int(r["protocol"])).name}
+            for r in rows]
 
 
 def test_incremental_before_any_full_fetch_equals_the_full_fetch():
@@ -559,11 +567,7 @@ def test_incremental_before_any_full_fetch_equals_the_full_fetch():
         for r in fl:
             ref.packet(tuple_of(Session.from_key(r)), tm[int(r["slot"])])
         now = T0 + 100 * S
-        rows = cap.export_flows()[::2]
-        eps = [{"ip": str(Session.from_key(r).dst_ip), "port": int(r["dst_port"]), "protocol": Protocol(int(r["protocol"])).name}
-               for r in rows]
-        cap.set_custom_whitelists(json.dumps({"date": "today", "signature": None, "whitelists": [
-            {"name": "custom_whitelist", "extends": None, "endpoints": eps}]}))   # pass time 0: no stamps
+        cap.set_custom_whitelists(wl_doc(exact_endpoints(cap.export_flows()[::2])))   # pass time 0: no stamps
         cap.set_pass_time(now)
         cap.set_custom_blacklists(json.dumps(L1))                # stamps the flows whose mask it sets
         cap.set_filter(SessionFilter.GlobalOnly)
@@ -575,6 +579,10 @@ def test_incremental_before_any_full_fetch_equals_the_full_fetch():
             assert cap._fetch_ts[name] == 0
             assert len(inc) == len(full) > 20, name
             assert [info_fields(i) for i in inc] == [info_fields(i) for i in full], name
+            want = joinref.sessions(cap, name)                   # the separate exports, joined on the host
+            assert len(want) == len(full)
+            joinref.assert_same(inc, want, (name, "incremental"))
+            joinref.assert_same(full, want, (name, "full"))
         cap.set_filter(SessionFilter.All)
         # last_modified_ns against the restatement: the list change above ran under `now`
         ref.set_pass_time(now)
@@ -588,3 +596,70 @@ def test_incremental_before_any_full_fetch_equals_the_full_fetch():
         assert cap.get_sessions(incremental=True) == [] and len(cap.get_current_sessions(incremental=True)) == NFLOWS
     finally:
         cap.close()
+
+
+@pytest.mark.parametrize("timed", [True, False], ids=["timed", "untimed"])
+def test_getters_equal_the_join_of_the_separate_exports(timed):
+    """Every getter's full fetch (timed: its first incremental fetch too) against tests/joinref.py, field for
+    field, under both filters, before and after an analysis, and with host verdicts (process names)."""
+    cap = dressed_cap(timed)
+    try:
+        flows = cap.export_flows()
+        # exact endpoints for every other flow, and a process endpoint that leaves the other port-22 flows to the host
+        cap.set_custom_whitelists(wl_doc(exact_endpoints(flows[::2]) + [{"process": "curl", "port": 22, "protocol": "TCP"}]))
+        fns = {"sessions": cap.get_sessions, "current": cap.get_current_sessions, "blacklisted": cap.get_blacklisted_sessions,
+               "exceptions": cap.get_whitelist_exceptions, "anomalous": cap.get_anomalous_sessions}
+        if not timed:
+            with pytest.raises(ValueError):
+                cap.get_current_sessions()
+            del fns["current"]
+
+        def compare(names, incremental=False):
+            sizes = {}
+            for name in names:
+                got = fns[name](incremental=True) if incremental else fns[name]()
+                want = joinref.sessions(cap, name)               # (after the getter: it reads what its passes left)
+                joinref.assert_same(got, want, (name, timed, cap._an_mode, int(cap.filter), incremental))
+                sizes[name] = len(got)
+            print("getter sizes:", timed, cap._an_mode, cap.filter.name, sizes)
+            assert all(n > 0 for n in sizes.values()), sizes
+            return sizes
+
+        assert cap._an_mode is None and cap.get_anomalous_sessions() == []      # a model on the device, no analysis yet
+        for flt in (SessionFilter.GlobalOnly, SessionFilter.All):
+            cap.set_filter(flt)
+            compare([n for n in fns if n != "anomalous"])
+            assert not any("anomaly:" in i.criticality for i in cap.get_sessions())
+        cap._an_mode = "model"                                   # what analyze_sessions leaves after its device pass
+        for flt in (SessionFilter.GlobalOnly, SessionFilter.All):
+            cap.set_filter(flt)
+            sizes = compare(fns)
+            assert 0 < sizes["anomalous"] < NFLOWS and 0 < sizes["exceptions"] < NFLOWS and 0 < sizes["blacklisted"] < NFLOWS
+            assert (sizes["sessions"] == NFLOWS) == (flt == SessionFilter.All)
+            if timed:
+                assert 0 < sizes["current"] < sizes["sessions"]
+                assert compare([n for n in fns if n != "anomalous"], incremental=True) == {k: v for k, v in sizes.items() if k != "anomalous"}
+        got = cap.get_sessions()
+        assert all("anomaly:" in i.criticality for i in got) and any("blacklist:" in i.criticality for i in got)
+        # host verdicts: curl owns some of the flows the pass left to the host; they stop being exceptions
+        before = {i.session for i in cap.get_whitelist_exceptions()}
+        left = sorted(s for s in before if s.dst_port == 22)
+        assert len(left) > 20
+        cap.update_whitelist(None, {s: "curl" for s in left[::2]})
+        assert cap._wl_host_ok == set(left[::2])
+        sizes = compare(["sessions", "exceptions"])
+        assert sizes["exceptions"] == len(before) - len(cap._wl_host_ok) > 0
+        assert not {i.session for i in cap.get_whitelist_exceptions()} & cap._wl_host_ok
+        by_key = {i.session: i for i in cap.get_sessions()}
+        assert all(by_key[s].is_whitelisted.name == "Conforming" for s in cap._wl_host_ok)
+        assert cap.get_whitelist_conformance() is False
+    finally:
+        cap.close()
+
+
+def test_a_capture_without_a_table_has_no_sessions():
+    bare = FlodbaddGpuCapture(0, flow_capacity=0)
+    try:
+        assert bare.get_sessions() == []
+    finally:
+        bare.close()
