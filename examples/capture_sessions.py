@@ -14,7 +14,9 @@ libpcap does on loopback, so each injected frame is seen once.  Traffic: `--pack
 frames injected on `lo` through a second AF_PACKET socket, `--flows` client ports against
 127.0.0.1:8080 in both directions with SYN / SYN|ACK / ACK / PSH|ACK / FIN|ACK flags.  The captured
 batch goes through the GPU path (`FlodbaddGpuCapture.process_frames`: parse + classify + session
-table upsert); `--capture-only` skips the GPU (e.g. to write the batch with `--save`).
+table upsert); `--capture-only` skips the GPU (e.g. to write the batch with `--save`).  `--zeek` makes
+the capture timed (each frame's receive time is its capture timestamp) and prints the sessions as
+Zeek conn.log lines, the text of the reference's `format_sessions_zeek`, formatted on the GPU.
 """
 import argparse
 import os
@@ -57,9 +59,10 @@ def frame(seq, n_flows):
     return b"\0" * 12 + b"\x08\x00" + ip + tcp
 
 
-def capture_loopback(n_packets, n_flows, timeout=10.0):
+def capture_loopback(n_packets, n_flows, timeout=10.0, times=None):
     """Inject n_packets frames on lo and capture them back; returns (frames u8, offsets u32,
-    seconds from the first send to the last frame captured)."""
+    seconds from the first send to the last frame captured).  times: a list that receives each
+    captured frame's wall-clock time in ns (the capture timestamps of a timed capture)."""
     rx = socket.socket(socket.AF_PACKET, socket.SOCK_RAW, socket.htons(ETH_P_ALL))
     tx = socket.socket(socket.AF_PACKET, socket.SOCK_RAW, socket.htons(ETH_P_ALL))
     try:
@@ -84,6 +87,8 @@ def capture_loopback(n_packets, n_flows, timeout=10.0):
                 continue  # libpcap skips outgoing copies on loopback; other traffic is not ours
             buf += data
             offs.append(len(buf))
+            if times is not None:
+                times.append(time.time_ns())
             got += 1
         el = time.perf_counter() - t0
     finally:
@@ -98,9 +103,12 @@ def main():
     ap.add_argument("--flows", type=int, default=100)
     ap.add_argument("--save", default=None, help="write the captured batch (frames, offsets) as .npz")
     ap.add_argument("--capture-only", action="store_true", help="no GPU: capture (and --save) only")
+    ap.add_argument("--zeek", action="store_true",
+                    help="print the sessions as Zeek conn.log lines (format_sessions_zeek), formatted on the GPU")
     a = ap.parse_args()
+    times = [] if a.zeek else None
     try:
-        frames, offs, el = capture_loopback(a.packets, a.flows)
+        frames, offs, el = capture_loopback(a.packets, a.flows, times=times)
     except PermissionError as e:
         raise SystemExit("AF_PACKET capture on lo needs CAP_NET_RAW: %s" % e)
     n = len(offs) - 1
@@ -113,15 +121,21 @@ def main():
         return
     from flodbadd_amd.capture import FlodbaddGpuCapture
     from flodbadd_amd.sessions import SessionFilter
-    cap = FlodbaddGpuCapture(0, session_filter=SessionFilter.All, flow_capacity=1 << 16)
+    # (a conn.log line prints the session's start time and history: a timed capture that keeps the strings)
+    cap = FlodbaddGpuCapture(0, session_filter=SessionFilter.All, flow_capacity=1 << 16, timed=a.zeek, track_history=a.zeek)
     try:
         t0 = time.perf_counter()
-        r = cap.process_frames(frames, offs)
+        r = cap.process_frames(frames, offs, ts=np.array(times, dtype=np.uint64) if a.zeek else None)
         t1 = time.perf_counter()
         sessions = cap.get_sessions()  # before clearing: the reference's stop() clears them
         print("GPU parse + classify + session upsert: %d frames, %d session records in %.3f ms (host-inclusive)"
               % (n, len(r.records), (t1 - t0) * 1e3))
         print("Captured %d session(s)." % len(sessions))
+        if a.zeek:
+            from flodbadd_amd.sessions import ZEEK_HEADER
+            print(ZEEK_HEADER)
+            for line in cap.get_sessions_zeek().lines():
+                print(line)
         cap.clear_all_sessions()
     finally:
         cap.close()

@@ -112,6 +112,13 @@ VIEW_QUERY_DTYPE = np.dtype([("since_ns", "<u8"), ("set", "<u4"), ("filter", "<u
 assert FLOW_VIEW_DTYPE.itemsize == 256 and VIEW_QUERY_DTYPE.itemsize == 24
 FB_VIEW_ALL, FB_VIEW_CURRENT, FB_VIEW_BLACKLISTED, FB_VIEW_WL_EXCEPTIONS, FB_VIEW_ANOMALOUS = 0, 1, 2, 3, 4
 FB_VIEW_MODIFIED_SINCE = 1
+# fb_zeek_stats (fb_format_zeek_dev: one Zeek conn.log line per fb_flow_view, formatted on the device), the
+# longest line without its history, and the kernel's thresholds (fb_zeek.hip), for the tests at them: records
+# per workgroup step, the step bytes staged in LDS, the history length the wave copies together
+ZEEK_STATS_FIELDS = ["lines", "bytes", "lines_written", "ts_inexact", "hist_mismatch"]
+ZEEK_STATS_DTYPE = np.dtype([(f, "<u8") for f in ZEEK_STATS_FIELDS] + [("reserved", "<u8", (3,))])
+assert ZEEK_STATS_DTYPE.itemsize == 64
+FB_ZEEK_FIXED_MAX, FB_ZEEK_STEP, FB_ZEEK_STAGE_BYTES, FB_ZEEK_COOP_HIST = 312, 256, 40000, 64
 FB_SEGMENT_TIMEOUT_MS = 5000
 FB_CFG_TIMED = 2
 FB_QUEUE_SHARED = 1
@@ -236,7 +243,7 @@ class FbError(RuntimeError):
 # Every symbol include/flodbadd_gpu.h declares: (name, restype, argtypes).
 _P, _U32, _U64, _I = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 _PU32, _PU64 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
-FB_DEBUG_DENSE_STEAL_POLLS, FB_DEBUG_DENSE_OFFSET_SKEW, FB_DEBUG_VIEW_DIRECT = 1, 2, 3
+FB_DEBUG_DENSE_STEAL_POLLS, FB_DEBUG_DENSE_OFFSET_SKEW, FB_DEBUG_VIEW_DIRECT, FB_DEBUG_ZEEK_DIRECT = 1, 2, 3, 4
 
 GPU_SYMBOLS = [
     ("fb_abi_version", _U32, []),
@@ -347,6 +354,7 @@ GPU_SYMBOLS = [
     ("fb_flow_modified_dev", _I, [_P, _P, _U64, _P]),
     ("fb_flow_export_view_dev", _I, [_P, _P, _P, _U64, _P, _P]),
     ("fb_flow_export_view", _I, [_P, _P, _P, _U64, _PU64, _P]),
+    ("fb_format_zeek_dev", _I, [_P, _P, _U64, _P, _P, _U64, _P, _U64, _P, _P, _P]),
     ("fb_dns_track_enable", _I, [_P, _P]),
     ("fb_dns_track_clear", _I, [_P]),
     ("fb_dns_track_dev", _I, [_P, _P, _P, _P, _U32, _P, _P, _P, _P, _P]),

@@ -15,8 +15,8 @@ import ipaddress
 import numpy as np
 
 from . import _native as N
-from .sessions import (Session, SessionFilter, WhitelistState, flows_to_sessions, ip_to_words, is_lan_ip,
-                       views_to_sessions, words_to_ip)
+from .sessions import (ZEEK_HEADER, Session, SessionFilter, WhitelistState, flows_to_sessions, ip_to_words, is_lan_ip,
+                       pack_histories, views_to_sessions, words_to_ip)
 from .enrich import Blacklists
 from .analyzer import SessionAnalyzer, anomaly_tag_of, default_service_codes, merge_criticality, path_cut
 from .whitelists import Whitelists, is_session_in_whitelist, no_match_reason
@@ -52,6 +52,28 @@ class BatchResult:
 def stats_dict(arr, fields=N.STATS_FIELDS):
     """A one-record counters array (fb_batch_stats, or the record `fields` names) -> {field: int}."""
     return {k: int(arr[0][k]) for k in fields if not k.startswith("reserved")}
+
+
+class ZeekLog:
+    """What FlodbaddGpuCapture.export_zeek downloads: the conn.log text (uint8), the n + 1 line offsets
+    (line i is text[line_off[i]:line_off[i + 1]], '\\n' included) and the call's fb_zeek_stats."""
+
+    def __init__(self, text, line_off, stats):
+        self.text, self.line_off, self.stats = text, line_off, stats
+
+    def __len__(self):
+        return len(self.line_off) - 1
+
+    def lines(self):
+        """The lines as str, without their newlines, in the export's order (view order: Zeek logs are
+        unordered, so nothing is sorted)."""
+        return self.text.tobytes().decode("ascii").split("\n")[:-1] if len(self) else []
+
+    def write(self, path, header=True):
+        with open(path, "wb") as f:
+            if header:
+                f.write(ZEEK_HEADER.encode("ascii") + b"\n")
+            f.write(self.text.tobytes())
 
 
 class FlodbaddGpuCapture:
@@ -124,6 +146,8 @@ class FlodbaddGpuCapture:
         # incremental queries (src/capture.rs:411-426): the time of each getter's last full fetch (0: the
         # reference's epoch)
         self._fetch_ts = dict.fromkeys(("sessions", "current", "blacklisted", "exceptions"), 0)
+        # get_sessions_zeek's own fetch timestamp: a periodic exporter does not disturb get_sessions' increments
+        self._zeek_fetch_ts = 0
         # DNS tracker (src/dns.rs:16-121): names are immutable per id, so the strings are fetched once
         # ({id: str}); the resolutions are exported again only when the tracker's `writes` has moved
         self.track_dns = bool(track_dns)
@@ -542,21 +566,27 @@ class FlodbaddGpuCapture:
     def reset_fetch_timestamps(self):
         """reset_fetch_timestamps (src/capture.rs:411-426): every getter's next incremental fetch is full."""
         self._fetch_ts = dict.fromkeys(self._fetch_ts, 0)
+        self._zeek_fetch_ts = 0
 
     def modified_stamps(self):
         """fb_flow_modified_dev: the stamp of every table slot (index = fb_flow_rec.slot); all zero while no
         pass has run under a pass time."""
         return self._plane("fb_flow_modified_dev", np.uint64)
 
-    def export_view(self, view_set=N.FB_VIEW_ALL, since_ns=None, session_filter=None):
-        """fb_flow_export_view: the FLOW_VIEW_DTYPE records of the flows of `view_set` (N.FB_VIEW_*) that pass
-        session_filter evaluated now (None: every flow) and, with since_ns, whose last_modified_ns is later
-        than it (timed captures)."""
+    @staticmethod
+    def _view_query(view_set, since_ns, session_filter):
         q = np.zeros(1, dtype=N.VIEW_QUERY_DTYPE)
         q[0]["set"] = int(view_set)
         q[0]["filter"] = int(SessionFilter.All if session_filter is None else session_filter)
         if since_ns is not None:
             q[0]["flags"], q[0]["since_ns"] = N.FB_VIEW_MODIFIED_SINCE, int(since_ns)
+        return q
+
+    def export_view(self, view_set=N.FB_VIEW_ALL, since_ns=None, session_filter=None):
+        """fb_flow_export_view: the FLOW_VIEW_DTYPE records of the flows of `view_set` (N.FB_VIEW_*) that pass
+        session_filter evaluated now (None: every flow) and, with since_ns, whose last_modified_ns is later
+        than it (timed captures)."""
+        q = self._view_query(view_set, since_ns, session_filter)
         cnt = self.flow_count() if self.flow_capacity else 1
         out = np.zeros(max(cnt, 1), dtype=N.FLOW_VIEW_DTYPE)
         n = C.c_uint64(0)
@@ -638,6 +668,60 @@ class FlodbaddGpuCapture:
             self.update_sessions_status(now_ns)
         self._fetched("current", now_ns, incremental)
         return self._view_sessions(N.FB_VIEW_CURRENT, since, self.filter, whitelist=False, blacklist=self._bl_ran)
+
+    # ---- Zeek conn.log export (format_sessions_zeek, src/sessions.rs:694-774) ---------------------------
+    def export_zeek(self, view_set=N.FB_VIEW_ALL, since_ns=None, session_filter=None):
+        """The conn.log lines of the flows export_view(view_set, since_ns, session_filter) selects, formatted on
+        the device (fb_format_zeek_dev; timed captures): the view records stay in device memory, the history
+        strings are uploaded when track_history is set (else every history field is empty), and only the text,
+        its line offsets and the counters come back -> ZeekLog.  Lines are in view order.  The text buffer has
+        room for every line (FB_ZEEK_FIXED_MAX each, plus the history bytes), so there is no retry."""
+        lib = N.gpu_lib()
+        q = self._view_query(view_set, since_ns, session_filter)
+        cnt = self.flow_count() if self.flow_capacity else 0
+        d_views, d_n = N.DeviceBuffer(max(cnt, 1) * N.FLOW_VIEW_DTYPE.itemsize), N.DeviceBuffer(8)
+        N.check(lib.fb_flow_export_view_dev(self.ctx, N.ptr(q), d_views.ptr, cnt, d_n.ptr, None))
+        n = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cnt)
+        d_hist = d_hoff = None
+        n_slots = hist_bytes = 0
+        if self.track_history:
+            n_slots = int(self.table_info()["capacity"])
+            chars, off = pack_histories(self.histories, n_slots)
+            hist_bytes = len(chars)
+            d_hist, d_hoff = N.DeviceBuffer(max(hist_bytes, 1)), N.DeviceBuffer(off.nbytes)
+            if hist_bytes:
+                d_hist.upload(chars)
+            d_hoff.upload(off)
+        text_cap = n * N.FB_ZEEK_FIXED_MAX + hist_bytes
+        d_text, d_off, d_stats = N.DeviceBuffer(max(text_cap, 1)), N.DeviceBuffer(8 * (n + 1)), N.DeviceBuffer(64)
+        N.check(lib.fb_format_zeek_dev(self.ctx, d_views.ptr, n, d_hist.ptr if d_hist else None,
+                                       d_hoff.ptr if d_hoff else None, n_slots, d_text.ptr, text_cap, d_off.ptr,
+                                       d_stats.ptr, None))
+        st = stats_dict(d_stats.download(np.zeros(1, dtype=N.ZEEK_STATS_DTYPE)), N.ZEEK_STATS_FIELDS)
+        if st["hist_mismatch"]:
+            raise N.FbError(N.FB_ERR_INTERNAL, "%d flows whose history length differs from the table's hist_len"
+                            % st["hist_mismatch"])
+        if st["lines_written"] != n:
+            raise N.FbError(N.FB_ERR_INTERNAL, "%d of %d lines fit the text buffer" % (st["lines_written"], n))
+        line_off = d_off.download(np.zeros(n + 1, dtype=np.uint64))
+        text = np.zeros(st["bytes"], dtype=np.uint8)
+        if st["bytes"]:
+            d_text.download(text, st["bytes"])
+        return ZeekLog(text, line_off, st)
+
+    def get_sessions_zeek(self, now_ns=None, incremental=False):
+        """get_sessions as conn.log text: the flows that pass the current filter, the table aged first when
+        now_ns is given, incremental (timed captures) the flows modified since this getter's last full fetch
+        with a now_ns -> ZeekLog.  The getter has a fetch timestamp of its own, so a periodic exporter leaves
+        get_sessions' incremental state alone; reset_fetch_timestamps resets it too."""
+        if incremental and not self.timed:
+            raise ValueError("incremental fetches need a timed capture (timed=True): last_modified has no clock")
+        since = self._zeek_fetch_ts if incremental else None
+        if now_ns is not None:
+            self.update_sessions_status(now_ns)
+            if not incremental:
+                self._zeek_fetch_ts = int(now_ns)
+        return self.export_zeek(N.FB_VIEW_ALL, since, self.filter)
 
     # ---- new-session enrichment (src/packets.rs:429-485) -------------------------------------
     def set_asn_tables(self, v4, v6, records=None):

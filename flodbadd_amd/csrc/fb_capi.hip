@@ -138,6 +138,12 @@ struct fb_ctx {
     unsigned long long* d_pass_stats = nullptr;  // [kPassStatWords]
     uint64_t pass_time = 0;         // fb_set_pass_time: what the passes stamp the flows they change with (0: no stamps)
     bool view_direct = false;       // FB_DEBUG_VIEW_DIRECT: the view export's one-lane-per-record copy-out
+    // Zeek export (fb_format_zeek_dev, fb_zeek.hip): rocPRIM's scan storage and the event after its last use
+    // (the call may run on any stream: the next use waits for it)
+    bool zeek_direct = false;       // FB_DEBUG_ZEEK_DIRECT: no LDS staging of the text
+    void* d_zeek_tmp = nullptr;
+    uint64_t zeek_tmp_bytes = 0;
+    hipEvent_t ev_zeek = nullptr;
     // timed contexts (FB_CFG_TIMED, fb_time.hip): the next update's frame times, the capture-time pass's
     // scratch (its last use: ev_tscratch)
     bool timed = false;
@@ -725,6 +731,8 @@ int fb_destroy(fb_ctx* c) {
     dnstrack_free(c->dns);
     hipFree(c->d_mscratch);
     if (c->ev_mscratch) hipEventDestroy(c->ev_mscratch);
+    (void)hipFree(c->d_zeek_tmp);
+    if (c->ev_zeek) (void)hipEventDestroy(c->ev_zeek);
     if (c->h_mbox) hipHostFree(c->h_mbox);
     hipFree(c->d_n);
     hipFree(c->d_hword);
@@ -814,6 +822,9 @@ int fb_debug_set(fb_ctx* c, uint32_t knob, uint64_t value) {
             return FB_OK;
         case FB_DEBUG_VIEW_DIRECT:
             c->view_direct = value != 0;
+            return FB_OK;
+        case FB_DEBUG_ZEEK_DIRECT:
+            c->zeek_direct = value != 0;
             return FB_OK;
         default:
             return set_err(FB_ERR_INVAL, "unknown debug knob %u", knob);
@@ -2622,6 +2633,53 @@ int fb_flow_export_view(fb_ctx* c, const fb_view_query* q, fb_flow_view* out, ui
     return export_to_host(c, out, m, sizeof(fb_flow_view), n, (hipStream_t)stream, "view export", [&](void* d_out) {
         return fb_flow_export_view_dev(c, q, (fb_flow_view*)d_out, m, reinterpret_cast<uint64_t*>(c->d_n), stream);
     });
+}
+
+// ---- Zeek conn.log export (fb_zeek.hip) -----------------------------------------------------------
+int fb_format_zeek_dev(fb_ctx* c, const fb_flow_view* d_views, uint64_t n, const uint8_t* d_hist,
+                       const uint64_t* d_hist_off, uint64_t n_slots, uint8_t* d_text, uint64_t text_cap,
+                       uint64_t* d_line_off, fb_zeek_stats* d_stats, void* stream) {
+    if (!c || !d_views || !d_line_off || !d_stats)
+        return set_err(FB_ERR_INVAL, "ctx, d_views, d_line_off and d_stats are required");
+    if (d_hist && !d_hist_off) return set_err(FB_ERR_INVAL, "a history blob needs its offsets");
+    if (text_cap && !d_text) return set_err(FB_ERR_INVAL, "d_text is NULL with text_cap %llu", (unsigned long long)text_cap);
+    if (reinterpret_cast<uintptr_t>(d_views) & 15u) return set_err(FB_ERR_INVAL, "d_views must be 16-byte aligned");
+    if (!c->timed) return set_err(FB_ERR_INVAL, "the Zeek export needs FB_CFG_TIMED (there is no clock to print)");
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(fb_zeek_stats), s));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_line_off, 0, 8, s));
+        return FB_OK;
+    }
+    // the scan's storage: shared by every call on the context, so each use waits for the one before it, and
+    // a reallocation waits for that use on the host before the old buffer is freed
+    size_t want = 0;
+    HIP_TRY(zeek_scan_tmp_bytes(n, &want));
+    if (!c->ev_zeek) HIP_TRY(hipEventCreateWithFlags(&c->ev_zeek, hipEventDisableTiming));
+    HIP_TRY(hipStreamWaitEvent(s, c->ev_zeek, 0));  // (an event never recorded is complete)
+    if (want > c->zeek_tmp_bytes) {
+        HIP_TRY(hipEventSynchronize(c->ev_zeek));
+        (void)hipFree(c->d_zeek_tmp);
+        c->d_zeek_tmp = nullptr;
+        c->zeek_tmp_bytes = 0;
+        if (hipMalloc(&c->d_zeek_tmp, want) != hipSuccess)
+            return set_err(FB_ERR_NOMEM, "Zeek export scan scratch (%llu bytes)", (unsigned long long)want);
+        c->zeek_tmp_bytes = want;
+    }
+    ZeekArgs a;
+    a.views = d_views;
+    a.n = n;
+    a.hist = d_hist;
+    a.hist_off = reinterpret_cast<const unsigned long long*>(d_hist_off);
+    a.n_slots = n_slots;
+    a.text = d_text;
+    a.cap = text_cap;
+    a.off = reinterpret_cast<unsigned long long*>(d_line_off);
+    a.stats = d_stats;
+    HIP_TRY(launch_zeek(a, !c->zeek_direct, c->d_zeek_tmp, c->zeek_tmp_bytes, s));
+    HIP_TRY(hipEventRecord(c->ev_zeek, s));
+    return FB_OK;
 }
 
 // ---- multi-GPU merge (fb_merge.hip) ---------------------------------------------------------------

@@ -917,6 +917,25 @@ static_assert(sizeof(fb_flow_view) == 256 && sizeof(fb_view_query) == 24, "view 
 hipError_t launch_flow_view(const ViewArgs& a, fb_flow_view* out, unsigned long long out_cap, unsigned long long* d_n,
                             bool staged, hipStream_t s);
 
+// Zeek export (fb_zeek.hip, fb_format_zeek_dev): n > 0 view records, the history blob (null: none) and its
+// per-slot offsets, the text buffer and its capacity, line_off[n + 1] and the stats (zeroed by the caller).
+// tmp: rocPRIM's scan storage, at least zeek_scan_tmp_bytes(n).  staged: whether steps that fit the staging
+// budget go through LDS (false: fb_debug_set FB_DEBUG_ZEEK_DIRECT).
+struct ZeekArgs {
+    const fb_flow_view* views;
+    unsigned long long n;
+    const uint8_t* hist;
+    const unsigned long long* hist_off;
+    unsigned long long n_slots;
+    uint8_t* text;
+    unsigned long long cap;
+    unsigned long long* off;
+    fb_zeek_stats* stats;
+};
+static_assert(sizeof(fb_zeek_stats) == 64, "zeek ABI");
+hipError_t zeek_scan_tmp_bytes(unsigned long long n, size_t* bytes);
+hipError_t launch_zeek(const ZeekArgs& a, bool staged, void* tmp, size_t tmp_bytes, hipStream_t s);
+
 hipError_t launch_dns_parse(const uint8_t* frames, unsigned long long frames_bytes, const fb_dns_out* dns, uint32_t n,
                             const fb_batch_stats* stats, fb_dns_msg* msgs, char* names, fb_ip* addrs, hipStream_t s);
 

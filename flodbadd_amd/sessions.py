@@ -19,7 +19,7 @@ from ._native import (CONN_STATES, FB_FILTER_ALL, FB_FILTER_GLOBAL_ONLY, FB_FILT
                       FLOW_REC_DTYPE, FLOW_VIEW_DTYPE, SESSION_DST_SERVICE, SESSION_LOCAL_DST, SESSION_LOCAL_SRC, SESSION_SELF_DST,
                       SESSION_SELF_SRC, STATUS_ACTIVATED, STATUS_ACTIVE, STATUS_ADDED, STATUS_DEACTIVATED,
                       META_DST_SERVICE, META_HAS_FLAGS, META_LOCAL_DST, META_LOCAL_SRC, META_ORIGINATOR,
-                      META_SELF_DST, META_SELF_SRC, META_SWAP, PARSED_DTYPE, PKT_OUT_DTYPE)
+                      META_SELF_DST, META_SELF_SRC, META_SWAP, PARSED_DTYPE, PKT_OUT_DTYPE, KEY_FIELDS, gpu_lib, ptr)
 
 
 class Protocol(enum.IntEnum):
@@ -220,6 +220,13 @@ class SessionInfo:
     # on a capture that does not track DNS
     src_domain: Optional[str] = None
     dst_domain: Optional[str] = None
+
+    @property
+    def uid(self):
+        """SessionInfo.uid (src/sessions.rs; the reference draws a random UUID v4, src/packets.rs:350): the
+        deterministic session_uid of the key and the start time (0 on an untimed capture).  A property, not a
+        field: equality and the joins compare what they compared before."""
+        return session_uid(self.session, self.stats.start_time_ns or 0)
 
 
 _SERVICE_NAMES = None
@@ -428,6 +435,94 @@ def views_to_sessions(views, histories=None, bl_names=None, timed=True, status=T
                  _per_record(dom_ids, views["rec"]["slot"]), dom_names)
 
 
+# ---- Zeek conn.log (format_sessions_zeek, src/sessions.rs:694-774) ------------------------
+ZEEK_FIELDS = ["ts", "uid", "id.orig_h", "id.orig_p", "id.resp_h", "id.resp_p", "proto", "service", "duration",
+               "orig_bytes", "resp_bytes", "conn_state", "local_orig", "local_resp", "missed_bytes", "history",
+               "orig_pkts", "orig_ip_bytes", "resp_pkts", "resp_ip_bytes", "tunnel_parents"]
+ZEEK_HEADER = "\t".join(ZEEK_FIELDS)
+_MASK64 = (1 << 64) - 1
+
+
+def _uid_mix(x):
+    x = (x + 0x9E3779B97F4A7C15) & _MASK64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return x ^ (x >> 31)
+
+
+def session_uid(session, start_time_ns):
+    """The uid of a session: a = fb_flow_hash(key) (the library's host-side hash), b = mix(a ^ start_time_ns),
+    the sixteen bytes a then b big-endian as a version-4, variant-1 UUID in lowercase 8-4-4-4-12 hex.  It does
+    not depend on the table slot, so it survives growths and purges; a purged flow that returns starts at
+    another time and gets another uid, as a new session does in the reference."""
+    key = np.zeros(1, dtype=np.dtype(KEY_FIELDS))
+    s, d, fam = session.key_fields()
+    key[0]["src_ip"], key[0]["dst_ip"], key[0]["family"] = s, d, fam
+    key[0]["src_port"], key[0]["dst_port"], key[0]["protocol"] = session.src_port, session.dst_port, int(session.protocol)
+    a = int(gpu_lib().fb_flow_hash(ptr(key)))
+    b = _uid_mix(a ^ (int(start_time_ns) & _MASK64))
+    raw = bytearray(a.to_bytes(8, "big") + b.to_bytes(8, "big"))
+    raw[6] = (raw[6] & 0x0F) | 0x40
+    raw[8] = (raw[8] & 0x3F) | 0x80
+    h = raw.hex()
+    return "-".join((h[0:8], h[8:12], h[12:16], h[16:20], h[20:32]))
+
+
+def rust_ip_str(ip):
+    """An address as Rust's Display prints it (std::net): IPv4 dotted; IPv6 lowercase groups without leading
+    zeros, the first longest run of two or more zero groups as "::", and an IPv4-mapped address as
+    ::ffff:a.b.c.d -- the one form Python's str() printed differently (::ffff:102:304) before 3.13."""
+    ip = ipaddress.ip_address(ip)
+    if ip.version == 6 and int(ip) >> 32 == 0xFFFF:
+        return "::ffff:%s" % ipaddress.IPv4Address(int(ip) & 0xFFFFFFFF)
+    return ip.compressed
+
+
+def format_sessions_zeek(sessions):
+    """format_sessions_zeek (src/sessions.rs:694-774): the header, then one conn.log line per session of a
+    timed capture, in the order given.  ts and duration take the reference's f64 path on purpose --
+    repr(secs + micros / 1e6) is Rust's `{}` of the same sum (shortest round-trip, no exponent in this range,
+    no ".0" for an integral value) and '%.6f' its `{:.6}` -- so this is the independent check of the device's
+    integer formatting, not a copy of it.  The difference of the two times wraps to 64 bits as the record's
+    does.  missed_bytes is 0: the reference never increments it (src/packets.rs)."""
+    out = [ZEEK_HEADER]
+    for info in sessions:
+        st = info.stats
+        if st.start_time_ns is None:
+            raise ValueError("a Zeek line needs the session's capture times (a timed capture)")
+        secs, micros = st.start_time_ns // 10 ** 9, st.start_time_ns % 10 ** 9 // 1000
+        ts = repr(float(secs) + float(micros) / 1e6)
+        ts = ts[:-2] if ts.endswith(".0") else ts
+        if st.end_time_ns is None:
+            duration = "-"
+        else:
+            d = ((st.end_time_ns - st.start_time_ns + (1 << 63)) & _MASK64) - (1 << 63)
+            us = abs(d) // 1000 * (-1 if d < 0 else 1)  # num_microseconds truncates toward zero
+            duration = "%.6f" % (float(us) / 1e6)
+        s = info.session
+        out.append("\t".join((
+            ts, info.uid, rust_ip_str(s.src_ip), str(s.src_port), rust_ip_str(s.dst_ip), str(s.dst_port),
+            "tcp" if s.protocol == Protocol.TCP else "udp", "-", duration, str(st.outbound_bytes),
+            str(st.inbound_bytes), st.conn_state or "-", "-", "-", "0", st.history, str(st.orig_pkts),
+            str(st.orig_ip_bytes), str(st.resp_pkts), str(st.resp_ip_bytes), "-")))
+    return out
+
+
+def pack_histories(histories, capacity):
+    """{table slot: history str} -> (uint8 characters, uint64 off[capacity + 1]): the blob and per-slot offsets
+    fb_format_zeek_dev reads (slot s's history is chars[off[s]:off[s + 1]]; a slot without one is empty)."""
+    capacity = int(capacity)
+    lens = np.zeros(capacity + 1, dtype=np.uint64)
+    slots = np.fromiter(histories.keys(), dtype=np.int64, count=len(histories))
+    if len(slots) and not (0 <= slots.min() and slots.max() < capacity):
+        raise ValueError("history slots %d..%d outside the table (%d slots)" % (slots.min(), slots.max(), capacity))
+    lens[slots + 1] = np.fromiter(map(len, histories.values()), dtype=np.uint64, count=len(histories))
+    strs = list(histories.values())
+    chars = np.frombuffer("".join(strs[k] for k in np.argsort(slots, kind="stable").tolist()).encode("ascii"),
+                          dtype=np.uint8)
+    return chars, np.cumsum(lens, dtype=np.uint64)
+
+
 def filter_sessions(sessions: List[SessionInfo], flt: SessionFilter, lan_v6=()) -> List[SessionInfo]:
     """src/sessions.rs:678-692: is_local_session! / is_global_session! evaluate is_lan_ip on the
     session's addresses at call time (src/sessions.rs:660-672), not the flags stored at insert."""
@@ -441,7 +536,8 @@ def filter_sessions(sessions: List[SessionInfo], flt: SessionFilter, lan_v6=()) 
 __all__ = ["Protocol", "SessionFilter", "Session", "SessionPacketData", "SessionStats", "SessionStatus", "SessionInfo",
            "WhitelistState",
            "ip_to_words", "words_to_ip", "service_name", "records_to_packets", "flows_to_sessions", "views_to_sessions",
-           "filter_sessions",
+           "filter_sessions", "ZEEK_FIELDS", "ZEEK_HEADER", "session_uid", "rust_ip_str", "format_sessions_zeek",
+           "pack_histories",
            "packets_to_parsed", "determine_conn_state", "histories_from_records", "is_lan_ip", "is_local_session",
            "META_HAS_FLAGS", "META_SWAP", "META_ORIGINATOR", "META_LOCAL_SRC", "META_LOCAL_DST",
            "META_SELF_SRC", "META_SELF_DST", "META_DST_SERVICE"]

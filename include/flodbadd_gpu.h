@@ -337,8 +337,15 @@ int fb_set_frame_times(fb_ctx* ctx, const uint64_t* d_ts);
  * FB_DEBUG_DENSE_OFFSET_SKEW -- fault injection, added (mod 2^32) to the session half of every
  * dense tile offset, as a corrupted look-back word would be (< 2^32; logged on stderr when set);
  * FB_DEBUG_VIEW_DIRECT -- non-zero: fb_flow_export_view_dev stores one record per lane instead of staging
- * a step's records in LDS (same result; the shape the staged copy-out is measured against). */
-enum fb_debug_knob { FB_DEBUG_DENSE_STEAL_POLLS = 1, FB_DEBUG_DENSE_OFFSET_SKEW = 2, FB_DEBUG_VIEW_DIRECT = 3 };
+ * a step's records in LDS (same result; the shape the staged copy-out is measured against);
+ * FB_DEBUG_ZEEK_DIRECT -- non-zero: fb_format_zeek_dev stores every step's lines straight to global memory,
+ * the path a step too large for the LDS staging takes (same bytes). */
+enum fb_debug_knob {
+    FB_DEBUG_DENSE_STEAL_POLLS = 1,
+    FB_DEBUG_DENSE_OFFSET_SKEW = 2,
+    FB_DEBUG_VIEW_DIRECT = 3,
+    FB_DEBUG_ZEEK_DIRECT = 4
+};
 int fb_debug_set(fb_ctx* ctx, uint32_t knob, uint64_t value);
 /* Whether the fused parse + upsert calls (fb_process_seg_dev, fb_process_seg_async_dev) store the
  * SESSION records in d_out (default 1).  With 0 the session table is their only per-packet output,
@@ -1164,6 +1171,50 @@ int fb_flow_export_view_dev(fb_ctx* ctx, const fb_view_query* query, fb_flow_vie
                             void* stream);
 int fb_flow_export_view(fb_ctx* ctx, const fb_view_query* query, fb_flow_view* out, uint64_t cap, uint64_t* n,
                         void* stream);
+
+/* ---- Zeek conn.log export (format_sessions_zeek, src/sessions.rs:694-774) ----------
+ * One text line per fb_flow_view record, formatted on the device: 21 tab-separated fields and '\n'
+ *   ts uid id.orig_h id.orig_p id.resp_h id.resp_p proto service duration orig_bytes resp_bytes conn_state
+ *   local_orig local_resp missed_bytes history orig_pkts orig_ip_bytes resp_pkts resp_ip_bytes tunnel_parents
+ * (the header line is the caller's).  ts = time.start_time_ns as secs[.micros], trailing zeros dropped;
+ * duration = (end_time_ns - start_time_ns) truncated to microseconds as [-]secs.6 digits, "-" without an
+ * end; both in integer arithmetic, equal to the reference's f64 text for 2^14 <= secs < 2^33 and
+ * |micros| < 2^52 (records outside are counted in ts_inexact).  Addresses as Rust's Display prints them;
+ * uid = the 128 bits {fb_flow_hash(key), mix(hash ^ start_time_ns)} as a version-4 UUID (the reference
+ * draws a random one, src/packets.rs:350); service, local_orig, local_resp, tunnel_parents "-",
+ * missed_bytes 0, as the reference leaves them.
+ * FB_ZEEK_FIXED_MAX: the longest line without its history -- ts 18 (11 + '.' + 6), uid 36, two addresses
+ * of 39, two ports of 5, proto 3, four "-", duration 18 ('-' + 10 + '.' + 6: |end - start| < 2^63 ns),
+ * six counters of 20, conn_state 3, missed_bytes 1, 20 tabs, '\n'. */
+#define FB_ZEEK_FIXED_MAX 312u
+/* The kernel's shape, for the tests that sit on its thresholds: records per workgroup step, the bytes of
+ * a step the write-out stages in LDS (a larger step is stored directly), and the history length from
+ * which the wave copies a history together. */
+#define FB_ZEEK_STEP 256u
+#define FB_ZEEK_STAGE_BYTES 40000u
+#define FB_ZEEK_COOP_HIST 64u
+typedef struct fb_zeek_stats {
+    uint64_t lines;          /*  0: records given (n)                                                    */
+    uint64_t bytes;          /*  8: bytes all n lines need                                               */
+    uint64_t lines_written;  /* 16: leading lines that fit text_cap entirely                             */
+    uint64_t ts_inexact;     /* 24: records outside the exact ts / duration range (above)                */
+    uint64_t hist_mismatch;  /* 32: records whose rec.hist_len != the blob's length                      */
+    uint64_t reserved[3];
+} fb_zeek_stats;             /* 64 bytes */
+/* The lines of d_views[0 .. n) -- what fb_flow_export_view_dev wrote; the table is not touched -- into
+ * d_text: line i is d_text[d_line_off[i] .. d_line_off[i + 1]), input order.  The history characters are
+ * an input: d_hist[d_hist_off[slot] .. d_hist_off[slot + 1]) for rec.slot (d_hist_off has n_slots + 1
+ * entries, non-decreasing, inside d_hist).  d_hist NULL: every history field is empty and hist_mismatch
+ * stays 0.  With a blob its length decides what is written; a record whose hist_len disagrees, or whose
+ * slot is >= n_slots (empty history), is counted in hist_mismatch.  Lines that do not fit text_cap
+ * entirely are not written and nothing at or past d_text + text_cap is stored; d_line_off (n + 1 entries)
+ * and d_stats are complete either way, so a caller can size a retry.  n == 0 writes d_line_off[0] = 0 and
+ * zero stats.  DEVICE pointers, asynchronous, no host round trip.  FB_ERR_INVAL for a NULL ctx, d_views,
+ * d_line_off or d_stats, a blob without offsets, d_text NULL with text_cap != 0, d_views not
+ * 16-byte aligned, or a context without FB_CFG_TIMED (no clock to print). */
+int fb_format_zeek_dev(fb_ctx* ctx, const fb_flow_view* d_views, uint64_t n, const uint8_t* d_hist,
+                       const uint64_t* d_hist_off, uint64_t n_slots, uint8_t* d_text, uint64_t text_cap,
+                       uint64_t* d_line_off, fb_zeek_stats* d_stats, void* stream);
 
 /* ---- multi-GPU session table (BASELINE configs[4]) ------------------------------
  * The reference runs one capture task per interface into ONE shared DashMap (src/capture.rs:946-1016,
