@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -42,16 +43,87 @@ int set_err(int code, const char* fmt, ...) {
 // call buckets batch k (on the caller's stream, right after its parse) into set k & 1 while the
 // update stream applies batch k - 1 from the other set.
 struct UpdScratch {
-    uint32_t* entries = nullptr;   // [flow_recs] bucketed record slots (or combined ids)
-    FlowEntry* comb = nullptr;     // k_flow_combine entries (2 units each), comb_cap of them
-    uint32_t* rows = nullptr;      // [flow_chunks][flow_parts]
-    uint32_t* cols = nullptr;      // [flow_parts][flow_chunks]
-    uint32_t* rows_h = nullptr;    // [flow_chunks][flow_parts] combined groups' rows before k_flow_combine
-    uint32_t* e_orig = nullptr;    // [flow_recs] combined groups' original entry words (history)
-    uint2* e_sort = nullptr;       // [flow_recs] combined groups' records in record order (history)
-    uint32_t* hot = nullptr;       // [flow_recs / 16 + 16] hot groups for k_flow_combine
-    uint32_t* ctl = nullptr;       // [4] its counters (FlowParams::ctl)
-    uint32_t* order = nullptr;     // [flow_parts + kK2Lead + 1] K2's partition order (FlowParams::order)
+    DevBuf<uint32_t> entries;   // [flow_recs] bucketed record slots (or combined ids)
+    DevBuf<FlowEntry> comb;     // k_flow_combine entries (2 units each), comb_cap of them
+    DevBuf<uint32_t> rows;      // [flow_chunks][flow_parts]
+    DevBuf<uint32_t> cols;      // [flow_parts][flow_chunks]
+    DevBuf<uint32_t> rows_h;    // [flow_chunks][flow_parts] combined groups' rows before k_flow_combine
+    DevBuf<uint32_t> e_orig;    // [flow_recs] combined groups' original entry words (history)
+    DevBuf<uint2> e_sort;       // [flow_recs] combined groups' records in record order (history)
+    DevBuf<uint32_t> hot;       // [flow_recs / 16 + 16] hot groups for k_flow_combine
+    DevBuf<uint32_t> ctl;       // [4] its counters (FlowParams::ctl)
+    DevBuf<uint32_t> order;     // [flow_parts + kK2Lead + 1] K2's partition order (FlowParams::order)
+};
+// Per-record scratch of an update, [flow_recs] each: made together by ensure_flow_scratch (the buffers of
+// the odd async batches by the first pipelined call after it).
+struct RecScratch {
+    DevBuf<uint32_t> hword;      // K2's history word per entry
+    DevBuf<uint32_t> rec_part;   // partition per record slot (fb_process_seg_dev)
+    DevBuf<uint32_t> rec_part2;  // ... of the odd async batches
+    DevBuf<uint4> rec_ent;       // update entry (UpdEnt, 64 B) per record slot
+    DevBuf<uint4> rec_ent2;      // ... of the odd async batches
+    DevBuf<uint32_t> agg_slot;   // [flow_recs / 2 + 1] table slot per combined entry
+};
+// Dense output (fb_parse_classify_dev & co., fb_seg_compact_dev): segment counts + their scan, and the
+// single-pass kernel's per-tile look-back words (k_parse_dense), for `cap` segments.
+struct ScanScratch {
+    DevBuf<uint32_t> cseg;               // [cap] segment counts (dense pass 1)
+    DevBuf<unsigned long long> cpre;     // [cap] batch-wide offset of every segment
+    DevBuf<unsigned long long> cstatus;  // [seg_scan_tiles(cap)] scan look-back words
+    DevBuf<uint32_t> cticket;            // scan ticket counter
+    DevBuf<unsigned long long> dstatus;  // [cap / parse_dense_tile_segs() + 1]
+    uint64_t cap = 0;                    // segments
+    uint32_t scan_epoch = 0;             // epoch of the last scan (0: status needs zeroing)
+    uint32_t dense_epoch = 0;            // epoch of the last dense launch (0: status needs zeroing)
+};
+// Host-mode staging: the frames, the per-packet arrays (`pkts_cap` packets) and the stats grow apart.
+struct Staging {
+    struct Pkts {
+        DevBuf<uint32_t> offsets;
+        DevBuf<fb_pkt_out> out;
+        DevBuf<fb_dns_out> dns;
+        DevBuf<uint8_t> cls;
+    };
+    DevBuf<uint8_t> frames;
+    Pkts pk;
+    DevBuf<fb_batch_stats> stats;
+};
+// The installed whitelist's index (fb_set_whitelist, fb_whitelist.hip).
+struct WlDev {
+    DevBuf<uint32_t> a4, k4, k6, gkey, gbeg, owner, country;
+    DevBuf<uint4> a6;
+    DevBuf<WlRule> rules;
+    uint32_t n4 = 0, n6 = 0, ng = 0, nr = 0, records = 0;
+    WlTables tables() const { return {a4, k4, a6, k6, gkey, gbeg, rules, owner, country, n4, n6, ng, nr, records}; }
+};
+// The installed anomaly model (fb_set_anomaly_model, fb_anomaly.hip).
+struct AnModel {
+    DevBuf<fb_if_node> nodes;
+    DevBuf<uint32_t> first;
+    DevBuf<uint32_t> service;  // [65536]; empty: every code 0
+    uint32_t trees = 0;
+    fb_an_params prm = {};
+    bool active = false;
+    AnForest forest() const {
+        AnForest f;
+        if (active) {
+            f.nodes = nodes;
+            f.first = first;
+            f.n_trees = trees;
+            f.prm = prm;
+        }
+        f.service_code = service;
+        return f;
+    }
+};
+// Enrichment tables (fb_set_asn_tables / fb_set_blacklists, fb_enrich.hip).
+struct EnrichDev {
+    DevBuf<fb_asn_range> asn4, asn6;
+    DevBuf<uint32_t> bl4_pos;
+    DevBuf<uint4> bl6_pos;
+    DevBuf<unsigned long long> bl4_mask, bl6_mask;
+    uint32_t n4 = 0, n6 = 0, m4 = 0, m6 = 0;
+    EnrichTables tables() const { return {asn4, asn6, bl4_pos, bl4_mask, bl6_pos, bl6_mask, n4, n6, m4, m6}; }
 };
 
 // Per-slot planes: arrays beside the table, one element per slot, that a flow's element follows through
@@ -82,130 +154,104 @@ static_assert(sizeof(fb_flow_domain) == sizeof(uint2), "one name-id pair per slo
 // the counter words of one synchronous pass over the table (pass_begin / pass_end)
 constexpr uint32_t kPassStatWords = std::max({kAgeStatWords, kWlCounters, kBlCounters, kAnCounters, kDomCounters});
 
+// The flow table and the arrays sized by its capacity: made together (table_alloc), and replaced together by
+// a growth.  A plane is an array beside the table, one element per slot (kPlaneDesc); empty: not made yet.
+struct FlowTable {
+    uint64_t cap = 0;     // slots
+    uint32_t parts = 0;   // partitions of kFlowSlots slots
+    uint32_t shift = 64;  // 64 - log2(parts)
+    DevBuf<FlowSlot> slots;
+    DevBuf<unsigned long long> partials;  // [4 * parts] per-partition new / updated / occupied / history
+    DevBuf<uint32_t> hcount;              // [cap] history characters per slot of the last update
+    DevBuf<uint32_t> part_base;           // [parts + 1] history output offset per partition
+    DevBuf<uint32_t> hist_slow;           // [parts + 1] count + partitions for the general history kernel
+    DevBuf<uint4> char_call;              // [cap] first update call of S s H h per slot (the merge's)
+    DevBuf<uint8_t> plane[kPlanes];       // [cap * kPlaneDesc[p].elem]
+};
+
 struct fb_ctx {
     int device = 0;
-    DevConfig* h_cfg = nullptr;  // host shadow
-    DevConfig* d_cfg = nullptr;
+    std::unique_ptr<DevConfig> h_cfg;  // host shadow
+    DevBuf<DevConfig> d_cfg;
     bool cfg_dirty = true;
-    unsigned long long* d_tick = nullptr;  // [kTickWords] k_parse_seg stats words
+    DevBuf<unsigned long long> d_tick;  // [kTickWords] k_parse_seg stats words
     bool need_reset = true;       // zero the tick + error words before the next launch
     uint32_t epoch = 0;           // parse launches so far: its parity picks the launch's error word
     uint32_t seg_grid = 0;        // streaming segmented kernel: co-resident blocks
     uint32_t seg_grid_async = 0;  // ... in the pipelined call: FB_ASYNC_BPC blocks per CU (not the full
                                   // grid), so the previous batch's table update keeps part of each CU
-    uint32_t* d_error = nullptr;  // [4] error words, indexed by launch & 3 (a launch clears the next one's;
+    DevBuf<uint32_t> d_error;     // [4] error words, indexed by launch & 3 (a launch clears the next one's;
                                   // a pipelined update still writes the one two launches back)
-    // dense output (fb_parse_classify_dev & co., fb_seg_compact_dev): segment counts + their scan
-    uint32_t* d_cseg = nullptr;            // [cseg_cap] segment counts (dense pass 1)
-    unsigned long long* d_cpre = nullptr;  // [cseg_cap] batch-wide offset of every segment
-    unsigned long long* d_cstatus = nullptr;  // [seg_scan_tiles(cseg_cap)] scan look-back words
-    uint32_t* d_cticket = nullptr;            // scan ticket counter
-    uint32_t scan_epoch = 0;                  // epoch of the last scan (0: status needs zeroing)
-    uint64_t cseg_cap = 0;                    // segments
-    // single-pass dense output (k_parse_dense): per-tile look-back words, epoch, grid, and the
-    // look-back's polls before it computes a late predecessor's sums itself (fb_debug_set
-    // FB_DEBUG_DENSE_STEAL_POLLS; tests set 0 to force that path)
-    unsigned long long* d_dstatus = nullptr;  // [cseg_cap / parse_dense_tile_segs() + 1]
-    uint32_t dense_epoch = 0;                 // epoch of the last launch (0: status needs zeroing)
+    ScanScratch sc;               // dense output scratch (ensure_compact_scratch)
+    // single-pass dense output (k_parse_dense): grid, and the look-back's polls before it computes a late
+    // predecessor's sums itself (fb_debug_set FB_DEBUG_DENSE_STEAL_POLLS; tests set 0 to force that path)
     uint32_t dense_grid = 0;
     uint32_t steal_polls = 1u << 12;
     unsigned long long dn_skew = 0ull;  // FB_DEBUG_DENSE_OFFSET_SKEW: fault injection (k_parse_dense copy bounds)
-    hipEvent_t stage_event = nullptr;  // fb_set_stage_event (caller-owned): recorded between the
-                                       // parse and the update of fb_process[_seg]_dev
     // flow table
-    FlowSlot* d_table = nullptr;
-    uint64_t table_cap = 0;
-    uint32_t flow_parts = 0;        // partitions of kFlowSlots slots
-    uint32_t flow_shift = 64;       // 64 - log2(flow_parts)
+    FlowTable tb;
+    template <typename T>
+    T* plane(PlaneId p) const { return reinterpret_cast<T*>(tb.plane[p].get()); }
     UpdScratch us[2];               // update scratch sets (set 1: pipelined calls only, allocated lazily)
+    RecScratch rs;
     uint32_t comb_cap = 0;
     uint64_t flow_recs = 0;         // scratch capacity (multiple of kFlowChunk)
     uint32_t last_n = 0;            // packets of the last parse launch (bounds its records)
-    unsigned long long* d_partials = nullptr;  // [3 * flow_parts] per-partition new / updated / occupied
     // growth: the occupancy each update reports in host-mapped memory, updates issued
-    FlowMailbox* h_mbox = nullptr;  // pinned, host-mapped (written by k_flow_finish)
-    FlowMailbox* d_mbox = nullptr;  // its device address
+    PinnedBuf<FlowMailbox> mbox;    // host-mapped (written by k_flow_finish)
     uint64_t upd_seq = 0;           // table updates issued (the mailbox's seq counts them from 1)
     uint64_t grown_seq = 0;         // upd_seq at the last growth (older reports describe the old geometry)
     uint64_t clear_seq = 0;         // upd_seq at the last fb_flow_clear (older reports are void)
     uint64_t generation = 0;        // slot moves: growths and purges
     bool grow = true;               // FB_CFG_FIXED_TABLE clears it
-    uint32_t* d_remap = nullptr;    // the last growth's old -> new slot map
-    uint4* d_char_call = nullptr;   // [table_cap] first update call of S s H h per slot (the merge's)
-    void* d_plane[kPlanes] = {};    // [table_cap] each (kPlaneDesc); null: not made yet
-    template <typename T>
-    T* plane(PlaneId p) const { return static_cast<T*>(d_plane[p]); }
-    unsigned long long* d_pass_stats = nullptr;  // [kPassStatWords]
+    DevBuf<uint32_t> d_remap;       // the last growth's (or purge's) old -> new slot map
+    DevBuf<unsigned long long> d_pass_stats;  // [kPassStatWords]
     uint64_t pass_time = 0;         // fb_set_pass_time: what the passes stamp the flows they change with (0: no stamps)
     bool view_direct = false;       // FB_DEBUG_VIEW_DIRECT: the view export's one-lane-per-record copy-out
-    // Zeek export (fb_format_zeek_dev, fb_zeek.hip): rocPRIM's scan storage and the event after its last use
-    // (the call may run on any stream: the next use waits for it)
+    // Zeek export (fb_format_zeek_dev, fb_zeek.hip): rocPRIM's scan storage
     bool zeek_direct = false;       // FB_DEBUG_ZEEK_DIRECT: no LDS staging of the text
-    void* d_zeek_tmp = nullptr;
-    uint64_t zeek_tmp_bytes = 0;
-    hipEvent_t ev_zeek = nullptr;
-    // timed contexts (FB_CFG_TIMED, fb_time.hip): the next update's frame times, the capture-time pass's
-    // scratch (its last use: ev_tscratch)
+    StreamScratch zeek_tmp;
+    // timed contexts (FB_CFG_TIMED, fb_time.hip): the capture-time pass's scratch
     bool timed = false;
-    const unsigned long long* next_ts = nullptr;
-    void* d_tscratch = nullptr;
-    uint64_t tscratch_bytes = 0;
-    hipEvent_t ev_tscratch = nullptr;
+    StreamScratch tscratch;
     // session aging (fb_flow_age, fb_age.hip): the buffer the next purge writes its slot map into (swapped
-    // with d_remap when the purge removed something)
-    uint32_t* d_age_remap = nullptr;
-    uint64_t age_remap_n = 0;
-    // whitelist conformance (fb_set_whitelist / fb_flow_whitelist, fb_whitelist.hip): the installed
-    // list's index
+    // with d_remap when the purge removed something); reallocated when its size is not the table's
+    DevBuf<uint32_t> d_age_remap;
+    // whitelist conformance (fb_set_whitelist / fb_flow_whitelist, fb_whitelist.hip)
     bool wl_active = false;
-    uint32_t *d_wl_a4 = nullptr, *d_wl_k4 = nullptr, *d_wl_k6 = nullptr, *d_wl_gkey = nullptr, *d_wl_gbeg = nullptr;
-    uint4* d_wl_a6 = nullptr;
-    WlRule* d_wl_rules = nullptr;
-    uint32_t *d_wl_owner = nullptr, *d_wl_country = nullptr;
-    uint32_t wl_n4 = 0, wl_n6 = 0, wl_ng = 0, wl_nr = 0, wl_records = 0;
-    // anomaly pass (fb_set_anomaly_model / fb_flow_anomaly, fb_anomaly.hip): the installed model
-    bool an_active = false;
-    fb_if_node* d_an_nodes = nullptr;
-    uint32_t* d_an_first = nullptr;
-    uint32_t* d_an_service = nullptr;  // [65536]; null: every code 0
-    uint32_t an_trees = 0;
-    fb_an_params an_prm = {};
-    // DNS tracker (fb_dns_track_enable, fb_dnstrack.hip); null: tracking is off
+    WlDev wl;
+    AnModel an;     // anomaly pass (fb_set_anomaly_model / fb_flow_anomaly, fb_anomaly.hip)
+    EnrichDev en;   // fb_set_asn_tables / fb_set_blacklists
+    // DNS tracker (fb_dns_track_enable, fb_dnstrack.hip); null: tracking is off (freed by fb_destroy)
     DnsTrack* dns = nullptr;
-    void* d_mscratch = nullptr;   // multi-GPU merge scratch (export owner counts / merge tables)
-    hipEvent_t ev_mscratch = nullptr;  // after the last export / merge that used d_mscratch (either may
-                                       // run on any stream: the next use waits for it)
-    uint64_t mscratch_bytes = 0;
-    uint64_t remap_n = 0;
-    unsigned long long* d_n = nullptr;
-    // ordered per-flow state: update calls since create/clear, table slot of each record slot
+    StreamScratch mscratch;  // multi-GPU merge scratch (export owner counts / merge tables)
+    DevBuf<unsigned long long> d_n;
+    // ordered per-flow state: update calls since create/clear
     uint32_t flow_batch = 0;
-    uint32_t* d_hword = nullptr;          // [flow_recs] K2's history word per entry
-    uint32_t* d_rec_part = nullptr;       // [flow_recs] partition per record slot (fb_process_seg_dev)
-    const fb_pkt_out* part_recs = nullptr;  // the records part_buf was written for (one update)
-    uint32_t* part_buf = nullptr;           // the partition buffer the last fused parse wrote
-    uint32_t* part_target = nullptr;        // the buffer the next fused parse writes (null: d_rec_part)
-    uint4* d_rec_ent = nullptr;             // [flow_recs] update entry (UpdEnt, 64 B) per record slot
-    uint4* d_rec_ent2 = nullptr;            // ... of the odd async batches
-    uint4* ent_buf = nullptr;               // the entries the last fused parse wrote (with part_buf)
-    uint4* ent_target = nullptr;            // the entries the next fused parse writes (null: d_rec_ent)
     bool emit_records = true;               // fb_set_session_records: fused calls store SESSION records
     // fb_process_seg_async_dev: updates on the context's own stream, one batch behind the parses
-    hipStream_t upd = nullptr;
-    hipEvent_t ev_parsed = nullptr;
+    DevStream upd;
+    DevEvent ev_parsed;
     // after the last fb_flow_history_dev: it reads the last update's shared scratch (history words,
     // partials, slot counts, combined-entry slots), which the next update rewrites -- that update
     // waits for it on every stream it uses, whichever stream the history ran on
-    hipEvent_t ev_hist = nullptr;
+    DevEvent ev_hist;
     bool hist_pending = false;
-    hipEvent_t ev_upd[2] = {nullptr, nullptr};  // after the update of async batch k (k & 1)
+    DevEvent ev_upd[2];                         // after the update of async batch k (k & 1)
     uint64_t async_k = 0;                       // async batches issued
-    uint32_t* d_rec_part2 = nullptr;            // partitions of the odd async batches
-    const void* async_prev[3] = {nullptr, nullptr, nullptr};  // the last async batch's records, counts, stats
     uint32_t upd_word[2] = {4u, 4u};            // error word (launch & 3) of the async update in slot k & 1 (4: none)
-    uint32_t* d_agg_slot = nullptr;       // [flow_recs / 2 + 1] table slot per combined entry
     uint32_t last_set = 0;                // the update scratch set of the last update (history)
-    // the last update, for fb_flow_history_dev
+    // Borrowed, never freed here: the caller's buffers and event, and positions inside rs.
+    hipEvent_t stage_event = nullptr;  // fb_set_stage_event (caller-owned): recorded between the
+                                       // parse and the update of fb_process[_seg]_dev
+    const unsigned long long* next_ts = nullptr;  // fb_set_frame_times: the next update's frame times
+    const fb_pkt_out* part_recs = nullptr;  // the records part_buf was written for (one update)
+    uint32_t* part_buf = nullptr;           // the partition buffer the last fused parse wrote
+    uint32_t* part_target = nullptr;        // the buffer the next fused parse writes (null: rs.rec_part)
+    uint4* ent_buf = nullptr;               // the entries the last fused parse wrote (with part_buf)
+    uint4* ent_target = nullptr;            // the entries the next fused parse writes (null: rs.rec_ent)
+    const void* async_prev[3] = {nullptr, nullptr, nullptr};  // the last async batch's records, counts, stats
+    // ... the last update, for fb_flow_history_dev
     const fb_pkt_out* last_recs = nullptr;
     const uint32_t* last_part = nullptr;  // the fused parse's per-record words of the last update
     const uint32_t* last_seg = nullptr;
@@ -213,29 +259,8 @@ struct fb_ctx {
     uint32_t last_slots = 0;
     uint32_t last_chunks = 0;
     FlowParams last_p;                    // the last update's parameters (fb_flow_history_dev)
-    uint32_t* d_hcount = nullptr;         // [table_cap] history characters per slot of the last update
-    uint32_t* d_part_base = nullptr;      // [flow_parts + 1] history output offset per partition
-    uint32_t* d_hist_slow = nullptr;      // [flow_parts + 1] count + partitions for the general history kernel
-    uint32_t* d_hist_cnt = nullptr;       // per-block slot counts of hot history partitions (lazy)
-    uint64_t hist_cnt_bytes = 0;
-    // enrichment tables (fb_set_asn_tables / fb_set_blacklists)
-    fb_asn_range* d_asn4 = nullptr;
-    fb_asn_range* d_asn6 = nullptr;
-    uint32_t n_asn4 = 0, n_asn6 = 0;
-    uint32_t* d_bl4_pos = nullptr;
-    unsigned long long* d_bl4_mask = nullptr;
-    uint4* d_bl6_pos = nullptr;
-    unsigned long long* d_bl6_mask = nullptr;
-    uint32_t m_bl4 = 0, m_bl6 = 0;
-    // host-mode staging
-    uint8_t* s_frames = nullptr;
-    uint64_t s_frames_cap = 0;
-    uint32_t* s_offsets = nullptr;
-    fb_pkt_out* s_out = nullptr;
-    fb_dns_out* s_dns = nullptr;
-    uint8_t* s_cls = nullptr;
-    uint64_t s_pkts_cap = 0;
-    fb_batch_stats* s_stats = nullptr;
+    DevBuf<uint8_t> d_hist_cnt;           // per-block slot counts of hot history partitions (lazy), bytes
+    Staging st;                           // host-mode staging (ensure_staging)
 };
 
 int fbk::ctx_device(const fb_ctx* c) { return c->device; }
@@ -276,15 +301,13 @@ static int drain_updates(fb_ctx* c) {
 
 // ---- per-slot planes (kPlaneDesc) ----------------------------------------------------------------
 static hipError_t plane_zero(fb_ctx* c, PlaneId p, hipStream_t s) {
-    return c->d_plane[p] ? hipMemsetAsync(c->d_plane[p], 0, c->table_cap * kPlaneDesc[p].elem, s) : hipSuccess;
+    return c->tb.plane[p] ? hipMemsetAsync(c->tb.plane[p], 0, c->tb.cap * kPlaneDesc[p].elem, s) : hipSuccess;
 }
 // The plane exists (made zeroed when it does not).
 static int plane_ensure(fb_ctx* c, PlaneId p, hipStream_t s) {
-    if (c->d_plane[p]) return FB_OK;
-    if (hipMalloc(&c->d_plane[p], c->table_cap * kPlaneDesc[p].elem) != hipSuccess) {
-        c->d_plane[p] = nullptr;
+    if (c->tb.plane[p]) return FB_OK;
+    if (c->tb.plane[p].alloc(c->tb.cap * kPlaneDesc[p].elem) != hipSuccess)
         return set_err(FB_ERR_NOMEM, "%s", kPlaneDesc[p].name);
-    }
     HIP_TRY(plane_zero(c, p, s));
     return FB_OK;
 }
@@ -293,7 +316,32 @@ static int plane_ensure(fb_ctx* c, PlaneId p, hipStream_t s) {
 static hipError_t plane_move(const fb_ctx* c, PlaneId p, const uint32_t* remap, uint64_t new_cap, hipStream_t s,
                              void* nw) {
     const hipError_t e = hipMemsetAsync(nw, 0, new_cap * kPlaneDesc[p].elem, s);
-    return e != hipSuccess ? e : kPlaneDesc[p].remap(c->d_plane[p], remap, c->table_cap, nw, s);
+    return e != hipSuccess ? e : kPlaneDesc[p].remap(c->tb.plane[p], remap, c->tb.cap, nw, s);
+}
+// A table of `cap` slots (a power of two, kFlowSlots at least) with the arrays sized by it, and the planes
+// `like` has: whole, or t is left empty and the name of what could not be allocated returned (else null).
+static const char* table_alloc(FlowTable& t, uint64_t cap, const FlowTable* like) {
+    const uint64_t parts = cap / kFlowSlots;
+    const char* failed = nullptr;
+    const hipError_t e = alloc_group(t, [&](FlowTable& n) {
+        n.cap = cap;
+        n.parts = (uint32_t)parts;
+        for (n.shift = 64u; (1ull << (64u - n.shift)) < parts;) --n.shift;
+        failed = "flow table";
+        hipError_t a = n.slots.alloc(cap);
+        if (a != hipSuccess) return a;
+        failed = "flow table partials";
+        a = alloc_each(n.partials, 4ull * parts, n.hcount, cap, n.part_base, parts + 1ull, n.hist_slow, parts + 1ull);
+        if (a != hipSuccess) return a;
+        failed = "character-call array";
+        a = n.char_call.alloc(cap);
+        for (uint32_t p = 0; a == hipSuccess && like && p < kPlanes; ++p) {
+            failed = kPlaneDesc[p].name;
+            if (like->plane[p]) a = n.plane[p].alloc(cap * kPlaneDesc[p].elem);
+        }
+        return a;
+    });
+    return e == hipSuccess ? nullptr : failed;
 }
 // After a purge that moved slots: the planes k_flow_age does not move itself follow through the slot map
 // it published (c->d_remap).  A plane whose move failed is dropped -- every flow reads as unseen /
@@ -301,18 +349,16 @@ static hipError_t plane_move(const fb_ctx* c, PlaneId p, const uint32_t* remap, 
 static int planes_follow_purge(fb_ctx* c, hipStream_t s) {
     int rc = FB_OK;
     for (uint32_t p = 0; p < kPlanes; ++p) {
-        if (kPlaneDesc[p].age_moves || !c->d_plane[p]) continue;
-        void* nw = nullptr;
-        hipError_t e = hipMalloc(&nw, c->table_cap * kPlaneDesc[p].elem);
-        if (e == hipSuccess) e = plane_move(c, (PlaneId)p, c->d_remap, c->table_cap, s, nw);
+        if (kPlaneDesc[p].age_moves || !c->tb.plane[p]) continue;
+        DevBuf<uint8_t> nw;
+        hipError_t e = nw.alloc(c->tb.cap * kPlaneDesc[p].elem);
+        if (e == hipSuccess) e = plane_move(c, (PlaneId)p, c->d_remap, c->tb.cap, s, nw);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) {
-            hipFree(nw);
-            nw = nullptr;
+            nw.reset();
             if (!rc) rc = set_err(FB_ERR_HIP, "%s remap: %s", kPlaneDesc[p].name, hipGetErrorString(e));
         }
-        hipFree(c->d_plane[p]);
-        c->d_plane[p] = nw;
+        c->tb.plane[p] = std::move(nw);
     }
     return rc;
 }
@@ -322,21 +368,15 @@ static int planes_clear(fb_ctx* c, hipStream_t s) {
         if (kPlaneDesc[p].lazy) HIP_TRY(plane_zero(c, (PlaneId)p, s));
     return FB_OK;
 }
-static void planes_free(fb_ctx* c) {
-    for (void*& p : c->d_plane) {
-        hipFree(p);
-        p = nullptr;
-    }
-}
 // The fb_flow_*_dev getters: min(cap, table capacity) elements; a plane no pass has made reads zeros.
 static int plane_copy_out(fb_ctx* c, PlaneId p, void* d_out, uint64_t cap, void* stream) {
     if (!c || (cap && !d_out)) return set_err(FB_ERR_INVAL, "bad arguments");
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
-    const uint64_t bytes = std::min<uint64_t>(cap, c->table_cap) * kPlaneDesc[p].elem;
+    const uint64_t bytes = std::min<uint64_t>(cap, c->tb.cap) * kPlaneDesc[p].elem;
     if (bytes == 0) return FB_OK;
-    if (c->d_plane[p])
-        HIP_TRY(hipMemcpyAsync(d_out, c->d_plane[p], bytes, hipMemcpyDeviceToDevice, s));
+    if (c->tb.plane[p])
+        HIP_TRY(hipMemcpyAsync(d_out, c->tb.plane[p], bytes, hipMemcpyDeviceToDevice, s));
     else
         HIP_TRY(hipMemsetAsync(d_out, 0, bytes, s));
     return FB_OK;
@@ -348,10 +388,8 @@ static int pass_begin(fb_ctx* c, uint32_t words, hipStream_t s) {
     const int rc = drain_updates(c);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(s));
-    if (!c->d_pass_stats && hipMalloc(&c->d_pass_stats, kPassStatWords * 8ull) != hipSuccess) {
-        c->d_pass_stats = nullptr;
+    if (!c->d_pass_stats && c->d_pass_stats.alloc(kPassStatWords) != hipSuccess)
         return set_err(FB_ERR_NOMEM, "pass counters");
-    }
     HIP_TRY(hipMemsetAsync(c->d_pass_stats, 0, words * 8ull, s));
     return FB_OK;
 }
@@ -376,16 +414,15 @@ static int pass_stamps(fb_ctx* c, hipStream_t s, unsigned long long** mod) {
 template <typename Run>
 static int export_to_host(fb_ctx* c, void* out, uint64_t cap, size_t rec, uint64_t* n, hipStream_t s, const char* what,
                           Run run) {
-    void* d_out = nullptr;
-    if (hipMalloc(&d_out, cap * rec) != hipSuccess) return set_err(FB_ERR_NOMEM, "export buffer");
+    DevBuf<uint8_t> d_out;
+    if (d_out.alloc(cap * rec) != hipSuccess) return set_err(FB_ERR_NOMEM, "export buffer");
     unsigned long long h = 0;
-    const int rc = run(d_out);
+    const int rc = run(d_out.get());
     hipError_t e = rc ? hipSuccess : hipMemcpyAsync(&h, c->d_n, 8, hipMemcpyDeviceToHost, s);
     if (!rc && e == hipSuccess) e = hipStreamSynchronize(s);
     const uint64_t got = std::min<uint64_t>(h, cap);
     if (!rc && e == hipSuccess && got) e = hipMemcpyAsync(out, d_out, got * rec, hipMemcpyDeviceToHost, s);
     if (!rc && e == hipSuccess) e = hipStreamSynchronize(s);
-    hipFree(d_out);
     if (rc) return rc;
     if (e != hipSuccess) return set_err(FB_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
     *n = got;
@@ -398,67 +435,30 @@ bool build_blacklist_tables(const fb_cidr* nets, uint32_t n, std::vector<uint32_
                             std::vector<unsigned long long>& m6);
 }
 
-static EnrichTables enrich_tables(const fb_ctx* c) {
-    EnrichTables t;
-    t.asn4 = c->d_asn4;
-    t.asn6 = c->d_asn6;
-    t.n4 = c->n_asn4;
-    t.n6 = c->n_asn6;
-    t.bl4_pos = c->d_bl4_pos;
-    t.bl4_mask = c->d_bl4_mask;
-    t.bl6_pos = c->d_bl6_pos;
-    t.bl6_mask = c->d_bl6_mask;
-    t.m4 = c->m_bl4;
-    t.m6 = c->m_bl6;
-    return t;
-}
-
-// Replace a device array with a copy of host data (n elements); empty -> nullptr.
+// Replace a device array with a copy of host data (n elements); empty -> an empty buffer.
 template <typename T>
-static int upload_array(T** d, const T* h, size_t n) {
-    if (*d) (void)hipFree(*d);
-    *d = nullptr;
-    if (n == 0) return FB_OK;
-    if (hipMalloc((void**)d, n * sizeof(T)) != hipSuccess) return set_err(FB_ERR_NOMEM, "enrichment table");
-    HIP_TRY(hipMemcpy(*d, h, n * sizeof(T), hipMemcpyHostToDevice));
+static int upload_array(DevBuf<T>& d, const T* h, size_t n) {
+    if (d.alloc(n) != hipSuccess) return set_err(FB_ERR_NOMEM, "enrichment table");
+    if (n) HIP_TRY(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
     return FB_OK;
-}
-
-static void free_upd_scratch(UpdScratch& u) {
-    hipFree(u.entries);
-    hipFree(u.comb);
-    hipFree(u.rows);
-    hipFree(u.cols);
-    hipFree(u.rows_h);
-    hipFree(u.e_orig);
-    hipFree(u.e_sort);
-    hipFree(u.hot);
-    hipFree(u.ctl);
-    hipFree(u.order);
-    u = UpdScratch();
 }
 
 // One update scratch set sized for c->flow_recs records.
 static int alloc_upd_scratch(fb_ctx* c, UpdScratch& u, hipStream_t s) {
-    const uint64_t recs = c->flow_recs, chunks = recs / kFlowChunk;
-    if (hipMalloc(&u.entries, recs * 4ull) != hipSuccess ||
-        hipMalloc(&u.comb, (uint64_t)c->comb_cap * 2ull * sizeof(FlowEntry)) != hipSuccess ||
-        hipMalloc(&u.rows_h, chunks * c->flow_parts * 4ull) != hipSuccess ||
-        hipMalloc(&u.e_orig, recs * 4ull) != hipSuccess || hipMalloc(&u.e_sort, recs * 8ull) != hipSuccess ||
-        hipMalloc(&u.rows, chunks * c->flow_parts * 4ull) != hipSuccess ||
-        hipMalloc(&u.cols, chunks * c->flow_parts * 4ull) != hipSuccess ||
-        hipMalloc(&u.hot, (recs / 16 + 16) * 4ull) != hipSuccess || hipMalloc(&u.ctl, 16) != hipSuccess ||
-        hipMalloc(&u.order, ((uint64_t)c->flow_parts + kK2Lead + 1u) * 4ull) != hipSuccess) {
-        free_upd_scratch(u);
-        return set_err(FB_ERR_NOMEM, "flow update scratch (%llu records)", (unsigned long long)recs);
-    }
+    const uint64_t recs = c->flow_recs, rows = recs / kFlowChunk * c->tb.parts;
+    const hipError_t e = alloc_group(u, [&](UpdScratch& n) {
+        return alloc_each(n.entries, recs, n.comb, (uint64_t)c->comb_cap * 2ull, n.rows_h, rows, n.e_orig, recs, n.e_sort,
+                          recs, n.rows, rows, n.cols, rows, n.hot, recs / 16 + 16, n.ctl, 4,
+                          n.order, (uint64_t)c->tb.parts + kK2Lead + 1u);
+    });
+    if (e != hipSuccess) return set_err(FB_ERR_NOMEM, "flow update scratch (%llu records)", (unsigned long long)recs);
     HIP_TRY(hipMemsetAsync(u.ctl, 0, 16, s));
     return FB_OK;
 }
 
 // Session-table update scratch for batches of up to `recs` records (grown, never shrunk).
 static int ensure_flow_scratch(fb_ctx* c, uint64_t recs, hipStream_t s) {
-    if (!c->d_table) return FB_OK;
+    if (!c->tb.slots) return FB_OK;
     recs = std::max<uint64_t>(recs, kFlowChunk);
     recs = (recs + kFlowChunk - 1) / kFlowChunk * kFlowChunk;
     if (recs <= c->flow_recs) return FB_OK;
@@ -466,28 +466,18 @@ static int ensure_flow_scratch(fb_ctx* c, uint64_t recs, hipStream_t s) {
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     const bool had_set1 = c->us[1].entries != nullptr;
-    for (UpdScratch& u : c->us) free_upd_scratch(u);
-    hipFree(c->d_hword);
-    hipFree(c->d_rec_part);
-    hipFree(c->d_rec_part2);
-    hipFree(c->d_rec_ent);
-    hipFree(c->d_rec_ent2);
-    hipFree(c->d_agg_slot);
-    c->d_rec_part = c->d_rec_part2 = nullptr;
-    c->d_rec_ent = c->d_rec_ent2 = nullptr;
+    for (UpdScratch& u : c->us) u = UpdScratch();
     c->part_recs = nullptr;
     c->part_buf = nullptr;
     c->ent_buf = nullptr;
-    c->d_hword = nullptr;
     c->comb_cap = 0;
-    c->d_agg_slot = nullptr;
     c->last_recs = nullptr;  // its scratch is gone
     c->last_part = nullptr;
     c->flow_recs = 0;
-    if (hipMalloc(&c->d_hword, recs * 4ull) != hipSuccess || hipMalloc(&c->d_rec_part, recs * 4ull) != hipSuccess ||
-        hipMalloc(&c->d_rec_ent, recs * 16ull * kUpdEntU4) != hipSuccess ||
-        hipMalloc(&c->d_agg_slot, (recs / 2 + 1) * 4ull) != hipSuccess)
-        return set_err(FB_ERR_NOMEM, "flow update scratch (%llu records)", (unsigned long long)recs);
+    const hipError_t e = alloc_group(c->rs, [&](RecScratch& r) {
+        return alloc_each(r.hword, recs, r.rec_part, recs, r.rec_ent, recs * kUpdEntU4, r.agg_slot, recs / 2 + 1);
+    });
+    if (e != hipSuccess) return set_err(FB_ERR_NOMEM, "flow update scratch (%llu records)", (unsigned long long)recs);
     c->flow_recs = recs;
     // combined entries: at most one per two records of the hot groups; a quarter of the batch's
     // records is room for any skew we measured (past it a hot group just stays plain)
@@ -502,7 +492,7 @@ static int empty_update(fb_ctx* c);
 static int upload_cfg(fb_ctx* c, hipStream_t s) {
     if (!c->cfg_dirty) return FB_OK;
     HIP_TRY(hipStreamSynchronize(s));  // nothing on this stream may still read d_cfg
-    HIP_TRY(hipMemcpyAsync(c->d_cfg, c->h_cfg, sizeof(DevConfig), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->d_cfg, c->h_cfg.get(), sizeof(DevConfig), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
     c->cfg_dirty = false;
     return FB_OK;
@@ -526,42 +516,29 @@ static uint64_t dense_status_words(uint64_t nseg) { return nseg / parse_dense_ti
 // Scan scratch of the dense entry points, for batches of up to `n` frames (grown, never shrunk).
 static int ensure_compact_scratch(fb_ctx* c, uint64_t n, hipStream_t s) {
     const uint64_t nseg = (n + FB_SEG_FRAMES - 1) / FB_SEG_FRAMES;
-    if (nseg <= c->cseg_cap) return FB_OK;
+    if (nseg <= c->sc.cap) return FB_OK;
     HIP_TRY(hipStreamSynchronize(s));
-    hipFree(c->d_cseg);
-    hipFree(c->d_cpre);
-    hipFree(c->d_cstatus);
-    hipFree(c->d_cticket);
-    hipFree(c->d_dstatus);
-    c->d_cseg = nullptr;
-    c->d_cpre = nullptr;
-    c->d_cstatus = nullptr;
-    c->d_cticket = nullptr;
-    c->d_dstatus = nullptr;
-    c->cseg_cap = 0;
-    c->scan_epoch = 0;
-    c->dense_epoch = 0;
     const uint64_t want = std::max<uint64_t>(nseg, 1024);
-    if (hipMalloc(&c->d_cseg, want * 4ull) != hipSuccess || hipMalloc(&c->d_cpre, want * 8ull) != hipSuccess ||
-        hipMalloc(&c->d_cstatus, seg_scan_tiles((uint32_t)want) * 8ull) != hipSuccess ||
-        hipMalloc(&c->d_cticket, 4) != hipSuccess ||
-        hipMalloc(&c->d_dstatus, dense_status_words(want) * 8ull) != hipSuccess)
-        return set_err(FB_ERR_NOMEM, "dense-output scratch (%llu segments)", (unsigned long long)want);
-    HIP_TRY(hipMemsetAsync(c->d_cticket, 0, 4, s));
-    c->cseg_cap = want;
+    const hipError_t e = alloc_group(c->sc, [&](ScanScratch& n) {
+        return alloc_each(n.cseg, want, n.cpre, want, n.cstatus, seg_scan_tiles((uint32_t)want), n.cticket, 1, n.dstatus,
+                          dense_status_words(want));
+    });
+    if (e != hipSuccess) return set_err(FB_ERR_NOMEM, "dense-output scratch (%llu segments)", (unsigned long long)want);
+    HIP_TRY(hipMemsetAsync(c->sc.cticket, 0, 4, s));
+    c->sc.cap = want;
     return FB_OK;
 }
 
 // The next scan's scratch: a fresh epoch (the status words are zeroed, stream-ordered, when the
 // 8-bit epoch wraps).
 static int scan_scratch(fb_ctx* c, hipStream_t s, SegScanScratch& sc) {
-    if (c->scan_epoch == 0u || c->scan_epoch >= 255u) {
-        HIP_TRY(hipMemsetAsync(c->d_cstatus, 0, seg_scan_tiles((uint32_t)c->cseg_cap) * 8ull, s));
-        c->scan_epoch = 0u;
+    if (c->sc.scan_epoch == 0u || c->sc.scan_epoch >= 255u) {
+        HIP_TRY(hipMemsetAsync(c->sc.cstatus, 0, seg_scan_tiles((uint32_t)c->sc.cap) * 8ull, s));
+        c->sc.scan_epoch = 0u;
     }
-    sc.status = c->d_cstatus;
-    sc.ticket = c->d_cticket;
-    sc.epoch = ++c->scan_epoch;
+    sc.status = c->sc.cstatus;
+    sc.ticket = c->sc.cticket;
+    sc.epoch = ++c->sc.scan_epoch;
     sc.err = c->d_error + (c->epoch & 3u);
     return FB_OK;
 }
@@ -639,22 +616,21 @@ fb_ctx* fb_create(int device, const fb_config* cfg) {
         if (occupancy_parse_dense(&db) != hipSuccess || db < 1) db = 1;
         c->dense_grid = std::min<uint32_t>((uint32_t)(db * prop.multiProcessorCount), 1023u);  // 10-bit stats tickets
     }
-    c->h_cfg = new (std::nothrow) DevConfig();
+    c->h_cfg.reset(new (std::nothrow) DevConfig());
     bool ok = c->h_cfg != nullptr;
     if (ok) {
-        memset(c->h_cfg, 0, sizeof(DevConfig));
+        memset(c->h_cfg.get(), 0, sizeof(DevConfig));
         memcpy(c->h_cfg->service_bitmap, cfg->service_bitmap ? cfg->service_bitmap : kDefaultServiceBitmap,
                FB_SERVICE_BITMAP_BYTES);
         c->h_cfg->filter = cfg->filter;
-        set_lan(c->h_cfg, cfg->lan_v6, cfg->n_lan_v6);
+        set_lan(c->h_cfg.get(), cfg->lan_v6, cfg->n_lan_v6);
         c->h_cfg->n_own = cfg->n_own_ips;
         for (uint32_t i = 0; i < cfg->n_own_ips; ++i) c->h_cfg->own[i] = cfg->own_ips[i];
     }
-    ok = ok && hipMalloc(&c->d_cfg, sizeof(DevConfig)) == hipSuccess;
-    ok = ok && hipMalloc(&c->d_error, 16) == hipSuccess && hipMemset(c->d_error, 0, 16) == hipSuccess;
-    ok = ok && hipMalloc(&c->d_tick, kTickWords * 8ull) == hipSuccess &&
-         hipMemset(c->d_tick, 0, kTickWords * 8ull) == hipSuccess;
-    ok = ok && hipMalloc(&c->d_n, 16) == hipSuccess;
+    ok = ok && c->d_cfg.alloc(1) == hipSuccess;
+    ok = ok && c->d_error.alloc(4) == hipSuccess && hipMemset(c->d_error, 0, 16) == hipSuccess;
+    ok = ok && c->d_tick.alloc(kTickWords) == hipSuccess && hipMemset(c->d_tick, 0, kTickWords * 8ull) == hipSuccess;
+    ok = ok && c->d_n.alloc(2) == hipSuccess;
     if (ok && cfg->flow_capacity > kFlowMaxCapacity) {
         set_err(FB_ERR_INVAL, "flow_capacity %llu > %llu slots", (unsigned long long)cfg->flow_capacity,
                 (unsigned long long)kFlowMaxCapacity);
@@ -663,26 +639,14 @@ fb_ctx* fb_create(int device, const fb_config* cfg) {
     if (ok && cfg->flow_capacity) {
         uint64_t cap = kFlowSlots;
         while (cap < cfg->flow_capacity) cap <<= 1;
-        c->table_cap = cap;
-        c->flow_parts = (uint32_t)(cap / kFlowSlots);
-        uint32_t lg = 0;
-        while ((1u << lg) < c->flow_parts) ++lg;
-        c->flow_shift = 64u - lg;
-        ok = hipMalloc(&c->d_table, cap * sizeof(FlowSlot)) == hipSuccess &&
-             hipMemset(c->d_table, 0, cap * sizeof(FlowSlot)) == hipSuccess &&
-             hipMalloc(&c->d_char_call, cap * sizeof(uint4)) == hipSuccess &&
-             hipMalloc(&c->d_partials, 4ull * c->flow_parts * 8ull) == hipSuccess &&
-             hipMalloc(&c->d_hcount, cap * 4ull) == hipSuccess &&
-             hipMalloc(&c->d_part_base, (c->flow_parts + 1ull) * 4ull) == hipSuccess &&
-             hipMalloc(&c->d_hist_slow, (c->flow_parts + 1ull) * 4ull) == hipSuccess &&
-             hipHostMalloc((void**)&c->h_mbox, sizeof(FlowMailbox), hipHostMallocMapped) == hipSuccess &&
-             hipHostGetDevicePointer((void**)&c->d_mbox, c->h_mbox, 0) == hipSuccess;
-        if (ok) memset(c->h_mbox, 0, sizeof(FlowMailbox));
+        ok = table_alloc(c->tb, cap, nullptr) == nullptr &&
+             hipMemset(c->tb.slots, 0, cap * sizeof(FlowSlot)) == hipSuccess &&
+             c->mbox.alloc(1, hipHostMallocMapped) == hipSuccess;
+        if (ok) memset(c->mbox.get(), 0, sizeof(FlowMailbox));
         c->grow = (cfg->flags & FB_CFG_FIXED_TABLE) == 0u;
         c->timed = (cfg->flags & FB_CFG_TIMED) != 0u;
         if (ok && c->timed)  // (zeroed on the null stream, which upload_cfg below synchronises before the return)
-            ok = plane_ensure(c, kPlaneTime, nullptr) == FB_OK &&
-                 hipEventCreateWithFlags(&c->ev_tscratch, hipEventDisableTiming) == hipSuccess;
+            ok = plane_ensure(c, kPlaneTime, nullptr) == FB_OK;
         ok = ok && ensure_flow_scratch(c, cfg->max_batch_packets, nullptr) == FB_OK;
     }
     ok = ok && upload_cfg(c, nullptr) == FB_OK;
@@ -698,71 +662,7 @@ int fb_destroy(fb_ctx* c) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
     DeviceGuard g(c->device);
     (void)hipDeviceSynchronize();
-    hipFree(c->d_cfg);
-    hipFree(c->d_tick);
-    hipFree(c->d_cseg);
-    hipFree(c->d_cpre);
-    hipFree(c->d_cstatus);
-    hipFree(c->d_cticket);
-    hipFree(c->d_dstatus);
-    hipFree(c->d_error);
-    hipFree(c->d_table);
-    for (UpdScratch& u : c->us) free_upd_scratch(u);
-    hipFree(c->d_partials);
-    hipFree(c->d_remap);
-    hipFree(c->d_char_call);
-    planes_free(c);
-    hipFree(c->d_pass_stats);
-    hipFree(c->d_tscratch);
-    if (c->ev_tscratch) hipEventDestroy(c->ev_tscratch);
-    hipFree(c->d_age_remap);
-    hipFree(c->d_wl_a4);
-    hipFree(c->d_wl_k4);
-    hipFree(c->d_wl_a6);
-    hipFree(c->d_wl_k6);
-    hipFree(c->d_wl_gkey);
-    hipFree(c->d_wl_gbeg);
-    hipFree(c->d_wl_rules);
-    hipFree(c->d_wl_owner);
-    hipFree(c->d_wl_country);
-    hipFree(c->d_an_nodes);
-    hipFree(c->d_an_first);
-    hipFree(c->d_an_service);
     dnstrack_free(c->dns);
-    hipFree(c->d_mscratch);
-    if (c->ev_mscratch) hipEventDestroy(c->ev_mscratch);
-    (void)hipFree(c->d_zeek_tmp);
-    if (c->ev_zeek) (void)hipEventDestroy(c->ev_zeek);
-    if (c->h_mbox) hipHostFree(c->h_mbox);
-    hipFree(c->d_n);
-    hipFree(c->d_hword);
-    hipFree(c->d_rec_part);
-    hipFree(c->d_rec_part2);
-    hipFree(c->d_rec_ent);
-    hipFree(c->d_rec_ent2);
-    hipFree(c->d_agg_slot);
-    if (c->upd) hipStreamDestroy(c->upd);
-    if (c->ev_parsed) hipEventDestroy(c->ev_parsed);
-    if (c->ev_hist) hipEventDestroy(c->ev_hist);
-    for (hipEvent_t e : c->ev_upd)
-        if (e) hipEventDestroy(e);
-    hipFree(c->d_asn4);
-    hipFree(c->d_asn6);
-    hipFree(c->d_bl4_pos);
-    hipFree(c->d_bl4_mask);
-    hipFree(c->d_bl6_pos);
-    hipFree(c->d_bl6_mask);
-    hipFree(c->d_hcount);
-    hipFree(c->d_part_base);
-    hipFree(c->d_hist_slow);
-    hipFree(c->d_hist_cnt);
-    hipFree(c->s_frames);
-    hipFree(c->s_offsets);
-    hipFree(c->s_out);
-    hipFree(c->s_dns);
-    hipFree(c->s_cls);
-    hipFree(c->s_stats);
-    delete c->h_cfg;
     delete c;
     return FB_OK;
 }
@@ -782,7 +682,7 @@ int fb_set_service_bitmap(fb_ctx* c, const uint8_t* bm) {
 
 int fb_set_lan_v6(fb_ctx* c, const fb_lan_v6* nets, uint32_t n) {
     if (!c || n > FB_MAX_LAN_V6 || (n && !nets)) return set_err(FB_ERR_INVAL, "bad lan_v6 table");
-    set_lan(c->h_cfg, nets, n);
+    set_lan(c->h_cfg.get(), nets, n);
     c->cfg_dirty = true;
     return FB_OK;
 }
@@ -870,16 +770,16 @@ static int launch_seg(fb_ctx* c, const SegBatches& sb, uint32_t n_max, const fb_
     c->last_n = n_max;
     ParseParams p;
     memset(&p, 0, sizeof(p));
-    p.pre = c->d_cpre;
+    p.pre = c->sc.cpre;
     p.dense_out = dense_out;
     p.dense_dns = dense_dns;
     p.parsed = parsed;
     p.n = parsed ? sb.b[0].n : 0u;
-    p.rec_part = (want_parts && sb.count == 1u && c->d_table) ? (c->part_target ? c->part_target : c->d_rec_part)
+    p.rec_part = (want_parts && sb.count == 1u && c->tb.slots) ? (c->part_target ? c->part_target : c->rs.rec_part.get())
                                                               : nullptr;
-    p.rec_ent = p.rec_part ? (c->ent_target ? c->ent_target : c->d_rec_ent) : nullptr;
+    p.rec_ent = p.rec_part ? (c->ent_target ? c->ent_target : c->rs.rec_ent.get()) : nullptr;
     p.no_records = p.rec_part && !c->emit_records ? 1u : 0u;
-    p.part_shift = c->flow_shift;
+    p.part_shift = c->tb.shift;
     c->part_recs = p.rec_part ? sb.b[0].out : nullptr;
     c->part_buf = p.rec_part;
     c->ent_buf = p.rec_ent;
@@ -973,16 +873,15 @@ struct fb_seg_queue {
     int device = 0;
     uint32_t depth = 0;  // batches in flight at most
     uint32_t slots = 0;  // ring slots: depth rounded up to a power of two (the kernel masks)
-    hipStream_t stream = nullptr;
-    QueueHost* h = nullptr;      // pinned, coherent host memory (the kernel's ring and completion words)
-    QueueHost* h_dev = nullptr;  // its device alias
-    QueueDev* d_ring = nullptr;  // the device side of the ring
-    DevConfig* d_cfg = nullptr;  // the context's configuration when the queue was created
-    unsigned long long* d_tick = nullptr;
-    uint32_t* d_blk = nullptr;
-    uint32_t* d_head = nullptr;
-    uint32_t* d_err = nullptr;
-    unsigned long long* d_trace = nullptr;  // -DFB_QUEUE_TRACE builds
+    PinnedBuf<QueueHost> h;      // coherent, mapped host memory (the kernel's ring and completion words)
+    DevBuf<QueueDev> d_ring;     // the device side of the ring
+    DevBuf<DevConfig> d_cfg;     // the context's configuration when the queue was created
+    DevBuf<unsigned long long> d_tick;
+    DevBuf<uint32_t> d_blk;
+    DevBuf<uint32_t> d_head;
+    DevBuf<uint32_t> d_err;
+    DevBuf<unsigned long long> d_trace;  // -DFB_QUEUE_TRACE builds
+    DevStream stream;            // (declared after the buffers: destroyed before they are freed)
     uint64_t submitted = 0;
     uint64_t limit = FB_QUEUE_MAX_SUBMISSIONS;  // the kernel's batch numbers are 32-bit (k_parse_seg_queue)
     bool launched = false;
@@ -1003,15 +902,6 @@ static void queue_free(fb_seg_queue* q) {
         std::lock_guard<std::mutex> lk(g_queue_mu);
         --g_queue_live[q->device];
     }
-    if (q->stream) hipStreamDestroy(q->stream);
-    hipFree(q->d_cfg);
-    hipFree(q->d_tick);
-    hipFree(q->d_blk);
-    hipFree(q->d_head);
-    hipFree(q->d_err);
-    hipFree(q->d_ring);
-    hipFree(q->d_trace);
-    if (q->h) hipHostFree(q->h);
     delete q;
 }
 
@@ -1097,25 +987,22 @@ fb_seg_queue* fb_seg_queue_create_ex(fb_ctx* c, uint32_t depth, uint32_t idle_ms
     q->depth = depth;
     q->slots = 1u;
     while (q->slots < depth) q->slots <<= 1;
-    bool ok = hipHostMalloc((void**)&q->h, sizeof(QueueHost), hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess;
-    if (ok) {
-        memset(q->h, 0, sizeof(QueueHost));
-        ok = hipHostGetDevicePointer((void**)&q->h_dev, q->h, 0) == hipSuccess;
-    }
-    ok = ok && hipMalloc(&q->d_cfg, sizeof(DevConfig)) == hipSuccess &&
-         hipMemcpy(q->d_cfg, c->h_cfg, sizeof(DevConfig), hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMalloc(&q->d_tick, kQueueMax * 8u * 8u) == hipSuccess && hipMemset(q->d_tick, 0, kQueueMax * 64u) == hipSuccess;
-    ok = ok && hipMalloc(&q->d_blk, kQueueMax * 4u) == hipSuccess && hipMemset(q->d_blk, 0, kQueueMax * 4u) == hipSuccess;
-    ok = ok && hipMalloc(&q->d_head, kQueueMax * kQueueHeadWords * 4u) == hipSuccess &&
+    bool ok = q->h.alloc(1, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess;
+    if (ok) memset(q->h.get(), 0, sizeof(QueueHost));
+    ok = ok && q->d_cfg.alloc(1) == hipSuccess &&
+         hipMemcpy(q->d_cfg, c->h_cfg.get(), sizeof(DevConfig), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && q->d_tick.alloc(kQueueMax * 8u) == hipSuccess && hipMemset(q->d_tick, 0, kQueueMax * 64u) == hipSuccess;
+    ok = ok && q->d_blk.alloc(kQueueMax) == hipSuccess && hipMemset(q->d_blk, 0, kQueueMax * 4u) == hipSuccess;
+    ok = ok && q->d_head.alloc(kQueueMax * kQueueHeadWords) == hipSuccess &&
          hipMemset(q->d_head, 0, kQueueMax * kQueueHeadWords * 4u) == hipSuccess;
-    ok = ok && hipMalloc(&q->d_err, 4) == hipSuccess && hipMemset(q->d_err, 0, 4) == hipSuccess;
-    ok = ok && hipMalloc(&q->d_ring, sizeof(QueueDev)) == hipSuccess && hipMemset(q->d_ring, 0, sizeof(QueueDev)) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking) == hipSuccess;
+    ok = ok && q->d_err.alloc(1) == hipSuccess && hipMemset(q->d_err, 0, 4) == hipSuccess;
+    ok = ok && q->d_ring.alloc(1) == hipSuccess && hipMemset(q->d_ring, 0, sizeof(QueueDev)) == hipSuccess;
+    ok = ok && q->stream.create() == hipSuccess;
 #ifdef FB_QUEUE_TRACE
     if (ok) {
         std::vector<unsigned long long> t0((size_t)kQTraceAll, 0ull);
         std::fill(t0.begin() + kQtFirst * kQTraceN, t0.begin() + (kQtArr0 + 1) * kQTraceN, ~0ull);
-        ok = hipMalloc(&q->d_trace, t0.size() * 8u) == hipSuccess &&
+        ok = q->d_trace.alloc(t0.size()) == hipSuccess &&
              hipMemcpy(q->d_trace, t0.data(), t0.size() * 8u, hipMemcpyHostToDevice) == hipSuccess;
     }
 #endif
@@ -1126,7 +1013,7 @@ fb_seg_queue* fb_seg_queue_create_ex(fb_ctx* c, uint32_t depth, uint32_t idle_ms
     }
     QueueParams p;
     p.cfg = q->d_cfg;
-    p.h = q->h_dev;
+    p.h = q->h.dev();
     p.d = q->d_ring;
     p.tick = q->d_tick;
     p.blk_done = q->d_blk;
@@ -1300,7 +1187,7 @@ int fb_seg_compact_dev(fb_ctx* c, const fb_pkt_out* d_seg_out, const uint32_t* d
     SegScanScratch sc;
     rc = scan_scratch(c, s, sc);
     if (rc) return rc;
-    HIP_TRY(launch_seg_compact(d_seg_out, d_seg, (n + FB_SEG_FRAMES - 1) / FB_SEG_FRAMES, c->d_cpre, sc, d_out, d_dns,
+    HIP_TRY(launch_seg_compact(d_seg_out, d_seg, (n + FB_SEG_FRAMES - 1) / FB_SEG_FRAMES, c->sc.cpre, sc, d_out, d_dns,
                                s));
     return FB_OK;
 }
@@ -1321,9 +1208,9 @@ static int parse_dense_single(fb_ctx* c, const uint8_t* d_frames, uint64_t frame
     if (!rc) rc = ensure_compact_scratch(c, n, s);
     if (rc) return rc;
     const uint32_t nseg = (n + FB_SEG_FRAMES - 1) / FB_SEG_FRAMES;
-    if (c->dense_epoch == 0u || c->dense_epoch >= 255u) {
-        HIP_TRY(hipMemsetAsync(c->d_dstatus, 0, dense_status_words(c->cseg_cap) * 8ull, s));
-        c->dense_epoch = 0u;
+    if (c->sc.dense_epoch == 0u || c->sc.dense_epoch >= 255u) {
+        HIP_TRY(hipMemsetAsync(c->sc.dstatus, 0, dense_status_words(c->sc.cap) * 8ull, s));
+        c->sc.dense_epoch = 0u;
     }
     c->last_n = n;
     c->part_recs = nullptr;
@@ -1339,7 +1226,7 @@ static int parse_dense_single(fb_ctx* c, const uint8_t* d_frames, uint64_t frame
     p.error_next = c->d_error + ((launch + 1u) & 3u);
     p.dense_out = d_out;
     p.dense_dns = d_dns;
-    p.dstatus = c->d_dstatus;
+    p.dstatus = c->sc.dstatus;
     p.steal_polls = c->steal_polls;
     p.dn_skew = c->dn_skew;
 #ifdef FB_DN_TRACE
@@ -1349,7 +1236,7 @@ static int parse_dense_single(fb_ctx* c, const uint8_t* d_frames, uint64_t frame
     HIP_TRY(hipMemsetAsync(g_dtrace, 0, 8u * 4u * (8192u + 1024u), s));
     p.dtrace = g_dtrace;
 #endif
-    p.dep = ++c->dense_epoch;
+    p.dep = ++c->sc.dense_epoch;
     p.ntiles = (nseg + parse_dense_tile_segs() - 1) / parse_dense_tile_segs();
     const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(c->dense_grid, p.ntiles));
     SegBatch b;
@@ -1376,14 +1263,14 @@ static int parse_dense(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes
 #endif
     int rc = ensure_compact_scratch(c, n, s);
     if (rc) return rc;
-    rc = launch_seg(c, one_batch(d_frames, frames_bytes, d_offsets, n, nullptr, c->d_cseg, d_class, d_stats), n, d_in,
+    rc = launch_seg(c, one_batch(d_frames, frames_bytes, d_offsets, n, nullptr, c->sc.cseg, d_class, d_stats), n, d_in,
                     s, false, SegPass::kCount);
     if (rc || (!d_out && !d_dns)) return rc;
     const uint32_t nseg = (n + FB_SEG_FRAMES - 1) / FB_SEG_FRAMES;
     SegScanScratch sc;
     rc = scan_scratch(c, s, sc);
     if (rc) return rc;
-    HIP_TRY(launch_seg_scan(c->d_cseg, nseg, c->d_cpre, sc, s));
+    HIP_TRY(launch_seg_scan(c->sc.cseg, nseg, c->sc.cpre, sc, s));
     return launch_seg(c, one_batch(d_frames, frames_bytes, d_offsets, n, nullptr, nullptr, nullptr, nullptr), n, d_in, s,
                       false, SegPass::kDenseOut, d_out, d_dns);
 }
@@ -1411,28 +1298,17 @@ int fb_process_parsed_dev(fb_ctx* c, const fb_parsed_pkt* d_in, uint32_t n, fb_p
 }
 
 static int ensure_staging(fb_ctx* c, uint64_t n, uint64_t bytes) {
-    if (bytes > c->s_frames_cap) {
-        hipFree(c->s_frames);
-        c->s_frames = nullptr;
-        c->s_frames_cap = 0;
-        uint64_t want = std::max<uint64_t>(bytes, 1 << 20);
-        if (hipMalloc(&c->s_frames, want) != hipSuccess) return set_err(FB_ERR_NOMEM, "staging frames");
-        c->s_frames_cap = want;
+    Staging& st = c->st;
+    if (bytes > st.frames.size() && st.frames.alloc(std::max<uint64_t>(bytes, 1 << 20)) != hipSuccess)
+        return set_err(FB_ERR_NOMEM, "staging frames");
+    if (n > st.pk.cls.size()) {
+        const uint64_t want = std::max<uint64_t>(n, 4096);
+        const hipError_t e = alloc_group(st.pk, [&](Staging::Pkts& p) {
+            return alloc_each(p.offsets, want + 1, p.out, want, p.dns, want, p.cls, want);
+        });
+        if (e != hipSuccess) return set_err(FB_ERR_NOMEM, "staging packets");
     }
-    if (n > c->s_pkts_cap) {
-        hipFree(c->s_offsets); hipFree(c->s_out); hipFree(c->s_dns); hipFree(c->s_cls);
-        c->s_offsets = nullptr; c->s_out = nullptr; c->s_dns = nullptr; c->s_cls = nullptr;
-        c->s_pkts_cap = 0;
-        uint64_t want = std::max<uint64_t>(n, 4096);
-        if (hipMalloc(&c->s_offsets, (want + 1) * 4) != hipSuccess ||
-            hipMalloc(&c->s_out, want * sizeof(fb_pkt_out)) != hipSuccess ||
-            hipMalloc(&c->s_dns, want * sizeof(fb_dns_out)) != hipSuccess ||
-            hipMalloc(&c->s_cls, want) != hipSuccess)
-            return set_err(FB_ERR_NOMEM, "staging packets");
-        c->s_pkts_cap = want;
-    }
-    if (!c->s_stats && hipMalloc(&c->s_stats, sizeof(fb_batch_stats)) != hipSuccess)
-        return set_err(FB_ERR_NOMEM, "staging stats");
+    if (!st.stats && st.stats.alloc(1) != hipSuccess) return set_err(FB_ERR_NOMEM, "staging stats");
     return FB_OK;
 }
 
@@ -1455,20 +1331,20 @@ int fb_parse_classify(fb_ctx* c, const uint8_t* frames, uint64_t frames_bytes, c
     hipStream_t s = (hipStream_t)stream;
     int rc = ensure_staging(c, n, frames_bytes);
     if (rc) return rc;
-    if (frames_bytes) HIP_TRY(hipMemcpyAsync(c->s_frames, frames, frames_bytes, hipMemcpyHostToDevice, s));
-    if (n) HIP_TRY(hipMemcpyAsync(c->s_offsets, offsets, (uint64_t)(n + 1) * 4, hipMemcpyHostToDevice, s));
-    rc = fb_parse_classify_dev(c, c->s_frames, frames_bytes, c->s_offsets, n, out ? c->s_out : nullptr,
-                               dns ? c->s_dns : nullptr, cls ? c->s_cls : nullptr, c->s_stats, s);
+    if (frames_bytes) HIP_TRY(hipMemcpyAsync(c->st.frames, frames, frames_bytes, hipMemcpyHostToDevice, s));
+    if (n) HIP_TRY(hipMemcpyAsync(c->st.pk.offsets, offsets, (uint64_t)(n + 1) * 4, hipMemcpyHostToDevice, s));
+    rc = fb_parse_classify_dev(c, c->st.frames, frames_bytes, c->st.pk.offsets, n, out ? c->st.pk.out.get() : nullptr,
+                               dns ? c->st.pk.dns.get() : nullptr, cls ? c->st.pk.cls.get() : nullptr, c->st.stats, s);
     if (rc) return rc;
     fb_batch_stats st;
-    HIP_TRY(hipMemcpyAsync(&st, c->s_stats, sizeof(st), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&st, c->st.stats, sizeof(st), hipMemcpyDeviceToHost, s));
     rc = check_error_word(c, s);  // synchronises the stream
     if (rc) return rc;
     if (out && st.n_session)
-        HIP_TRY(hipMemcpyAsync(out, c->s_out, st.n_session * sizeof(fb_pkt_out), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out, c->st.pk.out, st.n_session * sizeof(fb_pkt_out), hipMemcpyDeviceToHost, s));
     if (dns && st.n_dns)
-        HIP_TRY(hipMemcpyAsync(dns, c->s_dns, st.n_dns * sizeof(fb_dns_out), hipMemcpyDeviceToHost, s));
-    if (cls && n) HIP_TRY(hipMemcpyAsync(cls, c->s_cls, n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(dns, c->st.pk.dns, st.n_dns * sizeof(fb_dns_out), hipMemcpyDeviceToHost, s));
+    if (cls && n) HIP_TRY(hipMemcpyAsync(cls, c->st.pk.cls, n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (n_out) *n_out = (uint32_t)st.n_session;
     if (n_dns) *n_dns = (uint32_t)st.n_dns;
@@ -1481,30 +1357,30 @@ int fb_process_parsed(fb_ctx* c, const fb_parsed_pkt* in, uint32_t n, fb_pkt_out
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
     if (n > FB_MAX_BATCH_PACKETS) return set_err(FB_ERR_INVAL, "n too large");
     if (n && !in) return set_err(FB_ERR_INVAL, "NULL input");
-    if (c->d_table) {
+    if (c->tb.slots) {
         if (int rc = timed_ready(c)) return rc;
     }
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     int rc = ensure_staging(c, n, (uint64_t)n * sizeof(fb_parsed_pkt));
     if (rc) return rc;
-    const fb_parsed_pkt* d_in = reinterpret_cast<const fb_parsed_pkt*>(c->s_frames);
-    if (n) HIP_TRY(hipMemcpyAsync(c->s_frames, in, (uint64_t)n * sizeof(fb_parsed_pkt), hipMemcpyHostToDevice, s));
-    rc = fb_process_parsed_dev(c, d_in, n, c->s_out, cls ? c->s_cls : nullptr, c->s_stats, s);
+    const fb_parsed_pkt* d_in = reinterpret_cast<const fb_parsed_pkt*>(c->st.frames.get());
+    if (n) HIP_TRY(hipMemcpyAsync(c->st.frames, in, (uint64_t)n * sizeof(fb_parsed_pkt), hipMemcpyHostToDevice, s));
+    rc = fb_process_parsed_dev(c, d_in, n, c->st.pk.out, cls ? c->st.pk.cls.get() : nullptr, c->st.stats, s);
     if (rc) return rc;
-    if (n && c->d_table) {
-        rc = fb_flow_update_dev(c, c->s_out, c->s_stats, s);
+    if (n && c->tb.slots) {
+        rc = fb_flow_update_dev(c, c->st.pk.out, c->st.stats, s);
         if (rc) return rc;
-    } else if (c->d_table) {
+    } else if (c->tb.slots) {
         empty_update(c);
     }
     fb_batch_stats st;
-    HIP_TRY(hipMemcpyAsync(&st, c->s_stats, sizeof(st), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&st, c->st.stats, sizeof(st), hipMemcpyDeviceToHost, s));
     rc = check_error_word(c, s);  // synchronises the stream
     if (rc) return rc;
     if (out && st.n_session)
-        HIP_TRY(hipMemcpyAsync(out, c->s_out, st.n_session * sizeof(fb_pkt_out), hipMemcpyDeviceToHost, s));
-    if (cls && n) HIP_TRY(hipMemcpyAsync(cls, c->s_cls, n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out, c->st.pk.out, st.n_session * sizeof(fb_pkt_out), hipMemcpyDeviceToHost, s));
+    if (cls && n) HIP_TRY(hipMemcpyAsync(cls, c->st.pk.cls, n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (n_out) *n_out = (uint32_t)st.n_session;
     if (stats) *stats = st;
@@ -1523,67 +1399,30 @@ static int empty_update(fb_ctx* c) {
 // ---- table growth -------------------------------------------------------------------------------
 // Doubles the table on the device: every slot re-inserted into 2x partitions (k_flow_grow), the old
 // -> new slot map kept for fb_flow_slot_remap.  Drains the updates in flight first: growth is rare.
-// Every buffer of the grown table is held by a Grown until the growth is complete; only then are the
-// context's pointers swapped in (the Grown then holds the old buffers), and whatever it holds when it
-// goes out of scope is freed -- a failed growth leaves the context as it was.
-namespace {
-struct Grown {
-    FlowSlot* table = nullptr;
-    unsigned long long* partials = nullptr;
-    uint32_t *hcount = nullptr, *part_base = nullptr, *hist_slow = nullptr, *remap = nullptr;
-    uint4* char_call = nullptr;
-    void* plane[kPlanes] = {};
-    ~Grown() {
-        for (void* p : {(void*)table, (void*)partials, (void*)hcount, (void*)part_base, (void*)hist_slow, (void*)remap,
-                        (void*)char_call})
-            hipFree(p);
-        for (void* p : plane) hipFree(p);
-    }
-};
-}  // namespace
+// The grown table is a second FlowTable, and the slot map a buffer of its own, until the growth is
+// complete; only then are they swapped with the context's, which leave with this scope -- a failed growth
+// leaves the context as it was.
 static int grow_table(fb_ctx* c, hipStream_t s, uint32_t k) {
     int rc = drain_updates(c);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(s));
-    const uint64_t cap = c->table_cap << k, parts = cap / kFlowSlots;
-    Grown g;
-    if (hipMalloc(&g.table, cap * sizeof(FlowSlot)) != hipSuccess) return set_err(FB_ERR_NOMEM, "grown flow table");
-    if (hipMalloc(&g.partials, 4ull * parts * 8ull) != hipSuccess || hipMalloc(&g.hcount, cap * 4ull) != hipSuccess ||
-        hipMalloc(&g.part_base, (parts + 1ull) * 4ull) != hipSuccess ||
-        hipMalloc(&g.hist_slow, (parts + 1ull) * 4ull) != hipSuccess)
-        return set_err(FB_ERR_NOMEM, "grown flow table partials");
-    if (hipMalloc(&g.remap, c->table_cap * 4ull) != hipSuccess) return set_err(FB_ERR_NOMEM, "slot remap");
-    if (hipMalloc(&g.char_call, cap * sizeof(uint4)) != hipSuccess)
-        return set_err(FB_ERR_NOMEM, "grown character-call array");
-    HIP_TRY(hipMemsetAsync(g.table, 0, cap * sizeof(FlowSlot), s));
-    HIP_TRY(launch_flow_grow(c->d_table, c->flow_parts, k, c->flow_shift - k, g.table, g.remap, c->d_char_call,
-                             g.char_call, s));
-    for (uint32_t p = 0; p < kPlanes; ++p) {  // every plane made so far follows its flows' new slots
-        if (!c->d_plane[p]) continue;
-        if (hipMalloc(&g.plane[p], cap * kPlaneDesc[p].elem) != hipSuccess)
-            return set_err(FB_ERR_NOMEM, "grown %s", kPlaneDesc[p].name);
-        HIP_TRY(plane_move(c, (PlaneId)p, g.remap, cap, s, g.plane[p]));
-    }
+    FlowTable nw;
+    DevBuf<uint32_t> remap;
+    if (const char* what = table_alloc(nw, c->tb.cap << k, &c->tb)) return set_err(FB_ERR_NOMEM, "grown %s", what);
+    if (remap.alloc(c->tb.cap) != hipSuccess) return set_err(FB_ERR_NOMEM, "slot remap");
+    HIP_TRY(hipMemsetAsync(nw.slots, 0, nw.cap * sizeof(FlowSlot), s));
+    HIP_TRY(launch_flow_grow(c->tb.slots, c->tb.parts, k, nw.shift, nw.slots, remap, c->tb.char_call, nw.char_call, s));
+    for (uint32_t p = 0; p < kPlanes; ++p)  // every plane made so far follows its flows' new slots
+        if (c->tb.plane[p]) HIP_TRY(plane_move(c, (PlaneId)p, remap, nw.cap, s, nw.plane[p]));
     HIP_TRY(hipStreamSynchronize(s));
-    std::swap(c->d_table, g.table);
-    std::swap(c->d_partials, g.partials);
-    std::swap(c->d_hcount, g.hcount);
-    std::swap(c->d_part_base, g.part_base);
-    std::swap(c->d_hist_slow, g.hist_slow);
-    std::swap(c->d_remap, g.remap);
-    std::swap(c->d_char_call, g.char_call);
-    for (uint32_t p = 0; p < kPlanes; ++p)
-        if (g.plane[p]) std::swap(c->d_plane[p], g.plane[p]);
-    c->remap_n = c->table_cap;
-    c->table_cap = cap;
-    c->flow_parts <<= k;
-    c->flow_shift -= k;
+    std::swap(c->tb, nw);
+    c->d_remap.swap(remap);
     c->grown_seq = c->upd_seq;
     ++c->generation;
     // scratch sized by the partition count (K1 rows / K2 columns), history sort bits: rebuilt
     const uint64_t recs = c->flow_recs;
     const bool had_set1 = c->us[1].entries != nullptr;
-    for (UpdScratch& u : c->us) free_upd_scratch(u);
+    for (UpdScratch& u : c->us) u = UpdScratch();
     c->flow_recs = 0;
     rc = ensure_flow_scratch(c, recs, s);
     if (!rc && had_set1) rc = alloc_upd_scratch(c, c->us[1], s);
@@ -1605,8 +1444,8 @@ static int grow_table(fb_ctx* c, hipStream_t s, uint32_t k) {
 static constexpr uint64_t kGrowPart = kFlowSlots * 7u / 8u;
 static constexpr double kMailboxWaitS = 120.0;
 static int maybe_grow(fb_ctx* c, hipStream_t s) {
-    if (!c->d_table || !c->grow || c->part_recs) return FB_OK;  // (a fused parse already bucketed for this geometry)
-    const volatile FlowMailbox* m = c->h_mbox;
+    if (!c->tb.slots || !c->grow || c->part_recs) return FB_OK;  // (a fused parse already bucketed for this geometry)
+    const volatile FlowMailbox* m = c->mbox;
     const uint64_t issued = c->upd_seq - c->clear_seq;              // updates since create / clear
     const uint64_t need = c->clear_seq + (issued >= 2u ? issued - 1u : issued);
     uint64_t seq = __atomic_load_n(&m->seq, __ATOMIC_ACQUIRE);
@@ -1626,15 +1465,15 @@ static int maybe_grow(fb_ctx* c, hipStream_t s) {
     // the smallest k (table x 2^k) that holds the projection: one growth (one slot remap) per call
     uint32_t k = 0;
     for (;; ++k) {
-        const uint64_t parts = (uint64_t)c->flow_parts << k;
-        if ((c->table_cap << k) > kFlowMaxCapacity || k > 5u) {
+        const uint64_t parts = (uint64_t)c->tb.parts << k;
+        if ((c->tb.cap << k) > kFlowMaxCapacity || k > 5u) {
             if (k > 0) --k;
             break;
         }
         // a report from before a growth describes other partitions: only its flow count is used there
         const uint64_t maxp = (k == 0 && seq > c->grown_seq) ? m->max_part : flows / parts + 3u * kFlowSlots / 16u;
         const uint64_t add = (ahead * newf + parts - 1u) / parts;
-        if (maxp + add + kFlowSlots / 32u <= kGrowPart && flows + ahead * newf <= (c->table_cap << k) * 3u / 4u) break;
+        if (maxp + add + kFlowSlots / 32u <= kGrowPart && flows + ahead * newf <= (c->tb.cap << k) * 3u / 4u) break;
     }
     return k ? grow_table(c, s, k) : FB_OK;
 }
@@ -1646,7 +1485,7 @@ static int maybe_grow(fb_ctx* c, hipStream_t s) {
 static int flow_update(fb_ctx* c, const fb_pkt_out* d_recs, const uint32_t* d_seg, uint32_t n_slots,
                        fb_batch_stats* d_stats, hipStream_t s, bool split = false, hipStream_t s_bucket = nullptr,
                        uint32_t set = 0) {
-    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     DeviceGuard g(c->device);
     if (!split) s_bucket = s;
     int rc = split ? FB_OK : join_updates(c, s);
@@ -1667,54 +1506,46 @@ static int flow_update(fb_ctx* c, const fb_pkt_out* d_recs, const uint32_t* d_se
     p.seg = d_seg;
     p.n_slots = n_slots;
     p.stats = d_stats;
-    p.table = c->d_table;
+    p.table = c->tb.slots;
     p.entries = u.entries;
     p.comb = u.comb;
     p.comb_cap = c->comb_cap;
     p.rows = u.rows;
     p.cols = u.cols;
-    p.partials = c->d_partials;
+    p.partials = c->tb.partials;
     p.error = c->d_error + (c->epoch & 3u);
     p.max_recs = (uint32_t)std::min<uint64_t>((uint64_t)chunks * kFlowChunk, c->flow_recs);
-    p.parts = c->flow_parts;
-    p.part_shift = c->flow_shift;
+    p.parts = c->tb.parts;
+    p.part_shift = c->tb.shift;
     p.chunk_stride = (uint32_t)(c->flow_recs / kFlowChunk);
     p.batch = c->flow_batch;
     p.rows_h = u.rows_h;
     p.e_orig = u.e_orig;
     p.e_sort = u.e_sort;
-    p.hcount = c->d_hcount;
-    p.part_base = c->d_part_base;
-    p.hword = c->d_hword;
+    p.hcount = c->tb.hcount;
+    p.part_base = c->tb.part_base;
+    p.hword = c->rs.hword;
     p.hot = u.hot;
     p.ctl = u.ctl;
 #ifndef FB_K2_ORDER
 #define FB_K2_ORDER 1
 #endif
-    p.order = FB_K2_ORDER ? u.order : nullptr;
-    p.agg_slot = c->d_agg_slot;
+    p.order = FB_K2_ORDER ? u.order.get() : nullptr;
+    p.agg_slot = c->rs.agg_slot;
     p.hot_cap = (uint32_t)(c->flow_recs / 16 + 16);
     p.rec_part = (d_seg && c->part_recs == d_recs) ? c->part_buf : nullptr;  // written by this batch's parse
     p.ent = p.rec_part ? c->ent_buf : nullptr;                                  // (with its update entries)
-    p.char_call = c->d_char_call;
+    p.char_call = c->tb.char_call;
     c->part_recs = nullptr;
     if (c->timed) {  // the capture-time pass's scratch (K2 writes its sort input into it)
         const uint32_t slots = p.max_recs < n_slots ? p.max_recs : n_slots;
         uint32_t bits = 0;
-        while ((1ull << bits) < c->table_cap) ++bits;
+        while ((1ull << bits) < c->tb.cap) ++bits;
         const uint64_t need = time_scratch_bytes(slots, bits);
-        HIP_TRY(hipStreamWaitEvent(s, c->ev_tscratch, 0));
-        if (need > c->tscratch_bytes) {
-            HIP_TRY(hipEventSynchronize(c->ev_tscratch));
-            hipFree(c->d_tscratch);
-            c->d_tscratch = nullptr;
-            c->tscratch_bytes = 0;
-            if (hipMalloc(&c->d_tscratch, need) != hipSuccess)
-                return set_err(FB_ERR_NOMEM, "capture-time scratch (%llu bytes)", (unsigned long long)need);
-            c->tscratch_bytes = need;
-        }
-        p.tkv = time_key_array(c->d_tscratch);
-        HIP_TRY(launch_time_prepare(c->d_tscratch, slots, s));
+        rc = c->tscratch.acquire(need, s, "capture-time scratch");
+        if (rc) return rc;
+        p.tkv = time_key_array(c->tscratch.get());
+        HIP_TRY(launch_time_prepare(c->tscratch.get(), slots, s));
         p.hot = nullptr;  // no combined entries: every record is a plain entry K2 places
     }
     HIP_TRY(launch_flow_bucket(p, chunks, s_bucket));
@@ -1725,12 +1556,13 @@ static int flow_update(fb_ctx* c, const fb_pkt_out* d_recs, const uint32_t* d_se
         HIP_TRY(hipStreamWaitEvent(s, c->ev_parsed, 0));
     }
     HIP_TRY(launch_flow_apply(p, chunks, s));
-    HIP_TRY(launch_flow_finish(d_stats, c->d_partials, c->flow_parts, c->d_error + (c->epoch & 3u), c->d_mbox,
+    HIP_TRY(launch_flow_finish(d_stats, c->tb.partials, c->tb.parts, c->d_error + (c->epoch & 3u), c->mbox.dev(),
                                ++c->upd_seq, s));
     if (c->timed) {  // the capture-time pass over the placed records (fb_time.hip)
         const uint32_t slots = p.max_recs < n_slots ? p.max_recs : n_slots;
-        HIP_TRY(launch_time_update(p, slots, c->table_cap, c->plane<FlowTime>(kPlaneTime), c->next_ts, c->d_tscratch, s));
-        HIP_TRY(hipEventRecord(c->ev_tscratch, s));
+        HIP_TRY(launch_time_update(p, slots, c->tb.cap, c->plane<FlowTime>(kPlaneTime), c->next_ts, c->tscratch.get(), s));
+        rc = c->tscratch.release(s);
+        if (rc) return rc;
         c->next_ts = nullptr;
     }
     ++c->flow_batch;
@@ -1774,7 +1606,7 @@ int fb_process_seg_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes
                        uint32_t n, fb_pkt_out* d_out, uint32_t* d_seg, uint8_t* d_class, fb_batch_stats* d_stats,
                        void* stream) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
-    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     int rc = timed_ready(c);
     if (rc) return rc;
     {
@@ -1797,25 +1629,21 @@ int fb_process_seg_async_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames
                              uint32_t n, fb_pkt_out* d_out, uint32_t* d_seg, uint8_t* d_class,
                              fb_batch_stats* d_stats, void* stream) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
-    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     if (n > FB_MAX_BATCH_PACKETS) return set_err(FB_ERR_INVAL, "n %u > FB_MAX_BATCH_PACKETS", n);
     if (int rc = timed_ready(c)) return rc;
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
-    if (!c->upd) {
-        if (hipStreamCreateWithFlags(&c->upd, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_parsed, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_upd[0], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_upd[1], hipEventDisableTiming) != hipSuccess)
-            return set_err(FB_ERR_HIP, "update stream / events");
-    }
+    if (!c->upd && (c->upd.create() != hipSuccess || c->ev_parsed.create() != hipSuccess ||
+                    c->ev_upd[0].create() != hipSuccess || c->ev_upd[1].create() != hipSuccess))
+        return set_err(FB_ERR_HIP, "update stream / events");
     const uint32_t slot = (uint32_t)(c->async_k & 1u);
     int rc = maybe_grow(c, s);  // before this batch's parse writes partitions (drains the pipeline if it grows)
     if (!rc) rc = ensure_flow_scratch(c, (n + FB_SEG_FRAMES - 1) / FB_SEG_FRAMES * FB_SEG_FRAMES, s);
     if (rc) return rc;
-    if (!c->d_rec_part2 && hipMalloc(&c->d_rec_part2, c->flow_recs * 4ull) != hipSuccess)
+    if (!c->rs.rec_part2 && c->rs.rec_part2.alloc(c->flow_recs) != hipSuccess)
         return set_err(FB_ERR_NOMEM, "second partition buffer");
-    if (!c->d_rec_ent2 && hipMalloc(&c->d_rec_ent2, c->flow_recs * 16ull * kUpdEntU4) != hipSuccess)
+    if (!c->rs.rec_ent2 && c->rs.rec_ent2.alloc(c->flow_recs * kUpdEntU4) != hipSuccess)
         return set_err(FB_ERR_NOMEM, "second update-entry buffer");
     // the same slot's previous batch (k-2): its update must be done before this parse rewrites the
     // slot's partition buffer; before any async batch, the last synchronous update is on `s` already
@@ -1824,8 +1652,8 @@ int fb_process_seg_async_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames
     // update too (no overlap: rotate two buffer sets to get it)
     if (c->async_k >= 1 && (d_out == c->async_prev[0] || d_seg == c->async_prev[1] || d_stats == c->async_prev[2]))
         HIP_TRY(hipStreamWaitEvent(s, c->ev_upd[slot ^ 1u], 0));
-    c->part_target = slot ? c->d_rec_part2 : c->d_rec_part;
-    c->ent_target = slot ? c->d_rec_ent2 : c->d_rec_ent;
+    c->part_target = slot ? c->rs.rec_part2.get() : c->rs.rec_part.get();
+    c->ent_target = slot ? c->rs.rec_ent2.get() : c->rs.rec_ent.get();
     const uint32_t grid_full = c->seg_grid;
     c->seg_grid = c->seg_grid_async;
     rc = parse_seg(c, d_frames, frames_bytes, d_offsets, n, d_out, d_seg, d_class, d_stats, stream, true);
@@ -1861,7 +1689,7 @@ int fb_process_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes, co
                    uint32_t n, fb_pkt_out* d_out, fb_dns_out* d_dns, uint8_t* d_class,
                    fb_batch_stats* d_stats, void* stream) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
-    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     if (!d_out) return set_err(FB_ERR_INVAL, "d_out is required");
     if (int rc = timed_ready(c)) return rc;
     int rc = fb_parse_classify_dev(c, d_frames, frames_bytes, d_offsets, n, d_out, d_dns, d_class, d_stats, stream);
@@ -1873,7 +1701,7 @@ int fb_process_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes, co
 
 int fb_flow_history_dev(fb_ctx* c, uint8_t* d_hist, uint32_t* d_hist_slot, uint32_t* d_n_hist, void* stream) {
     if (!c || !d_n_hist) return set_err(FB_ERR_INVAL, "ctx and d_n_hist are required");
-    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     int jr = join_updates(c, s);
@@ -1885,19 +1713,14 @@ int fb_flow_history_dev(fb_ctx* c, uint8_t* d_hist, uint32_t* d_hist_slot, uint3
     }
     if (!d_hist || !d_hist_slot) return set_err(FB_ERR_INVAL, "d_hist and d_hist_slot are required");
     const uint64_t cnt_bytes = flow_history_cnt_bytes(c->last_chunks);
-    if (cnt_bytes > c->hist_cnt_bytes) {
+    if (cnt_bytes > c->d_hist_cnt.size()) {
         HIP_TRY(hipStreamSynchronize(s));
-        hipFree(c->d_hist_cnt);
-        c->d_hist_cnt = nullptr;
-        c->hist_cnt_bytes = 0;
-        if (hipMalloc(&c->d_hist_cnt, cnt_bytes) != hipSuccess)
+        if (c->d_hist_cnt.alloc(cnt_bytes) != hipSuccess)
             return set_err(FB_ERR_NOMEM, "history block counts (%llu bytes)", (unsigned long long)cnt_bytes);
-        c->hist_cnt_bytes = cnt_bytes;
     }
-    if (!c->ev_hist && hipEventCreateWithFlags(&c->ev_hist, hipEventDisableTiming) != hipSuccess)
-        return set_err(FB_ERR_HIP, "history event");
-    HIP_TRY(launch_flow_history(c->last_p, c->last_chunks, d_hist_slot, d_hist, d_n_hist, c->d_hist_slow,
-                                cnt_bytes ? c->d_hist_cnt : nullptr, s));
+    if (c->ev_hist.create() != hipSuccess) return set_err(FB_ERR_HIP, "history event");
+    HIP_TRY(launch_flow_history(c->last_p, c->last_chunks, d_hist_slot, d_hist, d_n_hist, c->tb.hist_slow,
+                                cnt_bytes ? reinterpret_cast<uint32_t*>(c->d_hist_cnt.get()) : nullptr, s));
     HIP_TRY(hipEventRecord(c->ev_hist, s));
     c->hist_pending = true;
     return FB_OK;
@@ -1932,10 +1755,10 @@ int fb_set_asn_tables(fb_ctx* c, const fb_asn_range* v4, uint32_t n4, const fb_a
         if (asn_valid(v6[i], true)) a6.push_back(v6[i]);
     std::stable_sort(a4.begin(), a4.end(), [](const fb_asn_range& x, const fb_asn_range& y) { return asn_less(x, y, false); });
     std::stable_sort(a6.begin(), a6.end(), [](const fb_asn_range& x, const fb_asn_range& y) { return asn_less(x, y, true); });
-    int rc = upload_array(&c->d_asn4, a4.data(), a4.size());
-    if (!rc) rc = upload_array(&c->d_asn6, a6.data(), a6.size());
-    c->n_asn4 = rc ? 0 : (uint32_t)a4.size();
-    c->n_asn6 = rc ? 0 : (uint32_t)a6.size();
+    int rc = upload_array(c->en.asn4, a4.data(), a4.size());
+    if (!rc) rc = upload_array(c->en.asn6, a6.data(), a6.size());
+    c->en.n4 = rc ? 0 : (uint32_t)a4.size();
+    c->en.n6 = rc ? 0 : (uint32_t)a6.size();
     return rc;
 }
 
@@ -1948,19 +1771,19 @@ int fb_set_blacklists(fb_ctx* c, const fb_cidr* nets, uint32_t n) {
         return set_err(FB_ERR_INVAL, "blacklist entry with a bad family, prefix or list (< %u)", FB_MAX_BLACKLISTS);
     DeviceGuard g(c->device);
     HIP_TRY(hipDeviceSynchronize());
-    int rc = upload_array(&c->d_bl4_pos, p4.data(), p4.size());
-    if (!rc) rc = upload_array(&c->d_bl4_mask, m4.data(), m4.size());
-    if (!rc) rc = upload_array(&c->d_bl6_pos, p6.data(), p6.size());
-    if (!rc) rc = upload_array(&c->d_bl6_mask, m6.data(), m6.size());
-    c->m_bl4 = rc ? 0 : (uint32_t)p4.size();
-    c->m_bl6 = rc ? 0 : (uint32_t)p6.size();
+    int rc = upload_array(c->en.bl4_pos, p4.data(), p4.size());
+    if (!rc) rc = upload_array(c->en.bl4_mask, m4.data(), m4.size());
+    if (!rc) rc = upload_array(c->en.bl6_pos, p6.data(), p6.size());
+    if (!rc) rc = upload_array(c->en.bl6_mask, m6.data(), m6.size());
+    c->en.m4 = rc ? 0 : (uint32_t)p4.size();
+    c->en.m6 = rc ? 0 : (uint32_t)p6.size();
     return rc;
 }
 
 int fb_ip_lookup_dev(fb_ctx* c, const fb_ip* d_ips, uint32_t n, int32_t* d_asn, uint64_t* d_lists, void* stream) {
     if (!c || (n && !d_ips)) return set_err(FB_ERR_INVAL, "bad arguments");
     DeviceGuard g(c->device);
-    HIP_TRY(launch_ip_lookup(enrich_tables(c), d_ips, n, d_asn, (unsigned long long*)d_lists, (hipStream_t)stream));
+    HIP_TRY(launch_ip_lookup(c->en.tables(), d_ips, n, d_asn, (unsigned long long*)d_lists, (hipStream_t)stream));
     return FB_OK;
 }
 
@@ -1970,11 +1793,11 @@ int fb_flow_enrich_dev(fb_ctx* c, uint32_t new_only, fb_flow_enrich* d_out, uint
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
-    if (!c->d_table || (new_only && c->flow_batch == 0)) return FB_OK;
+    if (!c->tb.slots || (new_only && c->flow_batch == 0)) return FB_OK;
     int rc = join_updates(c, s);
     if (!rc) rc = upload_cfg(c, s);
     if (rc) return rc;
-    HIP_TRY(launch_flow_enrich(enrich_tables(c), c->d_cfg, c->d_table, c->table_cap, new_only ? 1u : 0u,
+    HIP_TRY(launch_flow_enrich(c->en.tables(), c->d_cfg, c->tb.slots, c->tb.cap, new_only ? 1u : 0u,
                                c->flow_batch - 1u, d_out, cap, (unsigned long long*)d_n, s));
     return FB_OK;
 }
@@ -1992,14 +1815,14 @@ int fb_dns_parse_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes, 
 int fb_flow_count(fb_ctx* c, uint64_t* n_flows, void* stream) {
     if (!c || !n_flows) return set_err(FB_ERR_INVAL, "bad arguments");
     *n_flows = 0;
-    if (!c->d_table) return FB_OK;
+    if (!c->tb.slots) return FB_OK;
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     unsigned long long h = 0;
     const int rc = join_updates(c, s);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->d_n, 0, 8, s));
-    HIP_TRY(launch_flow_count(c->d_table, c->table_cap, c->d_n, s));
+    HIP_TRY(launch_flow_count(c->tb.slots, c->tb.cap, c->d_n, s));
     HIP_TRY(hipMemcpyAsync(&h, c->d_n, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     *n_flows = h;
@@ -2012,11 +1835,11 @@ int fb_flow_export_sessions_dev(fb_ctx* c, uint32_t filter, fb_flow_rec* d_out, 
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
-    if (!c->d_table) return FB_OK;
+    if (!c->tb.slots) return FB_OK;
     int rc = join_updates(c, s);
     if (!rc && filter != FB_FILTER_ALL) rc = upload_cfg(c, s);  // the LAN configuration as of now
     if (rc) return rc;
-    HIP_TRY(launch_flow_export(c->d_table, c->table_cap, d_out, cap, (unsigned long long*)d_n, s, filter, c->d_cfg,
+    HIP_TRY(launch_flow_export(c->tb.slots, c->tb.cap, d_out, cap, (unsigned long long*)d_n, s, filter, c->d_cfg,
                                c->plane<FlowTime>(kPlaneTime)));
     return FB_OK;
 }
@@ -2029,7 +1852,7 @@ int fb_flow_export_times_dev(fb_ctx* c, fb_flow_time* d_out, uint64_t cap, uint6
     HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
     int rc = join_updates(c, s);
     if (rc) return rc;
-    HIP_TRY(launch_time_export(c->d_table, c->plane<FlowTime>(kPlaneTime), c->table_cap, d_out, cap,
+    HIP_TRY(launch_time_export(c->tb.slots, c->plane<FlowTime>(kPlaneTime), c->tb.cap, d_out, cap,
                                (unsigned long long*)d_n, s));
     return FB_OK;
 }
@@ -2041,7 +1864,7 @@ int fb_flow_export_times(fb_ctx* c, fb_flow_time* out, uint64_t cap, uint64_t* n
     if (cap == 0) return FB_OK;
     DeviceGuard g(c->device);
     return export_to_host(c, out, cap, sizeof(fb_flow_time), n, (hipStream_t)stream, "time export", [&](void* d_out) {
-        return fb_flow_export_times_dev(c, (fb_flow_time*)d_out, cap, reinterpret_cast<uint64_t*>(c->d_n), stream);
+        return fb_flow_export_times_dev(c, (fb_flow_time*)d_out, cap, reinterpret_cast<uint64_t*>(c->d_n.get()), stream);
     });
 }
 
@@ -2058,7 +1881,7 @@ int fb_flow_export_dev(fb_ctx* c, fb_flow_rec* d_out, uint64_t cap, uint64_t* d_
 int fb_flow_age(fb_ctx* c, uint64_t now_ns, const fb_age_params* params, uint32_t flags, fb_age_stats* out,
                 void* stream) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
-    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     if (!c->timed) return set_err(FB_ERR_INVAL, "the context was created without FB_CFG_TIMED (aging needs the clock)");
     if (flags & ~FB_AGE_PURGE) return set_err(FB_ERR_INVAL, "unknown flags %u", flags);
     static const fb_age_params kReference = {60ull * 1000000000ull, 180ull * 1000000000ull, 86400ull * 1000000000ull, 0};
@@ -2069,41 +1892,31 @@ int fb_flow_age(fb_ctx* c, uint64_t now_ns, const fb_age_params* params, uint32_
     int rc = pass_begin(c, kAgeStatWords, s);
     if (!rc) rc = plane_ensure(c, kPlaneStatus, s);
     if (rc) return rc;
-    if (purge && c->age_remap_n != c->table_cap) {
-        hipFree(c->d_age_remap);
-        c->d_age_remap = nullptr;
-        c->age_remap_n = 0;
-        if (hipMalloc(&c->d_age_remap, c->table_cap * 4ull) != hipSuccess) {
-            c->d_age_remap = nullptr;
-            return set_err(FB_ERR_NOMEM, "slot remap");
-        }
-        c->age_remap_n = c->table_cap;
-    }
+    if (purge && c->d_age_remap.size() != c->tb.cap && c->d_age_remap.alloc(c->tb.cap) != hipSuccess)
+        return set_err(FB_ERR_NOMEM, "slot remap");
     AgeArgs a;
-    a.table = c->d_table;
+    a.table = c->tb.slots;
     a.plane = c->plane<FlowTime>(kPlaneTime);
-    a.char_call = c->d_char_call;
+    a.char_call = c->tb.char_call;
     a.status = c->plane<uint8_t>(kPlaneStatus);
-    a.remap = purge ? c->d_age_remap : nullptr;
+    a.remap = purge ? c->d_age_remap.get() : nullptr;
     a.stats = c->d_pass_stats;
     a.now = now_ns;
     a.activity = ap.activity_ns;
     a.current = ap.current_ns;
     a.retention = ap.retention_ns;
     a.purge = purge ? 1u : 0u;
-    HIP_TRY(launch_flow_age(a, c->flow_parts, s));
+    HIP_TRY(launch_flow_age(a, c->tb.parts, s));
     unsigned long long h[kAgeStatWords] = {};
     rc = pass_end(c, h, kAgeStatWords, s);
     if (rc) return rc;
     if (h[6]) {  // flows were removed: survivors of their partitions may have moved
-        std::swap(c->d_remap, c->d_age_remap);
-        c->age_remap_n = c->d_age_remap ? c->remap_n : 0;  // (the old map's size; reallocated if it differs)
-        c->remap_n = c->table_cap;
+        c->d_remap.swap(c->d_age_remap);  // (the old map is reallocated if its size is not the table's)
         ++c->generation;
         c->last_recs = nullptr;  // the last update's slots moved: its history is no longer available
         c->last_part = nullptr;
-        c->h_mbox->flows = h[7];
-        c->h_mbox->max_part = h[8];
+        c->mbox->flows = h[7];
+        c->mbox->max_part = h[8];
         rc = planes_follow_purge(c, s);
         if (rc) return rc;
     }
@@ -2142,21 +1955,24 @@ int fb_set_whitelist(fb_ctx* c, const fb_wl_endpoint* eps, uint64_t n, const uin
     DeviceGuard g(c->device);
     HIP_TRY(hipDeviceSynchronize());
     c->wl_active = false;
-    int rc = upload_array(&c->d_wl_a4, ix.a4.data(), ix.a4.size());
-    if (!rc) rc = upload_array(&c->d_wl_k4, ix.k4.data(), ix.k4.size());
-    if (!rc) rc = upload_array(&c->d_wl_a6, ix.a6.data(), ix.a6.size());
-    if (!rc) rc = upload_array(&c->d_wl_k6, ix.k6.data(), ix.k6.size());
-    if (!rc) rc = upload_array(&c->d_wl_gkey, ix.gkey.data(), ix.gkey.size());
-    if (!rc) rc = upload_array(&c->d_wl_gbeg, ix.gbeg.data(), ix.gkey.empty() ? 0 : ix.gbeg.size());
-    if (!rc) rc = upload_array(&c->d_wl_rules, ix.rules.data(), ix.rules.size());
-    if (!rc) rc = upload_array(&c->d_wl_owner, rec_owner_id, n_records);
-    if (!rc) rc = upload_array(&c->d_wl_country, rec_country_id, n_records);
+    c->wl = WlDev();  // (no launch may still read it) -- and it stays empty when an upload fails
+    WlDev w;
+    int rc = upload_array(w.a4, ix.a4.data(), ix.a4.size());
+    if (!rc) rc = upload_array(w.k4, ix.k4.data(), ix.k4.size());
+    if (!rc) rc = upload_array(w.a6, ix.a6.data(), ix.a6.size());
+    if (!rc) rc = upload_array(w.k6, ix.k6.data(), ix.k6.size());
+    if (!rc) rc = upload_array(w.gkey, ix.gkey.data(), ix.gkey.size());
+    if (!rc) rc = upload_array(w.gbeg, ix.gbeg.data(), ix.gkey.empty() ? 0 : ix.gbeg.size());
+    if (!rc) rc = upload_array(w.rules, ix.rules.data(), ix.rules.size());
+    if (!rc) rc = upload_array(w.owner, rec_owner_id, n_records);
+    if (!rc) rc = upload_array(w.country, rec_country_id, n_records);
     if (rc) return rc;
-    c->wl_n4 = (uint32_t)ix.a4.size();
-    c->wl_n6 = (uint32_t)ix.a6.size();
-    c->wl_ng = (uint32_t)ix.gkey.size();
-    c->wl_nr = (uint32_t)ix.rules.size();
-    c->wl_records = n_records;
+    w.n4 = (uint32_t)ix.a4.size();
+    w.n6 = (uint32_t)ix.a6.size();
+    w.ng = (uint32_t)ix.gkey.size();
+    w.nr = (uint32_t)ix.rules.size();
+    w.records = n_records;
+    c->wl = std::move(w);
     c->wl_active = true;
     return FB_OK;
 }
@@ -2174,7 +1990,7 @@ int fb_clear_whitelist(fb_ctx* c) {
 // Synchronous, like fb_flow_age: drains the updates in flight, one pass, the counters read back.
 int fb_flow_whitelist(fb_ctx* c, uint32_t flags, fb_wl_stats* out, void* stream) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
-    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     if (!c->wl_active) return set_err(FB_ERR_INVAL, "no whitelist is installed (fb_set_whitelist)");
     if (flags) return set_err(FB_ERR_INVAL, "unknown flags %u", flags);
     DeviceGuard g(c->device);
@@ -2185,22 +2001,7 @@ int fb_flow_whitelist(fb_ctx* c, uint32_t flags, fb_wl_stats* out, void* stream)
     unsigned long long* mod = nullptr;
     if (!rc) rc = pass_stamps(c, s, &mod);
     if (rc) return rc;
-    WlTables w;
-    w.a4 = c->d_wl_a4;
-    w.k4 = c->d_wl_k4;
-    w.a6 = c->d_wl_a6;
-    w.k6 = c->d_wl_k6;
-    w.gkey = c->d_wl_gkey;
-    w.gbeg = c->d_wl_gbeg;
-    w.rules = c->d_wl_rules;
-    w.rec_owner = c->d_wl_owner;
-    w.rec_country = c->d_wl_country;
-    w.n4 = c->wl_n4;
-    w.n6 = c->wl_n6;
-    w.ng = c->wl_ng;
-    w.nr = c->wl_nr;
-    w.n_records = c->wl_records;
-    HIP_TRY(launch_flow_whitelist(w, enrich_tables(c), c->d_cfg, c->d_table, c->table_cap, c->plane<uint8_t>(kPlaneWl),
+    HIP_TRY(launch_flow_whitelist(c->wl.tables(), c->en.tables(), c->d_cfg, c->tb.slots, c->tb.cap, c->plane<uint8_t>(kPlaneWl),
                                   c->d_pass_stats, s, mod, c->pass_time));
     unsigned long long h[kWlCounters] = {};
     rc = pass_end(c, h, kWlCounters, s);
@@ -2228,10 +2029,10 @@ int fb_flow_export_whitelist_dev(fb_ctx* c, uint32_t state_mask, fb_flow_rec* d_
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
-    if (!c->d_table) return FB_OK;
+    if (!c->tb.slots) return FB_OK;
     const int rc = join_updates(c, s);
     if (rc) return rc;
-    HIP_TRY(launch_flow_export_whitelist(c->d_table, c->plane<uint8_t>(kPlaneWl), c->table_cap, state_mask, d_out, cap,
+    HIP_TRY(launch_flow_export_whitelist(c->tb.slots, c->plane<uint8_t>(kPlaneWl), c->tb.cap, state_mask, d_out, cap,
                                          (unsigned long long*)d_n, c->plane<FlowTime>(kPlaneTime), s));
     return FB_OK;
 }
@@ -2241,7 +2042,7 @@ int fb_flow_export_whitelist_dev(fb_ctx* c, uint32_t state_mask, fb_flow_rec* d_
 // counters read back.  The lists are whatever fb_set_blacklists installed last (none: every mask 0).
 int fb_flow_blacklist(fb_ctx* c, uint32_t flags, fb_bl_stats* out, void* stream) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
-    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     if (flags & ~FB_BL_MARK_WHITELIST) return set_err(FB_ERR_INVAL, "unknown flags %u", flags);
     const bool mark = (flags & FB_BL_MARK_WHITELIST) != 0u;
     DeviceGuard g(c->device);
@@ -2253,7 +2054,7 @@ int fb_flow_blacklist(fb_ctx* c, uint32_t flags, fb_bl_stats* out, void* stream)
     unsigned long long* mod = nullptr;
     if (!rc) rc = pass_stamps(c, s, &mod);
     if (rc) return rc;
-    HIP_TRY(launch_flow_blacklist(enrich_tables(c), c->d_table, c->table_cap, c->plane<unsigned long long>(kPlaneBl),
+    HIP_TRY(launch_flow_blacklist(c->en.tables(), c->tb.slots, c->tb.cap, c->plane<unsigned long long>(kPlaneBl),
                                   mark ? c->plane<uint8_t>(kPlaneWl) : nullptr, c->d_pass_stats, s, mod, c->pass_time));
     unsigned long long h[kBlCounters] = {};
     rc = pass_end(c, h, kBlCounters, s);
@@ -2280,10 +2081,10 @@ int fb_flow_export_blacklisted_dev(fb_ctx* c, fb_flow_rec* d_out, uint64_t* d_ma
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
-    if (!c->d_table || !c->d_plane[kPlaneBl]) return FB_OK;  // no pass yet: no flow has a mask
+    if (!c->tb.slots || !c->tb.plane[kPlaneBl]) return FB_OK;  // no pass yet: no flow has a mask
     const int rc = join_updates(c, s);
     if (rc) return rc;
-    HIP_TRY(launch_flow_export_blacklisted(c->d_table, c->plane<unsigned long long>(kPlaneBl), c->table_cap, d_out,
+    HIP_TRY(launch_flow_export_blacklisted(c->tb.slots, c->plane<unsigned long long>(kPlaneBl), c->tb.cap, d_out,
                                            (unsigned long long*)d_masks, cap, (unsigned long long*)d_n,
                                            c->plane<FlowTime>(kPlaneTime), s));
     return FB_OK;
@@ -2380,7 +2181,7 @@ int fb_dns_lookup_dev(fb_ctx* c, const fb_ip* d_ips, uint64_t n, uint32_t* d_nam
 // Synchronous, like fb_flow_blacklist: drains the updates in flight, one pass, the counters read back.
 int fb_flow_domains(fb_ctx* c, uint32_t flags, fb_dom_stats* out, void* stream) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
-    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     if (!c->dns) return set_err(FB_ERR_INVAL, "DNS tracking is not enabled (fb_dns_track_enable)");
     if (flags) return set_err(FB_ERR_INVAL, "unknown flags %u", flags);
     DeviceGuard g(c->device);
@@ -2390,7 +2191,7 @@ int fb_flow_domains(fb_ctx* c, uint32_t flags, fb_dom_stats* out, void* stream) 
     unsigned long long* mod = nullptr;
     if (!rc) rc = pass_stamps(c, s, &mod);
     if (rc) return rc;
-    HIP_TRY(launch_flow_domains(dnstrack_tables(c->dns), c->d_table, c->table_cap, c->plane<uint8_t>(kPlaneStatus),
+    HIP_TRY(launch_flow_domains(dnstrack_tables(c->dns), c->tb.slots, c->tb.cap, c->plane<uint8_t>(kPlaneStatus),
                                 c->plane<uint2>(kPlaneDom), c->d_pass_stats, s, mod, c->pass_time));
     unsigned long long h[kDomCounters] = {};
     rc = pass_end(c, h, kDomCounters, s);
@@ -2420,18 +2221,6 @@ int fb_if_validate(const fb_if_node* nodes, uint64_t n_nodes, const uint32_t* fi
     return FB_OK;
 }
 
-static AnForest an_forest(const fb_ctx* c) {
-    AnForest f;
-    if (c->an_active) {
-        f.nodes = c->d_an_nodes;
-        f.first = c->d_an_first;
-        f.n_trees = c->an_trees;
-        f.prm = c->an_prm;
-    }
-    f.service_code = c->d_an_service;
-    return f;
-}
-
 static bool service_codes_valid(const uint32_t* service_code) {
     for (uint32_t p = 0; service_code && p < 65536u; ++p)
         if (service_code[p] >= FB_AN_MAX_SERVICE_CODE) return false;
@@ -2443,7 +2232,7 @@ int fb_set_service_codes(fb_ctx* c, const uint32_t* service_code) {
     if (!service_codes_valid(service_code)) return set_err(FB_ERR_INVAL, "a service code is %u or above", FB_AN_MAX_SERVICE_CODE);
     DeviceGuard g(c->device);
     HIP_TRY(hipDeviceSynchronize());  // no sweep in flight reads the old codes
-    return upload_array(&c->d_an_service, service_code, service_code ? (size_t)65536 : (size_t)0);
+    return upload_array(c->an.service, service_code, service_code ? (size_t)65536 : (size_t)0);
 }
 
 // Everything is checked, and the new arrays are on the device, before the installed model is touched.
@@ -2459,27 +2248,17 @@ int fb_set_anomaly_model(fb_ctx* c, const fb_if_node* nodes, uint64_t n_nodes, c
         return set_err(FB_ERR_INVAL, "a cut is NaN, or has_stats is not 0 / 1");
     if (!service_codes_valid(service_code)) return set_err(FB_ERR_INVAL, "a service code is %u or above", FB_AN_MAX_SERVICE_CODE);
     DeviceGuard g(c->device);
-    fb_if_node* d_nodes = nullptr;
-    uint32_t *d_first = nullptr, *d_service = nullptr;
-    int rc = upload_array(&d_nodes, nodes, (size_t)n_nodes);
-    if (!rc) rc = upload_array(&d_first, first, (size_t)n_trees + 1u);
-    if (!rc) rc = upload_array(&d_service, service_code, service_code ? (size_t)65536 : (size_t)0);
-    hipError_t e = rc ? hipSuccess : hipDeviceSynchronize();  // no pass in flight reads the old arrays
-    if (rc || e != hipSuccess) {
-        hipFree(d_nodes);
-        hipFree(d_first);
-        hipFree(d_service);
-        return rc ? rc : set_err(FB_ERR_HIP, "hipDeviceSynchronize: %s", hipGetErrorString(e));
-    }
-    hipFree(c->d_an_nodes);
-    hipFree(c->d_an_first);
-    hipFree(c->d_an_service);
-    c->d_an_nodes = d_nodes;
-    c->d_an_first = d_first;
-    c->d_an_service = d_service;
-    c->an_trees = n_trees;
-    c->an_prm = *prm;
-    c->an_active = true;
+    AnModel m;
+    int rc = upload_array(m.nodes, nodes, (size_t)n_nodes);
+    if (!rc) rc = upload_array(m.first, first, (size_t)n_trees + 1u);
+    if (!rc) rc = upload_array(m.service, service_code, service_code ? (size_t)65536 : (size_t)0);
+    if (rc) return rc;
+    const hipError_t e = hipDeviceSynchronize();  // no pass in flight reads the old arrays
+    if (e != hipSuccess) return set_err(FB_ERR_HIP, "hipDeviceSynchronize: %s", hipGetErrorString(e));
+    m.trees = n_trees;
+    m.prm = *prm;
+    m.active = true;
+    c->an = std::move(m);
     return FB_OK;
 }
 
@@ -2487,7 +2266,7 @@ int fb_clear_anomaly_model(fb_ctx* c) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
     DeviceGuard g(c->device);
     HIP_TRY(hipDeviceSynchronize());
-    c->an_active = false;
+    c->an.active = false;
     HIP_TRY(plane_zero(c, kPlaneAn, nullptr));  // every record back to "unseen"
     HIP_TRY(hipStreamSynchronize(nullptr));
     return FB_OK;
@@ -2496,8 +2275,8 @@ int fb_clear_anomaly_model(fb_ctx* c) {
 // Synchronous, like fb_flow_blacklist: drains the updates in flight, one pass, the counters read back.
 int fb_flow_anomaly(fb_ctx* c, uint32_t flags, fb_an_stats* out, void* stream) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
-    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
-    if (!c->an_active) return set_err(FB_ERR_INVAL, "no anomaly model is installed (fb_set_anomaly_model)");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->an.active) return set_err(FB_ERR_INVAL, "no anomaly model is installed (fb_set_anomaly_model)");
     if (flags) return set_err(FB_ERR_INVAL, "unknown flags %u", flags);
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
@@ -2506,7 +2285,7 @@ int fb_flow_anomaly(fb_ctx* c, uint32_t flags, fb_an_stats* out, void* stream) {
     unsigned long long* mod = nullptr;
     if (!rc) rc = pass_stamps(c, s, &mod);
     if (rc) return rc;
-    HIP_TRY(launch_flow_anomaly(an_forest(c), c->d_table, c->plane<FlowTime>(kPlaneTime), c->table_cap,
+    HIP_TRY(launch_flow_anomaly(c->an.forest(), c->tb.slots, c->plane<FlowTime>(kPlaneTime), c->tb.cap,
                                 c->plane<fb_an_rec>(kPlaneAn), c->d_pass_stats, s, mod, c->pass_time));
     unsigned long long h[kAnCounters] = {};
     rc = pass_end(c, h, kAnCounters, s);
@@ -2535,10 +2314,10 @@ int fb_flow_export_anomalous_dev(fb_ctx* c, uint32_t min_level, fb_flow_rec* d_o
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
-    if (!c->d_table || !c->d_plane[kPlaneAn]) return FB_OK;  // no pass yet: no flow has a level
+    if (!c->tb.slots || !c->tb.plane[kPlaneAn]) return FB_OK;  // no pass yet: no flow has a level
     const int rc = join_updates(c, s);
     if (rc) return rc;
-    HIP_TRY(launch_flow_export_anomalous(c->d_table, c->plane<fb_an_rec>(kPlaneAn), c->table_cap, min_level, d_out, d_recs,
+    HIP_TRY(launch_flow_export_anomalous(c->tb.slots, c->plane<fb_an_rec>(kPlaneAn), c->tb.cap, min_level, d_out, d_recs,
                                          cap, (unsigned long long*)d_n, c->plane<FlowTime>(kPlaneTime), s));
     return FB_OK;
 }
@@ -2548,20 +2327,20 @@ int fb_flow_features_dev(fb_ctx* c, double* d_feat, uint32_t* d_slot, uint64_t c
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
-    if (!c->d_table) return FB_OK;
+    if (!c->tb.slots) return FB_OK;
     const int rc = join_updates(c, s);
     if (rc) return rc;
-    HIP_TRY(launch_flow_features(c->d_table, c->plane<FlowTime>(kPlaneTime), an_forest(c).service_code, c->table_cap, d_feat,
+    HIP_TRY(launch_flow_features(c->tb.slots, c->plane<FlowTime>(kPlaneTime), c->an.forest().service_code, c->tb.cap, d_feat,
                                  d_slot, cap, (unsigned long long*)d_n, s));
     return FB_OK;
 }
 
 int fb_if_score_dev(fb_ctx* c, const double* d_feat, uint64_t n, double* d_path_sum, void* stream) {
     if (!c || (n && (!d_feat || !d_path_sum))) return set_err(FB_ERR_INVAL, "bad arguments");
-    if (!c->an_active) return set_err(FB_ERR_INVAL, "no anomaly model is installed (fb_set_anomaly_model)");
+    if (!c->an.active) return set_err(FB_ERR_INVAL, "no anomaly model is installed (fb_set_anomaly_model)");
     if (n == 0) return FB_OK;
     DeviceGuard g(c->device);
-    HIP_TRY(launch_if_score(an_forest(c), d_feat, n, d_path_sum, (hipStream_t)stream));
+    HIP_TRY(launch_if_score(c->an.forest(), d_feat, n, d_path_sum, (hipStream_t)stream));
     return FB_OK;
 }
 
@@ -2582,7 +2361,7 @@ static int view_query_check(const fb_ctx* c, const fb_view_query* q) {
     if (q->filter > FB_FILTER_ALL) return set_err(FB_ERR_INVAL, "unknown filter %u", q->filter);
     if (q->flags & ~FB_VIEW_MODIFIED_SINCE) return set_err(FB_ERR_INVAL, "unknown flags %u", q->flags);
     if (q->reserved) return set_err(FB_ERR_INVAL, "reserved field is %u", q->reserved);
-    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     if ((q->flags & FB_VIEW_MODIFIED_SINCE) && !c->timed)
         return set_err(FB_ERR_INVAL, "FB_VIEW_MODIFIED_SINCE needs FB_CFG_TIMED (last_modified has no packet clock)");
     return FB_OK;
@@ -2601,7 +2380,7 @@ int fb_flow_export_view_dev(fb_ctx* c, const fb_view_query* q, fb_flow_view* d_o
     if (!rc && q->filter != FB_FILTER_ALL) rc = upload_cfg(c, s);  // the LAN configuration as of now
     if (rc) return rc;
     ViewArgs a;
-    a.table = c->d_table;
+    a.table = c->tb.slots;
     a.time = c->plane<FlowTime>(kPlaneTime);
     a.status = c->plane<uint8_t>(kPlaneStatus);
     a.wl = c->plane<uint8_t>(kPlaneWl);
@@ -2609,7 +2388,7 @@ int fb_flow_export_view_dev(fb_ctx* c, const fb_view_query* q, fb_flow_view* d_o
     a.an = c->plane<fb_an_rec>(kPlaneAn);
     a.mod = c->plane<unsigned long long>(kPlaneMod);
     a.cfg = c->d_cfg;
-    a.cap = c->table_cap;
+    a.cap = c->tb.cap;
     a.since = q->since_ns;
     a.set = q->set;
     a.filter = q->filter;
@@ -2631,7 +2410,7 @@ int fb_flow_export_view(fb_ctx* c, const fb_view_query* q, fb_flow_view* out, ui
     const uint64_t m = std::min(total, cap);
     if (m == 0) return FB_OK;
     return export_to_host(c, out, m, sizeof(fb_flow_view), n, (hipStream_t)stream, "view export", [&](void* d_out) {
-        return fb_flow_export_view_dev(c, q, (fb_flow_view*)d_out, m, reinterpret_cast<uint64_t*>(c->d_n), stream);
+        return fb_flow_export_view_dev(c, q, (fb_flow_view*)d_out, m, reinterpret_cast<uint64_t*>(c->d_n.get()), stream);
     });
 }
 
@@ -2656,17 +2435,8 @@ int fb_format_zeek_dev(fb_ctx* c, const fb_flow_view* d_views, uint64_t n, const
     // a reallocation waits for that use on the host before the old buffer is freed
     size_t want = 0;
     HIP_TRY(zeek_scan_tmp_bytes(n, &want));
-    if (!c->ev_zeek) HIP_TRY(hipEventCreateWithFlags(&c->ev_zeek, hipEventDisableTiming));
-    HIP_TRY(hipStreamWaitEvent(s, c->ev_zeek, 0));  // (an event never recorded is complete)
-    if (want > c->zeek_tmp_bytes) {
-        HIP_TRY(hipEventSynchronize(c->ev_zeek));
-        (void)hipFree(c->d_zeek_tmp);
-        c->d_zeek_tmp = nullptr;
-        c->zeek_tmp_bytes = 0;
-        if (hipMalloc(&c->d_zeek_tmp, want) != hipSuccess)
-            return set_err(FB_ERR_NOMEM, "Zeek export scan scratch (%llu bytes)", (unsigned long long)want);
-        c->zeek_tmp_bytes = want;
-    }
+    const int rc = c->zeek_tmp.acquire(want, s, "Zeek export scan scratch");
+    if (rc) return rc;
     ZeekArgs a;
     a.views = d_views;
     a.n = n;
@@ -2677,35 +2447,19 @@ int fb_format_zeek_dev(fb_ctx* c, const fb_flow_view* d_views, uint64_t n, const
     a.cap = text_cap;
     a.off = reinterpret_cast<unsigned long long*>(d_line_off);
     a.stats = d_stats;
-    HIP_TRY(launch_zeek(a, !c->zeek_direct, c->d_zeek_tmp, c->zeek_tmp_bytes, s));
-    HIP_TRY(hipEventRecord(c->ev_zeek, s));
-    return FB_OK;
+    HIP_TRY(launch_zeek(a, !c->zeek_direct, c->zeek_tmp.get(), c->zeek_tmp.capacity(), s));
+    return c->zeek_tmp.release(s);
 }
 
 // ---- multi-GPU merge (fb_merge.hip) ---------------------------------------------------------------
-// The export and the merge share d_mscratch and may be called on different streams: each use waits
-// on the event the previous use recorded (mscratch_use / mscratch_done), and a reallocation waits for
-// that use on the host before the old buffer is freed.
-static int ensure_mscratch(fb_ctx* c, uint64_t bytes, hipStream_t s) {
-    if (!c->ev_mscratch) HIP_TRY(hipEventCreateWithFlags(&c->ev_mscratch, hipEventDisableTiming));
-    HIP_TRY(hipStreamWaitEvent(s, c->ev_mscratch, 0));  // (an event never recorded is complete)
-    if (bytes <= c->mscratch_bytes) return FB_OK;
-    HIP_TRY(hipEventSynchronize(c->ev_mscratch));
-    HIP_TRY(hipStreamSynchronize(s));
-    hipFree(c->d_mscratch);
-    c->d_mscratch = nullptr;
-    c->mscratch_bytes = 0;
-    if (hipMalloc(&c->d_mscratch, bytes) != hipSuccess)
-        return set_err(FB_ERR_NOMEM, "merge scratch (%llu bytes)", (unsigned long long)bytes);
-    c->mscratch_bytes = bytes;
-    return FB_OK;
-}
+// The export, the routing and the merge share c->mscratch and may be called on different streams.
+static constexpr const char* kMergeScratch = "merge scratch";
 
 static int export_merge(fb_ctx* c, uint32_t world, uint32_t rank, uint64_t shard_first, const uint64_t* call_map,
                         uint32_t n_calls, fb_flow_mrec* d_out, uint64_t cap, uint64_t* d_counts, void* stream) {
     if (!c || !d_counts || (cap && !d_out)) return set_err(FB_ERR_INVAL, "ctx, d_counts and d_out are required");
     if (world == 0 || world > 64 || rank >= world) return set_err(FB_ERR_INVAL, "1 <= world <= 64, rank < world");
-    if (!c->d_table) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     if (call_map) {  // every position the table holds names a call below flow_batch
         if (n_calls < c->flow_batch)
             return set_err(FB_ERR_INVAL, "call map has %u entries, the table holds %u update calls", n_calls,
@@ -2720,20 +2474,19 @@ static int export_merge(fb_ctx* c, uint32_t world, uint32_t rank, uint64_t shard
     }
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
-    const uint64_t cnt_bytes = merge_export_scratch_bytes(c->table_cap, world);
+    const uint64_t cnt_bytes = merge_export_scratch_bytes(c->tb.cap, world);
     int rc = join_updates(c, s);
-    if (!rc) rc = ensure_mscratch(c, cnt_bytes + (call_map ? 8ull * std::max<uint32_t>(c->flow_batch, 1u) : 0ull), s);
+    if (!rc) rc = c->mscratch.acquire(cnt_bytes + (call_map ? 8ull * std::max<uint32_t>(c->flow_batch, 1u) : 0ull), s, kMergeScratch);
     if (rc) return rc;
     unsigned long long* d_map = nullptr;
     if (call_map && c->flow_batch) {
-        d_map = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->d_mscratch) + cnt_bytes);
+        d_map = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->mscratch.get()) + cnt_bytes);
         HIP_TRY(hipMemcpyAsync(d_map, call_map, 8ull * c->flow_batch, hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(launch_merge_export(c->d_table, c->d_char_call, c->table_cap, world, rank, shard_first,
+    HIP_TRY(launch_merge_export(c->tb.slots, c->tb.char_call, c->tb.cap, world, rank, shard_first,
                                 call_map ? d_map : nullptr, d_out, cap, (unsigned long long*)d_counts,
-                                c->d_mscratch, s));
-    HIP_TRY(hipEventRecord(c->ev_mscratch, s));
-    return FB_OK;
+                                c->mscratch.get(), s));
+    return c->mscratch.release(s);
 }
 
 int fb_flow_export_merge_dev(fb_ctx* c, uint32_t world, uint32_t rank, uint64_t shard_first, fb_flow_mrec* d_out,
@@ -2764,13 +2517,12 @@ int fb_route_records_dev(fb_ctx* c, const fb_pkt_out* d_recs, const fb_batch_sta
     if ((d_ts == nullptr) != (d_ts_out == nullptr)) return set_err(FB_ERR_INVAL, "d_ts and d_ts_out go together");
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
-    const int rc = ensure_mscratch(c, route_scratch_bytes(max_n, world), s);
+    const int rc = c->mscratch.acquire(route_scratch_bytes(max_n, world), s, kMergeScratch);
     if (rc) return rc;
     HIP_TRY(launch_route(d_recs, d_stats, max_n, world, shard_first, reinterpret_cast<const unsigned long long*>(d_ts),
                          d_out, reinterpret_cast<unsigned long long*>(d_ts_out), (unsigned long long*)d_counts,
-                         c->d_mscratch, s));
-    HIP_TRY(hipEventRecord(c->ev_mscratch, s));
-    return FB_OK;
+                         c->mscratch.get(), s));
+    return c->mscratch.release(s);
 }
 
 int fb_flow_merge_dev(fb_ctx* c, const fb_flow_mrec* d_in, uint64_t n, fb_flow_rec* d_out, uint64_t* d_n,
@@ -2779,17 +2531,16 @@ int fb_flow_merge_dev(fb_ctx* c, const fb_flow_mrec* d_in, uint64_t n, fb_flow_r
     if (n >= 0xFFFFFFFFull) return set_err(FB_ERR_INVAL, "n %llu >= 2^32", (unsigned long long)n);
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
-    const int rc = ensure_mscratch(c, n ? merge_scratch_bytes(n) : 0, s);
+    const int rc = c->mscratch.acquire(n ? merge_scratch_bytes(n) : 0, s, kMergeScratch);
     if (rc) return rc;
-    HIP_TRY(launch_merge(d_in, n, d_out, (unsigned long long*)d_n, c->d_mscratch, s));
-    HIP_TRY(hipEventRecord(c->ev_mscratch, s));
-    return FB_OK;
+    HIP_TRY(launch_merge(d_in, n, d_out, (unsigned long long*)d_n, c->mscratch.get(), s));
+    return c->mscratch.release(s);
 }
 
 int fb_flow_export_sessions(fb_ctx* c, uint32_t filter, fb_flow_rec* out, uint64_t cap, uint64_t* n, void* stream) {
     if (!c || !n || (cap && !out) || filter > FB_FILTER_ALL) return set_err(FB_ERR_INVAL, "bad arguments");
     *n = 0;
-    if (!c->d_table || cap == 0) return FB_OK;
+    if (!c->tb.slots || cap == 0) return FB_OK;
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     uint64_t total = 0;
@@ -2798,7 +2549,7 @@ int fb_flow_export_sessions(fb_ctx* c, uint32_t filter, fb_flow_rec* out, uint64
     const uint64_t m = std::min(total, cap);
     if (m == 0) return FB_OK;
     return export_to_host(c, out, m, sizeof(fb_flow_rec), n, s, "flow export", [&](void* d_out) {
-        return fb_flow_export_sessions_dev(c, filter, (fb_flow_rec*)d_out, m, reinterpret_cast<uint64_t*>(c->d_n), stream);
+        return fb_flow_export_sessions_dev(c, filter, (fb_flow_rec*)d_out, m, reinterpret_cast<uint64_t*>(c->d_n.get()), stream);
     });
 }
 
@@ -2809,11 +2560,11 @@ int fb_flow_export(fb_ctx* c, fb_flow_rec* out, uint64_t cap, uint64_t* n, void*
 int fb_flow_table_info_get(fb_ctx* c, fb_flow_table_info* info) {
     if (!c || !info) return set_err(FB_ERR_INVAL, "bad arguments");
     memset(info, 0, sizeof(*info));
-    if (!c->d_table) return FB_OK;
-    info->capacity = c->table_cap;
-    info->partitions = c->flow_parts;
+    if (!c->tb.slots) return FB_OK;
+    info->capacity = c->tb.cap;
+    info->partitions = c->tb.parts;
     info->generation = c->generation;
-    const volatile FlowMailbox* m = c->h_mbox;
+    const volatile FlowMailbox* m = c->mbox;
     const uint64_t seq = __atomic_load_n(&m->seq, __ATOMIC_ACQUIRE);
     if (seq && seq > c->clear_seq) {
         info->flows = m->flows;
@@ -2825,9 +2576,9 @@ int fb_flow_table_info_get(fb_ctx* c, fb_flow_table_info* info) {
 int fb_flow_slot_remap(fb_ctx* c, uint32_t* old_to_new, uint64_t cap, uint64_t* n) {
     if (!c || !n || (cap && !old_to_new)) return set_err(FB_ERR_INVAL, "bad arguments");
     *n = 0;
-    if (!c->d_remap || !c->remap_n) return FB_OK;
+    if (!c->d_remap) return FB_OK;
     DeviceGuard g(c->device);
-    const uint64_t m = std::min(cap, c->remap_n);
+    const uint64_t m = std::min<uint64_t>(cap, c->d_remap.size());
     if (m) HIP_TRY(hipMemcpy(old_to_new, c->d_remap, m * 4ull, hipMemcpyDeviceToHost));
     *n = m;
     return FB_OK;
@@ -2835,11 +2586,11 @@ int fb_flow_slot_remap(fb_ctx* c, uint32_t* old_to_new, uint64_t cap, uint64_t* 
 
 int fb_flow_clear(fb_ctx* c, void* stream) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
-    if (!c->d_table) return FB_OK;
+    if (!c->tb.slots) return FB_OK;
     DeviceGuard g(c->device);
     int rc = join_updates(c, (hipStream_t)stream);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(c->d_table, 0, c->table_cap * sizeof(FlowSlot), (hipStream_t)stream));
+    HIP_TRY(hipMemsetAsync(c->tb.slots, 0, c->tb.cap * sizeof(FlowSlot), (hipStream_t)stream));
     rc = planes_clear(c, (hipStream_t)stream);
     if (rc) return rc;
     c->flow_batch = 0;

@@ -408,78 +408,76 @@ unsigned long long pow2_at_least(unsigned long long v) {
 
 // The host's handle.  Capacities: `name_cap` ids fit the store and `addr_cap` addresses the table; both
 // indexes have twice that many slots (a power of two), so they stay at most half full.
+namespace {
+// The owners of what the kernels see as a NameIndex / an AddrTable, and of the name store: each made whole
+// (alloc_group) or not at all.
+struct NameIndexBuf {
+    DevBuf<unsigned long long> tag, meta;
+    DevBuf<uint32_t> first;
+    unsigned long long slots = 0;
+    NameIndex view() const { return {tag, meta, first, slots}; }
+};
+struct AddrTableBuf {
+    DevBuf<unsigned long long> tag;
+    DevBuf<uint32_t> stamp, key;
+    DevBuf<unsigned long long> val;
+    unsigned long long slots = 0;
+    AddrTable view() const { return {tag, stamp, key, val, slots}; }
+};
+struct NameStore {
+    DevBuf<uint32_t> names;  // [(cap + 1) * kNameDwords]
+    DevBuf<uint16_t> len;    // [cap + 1]
+};
+}  // namespace
+
 struct DnsTrack {
     unsigned long long hash_mask = ~0ull;
     uint32_t launch = 1;  // the next launch's number (stamps)
     // names
-    uint32_t* store = nullptr;       // [(name_cap + 1) * kNameDwords]
-    uint16_t* store_len = nullptr;   // [name_cap + 1]
-    NameIndex ix = {};
+    NameStore store;
+    NameIndexBuf ix;
     uint64_t name_cap = 0, names = 0;
     // resolutions
-    AddrTable at = {};
+    AddrTableBuf at;
     uint64_t addr_cap = 0, addrs = 0;
     // pending
-    uint32_t* pend_name = nullptr;           // [kIds]
-    unsigned long long* pend_time = nullptr; // [kIds]
+    DevBuf<uint32_t> pend_name;            // [kIds]
+    DevBuf<unsigned long long> pend_time;  // [kIds]
     uint64_t messages = 0, writes = 0;
-    // per-call scratch, for `scratch_n` messages
+    // per-call scratch, for `scratch_n` messages: `a` and `sorted` point into it
     uint32_t scratch_n = 0;
-    void* scratch = nullptr;
+    DevBuf<uint8_t> scratch;
     TrackArgs a = {};
     unsigned long long* sorted = nullptr;
-    void* sort_tmp = nullptr;
-    size_t sort_tmp_bytes = 0;
-    unsigned long long* d_ctr = nullptr;
+    DevBuf<uint8_t> sort_tmp;
+    DevBuf<unsigned long long> d_ctr;
 };
 
 namespace {
 
-void free_name_index(NameIndex& ix) {
-    hipFree(ix.tag);
-    hipFree(ix.meta);
-    hipFree(ix.first);
-    ix = {};
+bool alloc_name_index(NameIndexBuf& ix, uint64_t cap) {
+    const unsigned long long slots = pow2_at_least(2ull * cap);
+    const hipError_t e = alloc_group(ix, [&](NameIndexBuf& n) {
+        n.slots = slots;
+        return alloc_each(n.tag, slots, n.meta, slots, n.first, slots);
+    });
+    return e == hipSuccess && hipMemset(ix.tag, 0, slots * 8ull) == hipSuccess &&
+           hipMemset(ix.meta, 0, slots * 8ull) == hipSuccess && hipMemset(ix.first, 0xFF, slots * 4ull) == hipSuccess;
 }
-void free_addr_table(AddrTable& t) {
-    hipFree(t.tag);
-    hipFree(t.stamp);
-    hipFree(t.key);
-    hipFree(t.val);
-    t = {};
+bool alloc_addr_table(AddrTableBuf& t, uint64_t cap) {
+    const unsigned long long slots = pow2_at_least(2ull * cap);
+    const hipError_t e = alloc_group(t, [&](AddrTableBuf& n) {
+        n.slots = slots;
+        return alloc_each(n.tag, slots, n.stamp, slots, n.key, slots * 5ull, n.val, slots);
+    });
+    return e == hipSuccess && hipMemset(t.tag, 0, slots * 8ull) == hipSuccess &&
+           hipMemset(t.stamp, 0, slots * 4ull) == hipSuccess && hipMemset(t.val, 0, slots * 8ull) == hipSuccess;
 }
-bool alloc_name_index(NameIndex& ix, uint64_t cap) {
-    ix = {};
-    ix.slots = pow2_at_least(2ull * cap);
-    const bool ok = hipMalloc(&ix.tag, ix.slots * 8ull) == hipSuccess && hipMalloc(&ix.meta, ix.slots * 8ull) == hipSuccess &&
-                    hipMalloc(&ix.first, ix.slots * 4ull) == hipSuccess &&
-                    hipMemset(ix.tag, 0, ix.slots * 8ull) == hipSuccess && hipMemset(ix.meta, 0, ix.slots * 8ull) == hipSuccess &&
-                    hipMemset(ix.first, 0xFF, ix.slots * 4ull) == hipSuccess;
-    if (!ok) free_name_index(ix);
-    return ok;
-}
-bool alloc_addr_table(AddrTable& t, uint64_t cap) {
-    t = {};
-    t.slots = pow2_at_least(2ull * cap);
-    const bool ok = hipMalloc(&t.tag, t.slots * 8ull) == hipSuccess && hipMalloc(&t.stamp, t.slots * 4ull) == hipSuccess &&
-                    hipMalloc(&t.key, t.slots * 20ull) == hipSuccess && hipMalloc(&t.val, t.slots * 8ull) == hipSuccess &&
-                    hipMemset(t.tag, 0, t.slots * 8ull) == hipSuccess && hipMemset(t.stamp, 0, t.slots * 4ull) == hipSuccess &&
-                    hipMemset(t.val, 0, t.slots * 8ull) == hipSuccess;
-    if (!ok) free_addr_table(t);
-    return ok;
-}
-bool alloc_store(uint32_t** store, uint16_t** len, uint64_t cap) {
-    *store = nullptr;
-    *len = nullptr;
-    const bool ok = hipMalloc(store, (cap + 1ull) * FB_DNS_MAX_NAME) == hipSuccess &&
-                    hipMalloc(len, (cap + 1ull) * 2ull) == hipSuccess && hipMemset(*len, 0, (cap + 1ull) * 2ull) == hipSuccess;
-    if (!ok) {
-        hipFree(*store);
-        hipFree(*len);
-        *store = nullptr;
-        *len = nullptr;
-    }
-    return ok;
+bool alloc_store(NameStore& st, uint64_t cap) {
+    const hipError_t e = alloc_group(st, [&](NameStore& n) {
+        return alloc_each(n.names, (cap + 1ull) * kNameDwords, n.len, cap + 1ull);
+    });
+    return e == hipSuccess && hipMemset(st.len, 0, (cap + 1ull) * 2ull) == hipSuccess;
 }
 
 // The stamps are 32-bit launch numbers; a tracker that has used them up restamps what it holds.
@@ -491,28 +489,20 @@ int grow_names(DnsTrack* t, uint64_t want, hipStream_t s) {
     if (want <= t->name_cap) return FB_OK;
     if (want > FB_DNS_MAX_NAMES) return set_err(FB_ERR_TABLE_FULL, "DNS name store: %llu names pass the 24-bit ids", (unsigned long long)want);
     const uint64_t cap = std::min<uint64_t>(FB_DNS_MAX_NAMES, std::max<uint64_t>(2ull * t->name_cap, pow2_at_least(want)));
-    uint32_t* store;
-    uint16_t* len;
-    NameIndex ix;
-    if (!alloc_store(&store, &len, cap)) return set_err(FB_ERR_TABLE_FULL, "DNS name store cannot grow to %llu names", (unsigned long long)cap);
-    if (!alloc_name_index(ix, cap)) {
-        hipFree(store);
-        hipFree(len);
+    NameStore store;
+    NameIndexBuf ix;
+    if (!alloc_store(store, cap)) return set_err(FB_ERR_TABLE_FULL, "DNS name store cannot grow to %llu names", (unsigned long long)cap);
+    if (!alloc_name_index(ix, cap))
         return set_err(FB_ERR_TABLE_FULL, "DNS name index cannot grow to %llu names", (unsigned long long)cap);
-    }
-    HIP_TRY(hipMemcpyAsync(store, t->store, (t->names + 1ull) * FB_DNS_MAX_NAME, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(len, t->store_len, (t->names + 1ull) * 2ull, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(store.names, t->store.names, (t->names + 1ull) * FB_DNS_MAX_NAME, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(store.len, t->store.len, (t->names + 1ull) * 2ull, hipMemcpyDeviceToDevice, s));
     if (t->names)
-        hipLaunchKernelGGL(k_dns_name_rebuild, grid_for(t->names), dim3(256), 0, s, ix, store, len, (uint32_t)t->names,
-                           t->hash_mask, t->launch++);
+        hipLaunchKernelGGL(k_dns_name_rebuild, grid_for(t->names), dim3(256), 0, s, ix.view(), store.names.get(),
+                           store.len.get(), (uint32_t)t->names, t->hash_mask, t->launch++);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
-    hipFree(t->store);
-    hipFree(t->store_len);
-    free_name_index(t->ix);
-    t->store = store;
-    t->store_len = len;
-    t->ix = ix;
+    t->store = std::move(store);
+    t->ix = std::move(ix);
     t->name_cap = cap;
     return FB_OK;
 }
@@ -520,30 +510,24 @@ int grow_addrs(DnsTrack* t, uint64_t want, hipStream_t s) {
     if (want <= t->addr_cap) return FB_OK;
     if (want > (1ull << 28)) return set_err(FB_ERR_TABLE_FULL, "DNS resolutions: %llu addresses pass the limit", (unsigned long long)want);
     const uint64_t cap = std::min<uint64_t>(1ull << 28, std::max<uint64_t>(2ull * t->addr_cap, pow2_at_least(want)));
-    AddrTable nw;
+    AddrTableBuf nw;
     if (!alloc_addr_table(nw, cap)) return set_err(FB_ERR_TABLE_FULL, "DNS resolutions cannot grow to %llu addresses", (unsigned long long)cap);
-    hipLaunchKernelGGL(k_dns_addr_rebuild, grid_for(t->at.slots), dim3(256), 0, s, t->at, nw, t->launch++);
+    hipLaunchKernelGGL(k_dns_addr_rebuild, grid_for(t->at.slots), dim3(256), 0, s, t->at.view(), nw.view(), t->launch++);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
-    free_addr_table(t->at);
-    t->at = nw;
+    t->at = std::move(nw);
     t->addr_cap = cap;
     return FB_OK;
 }
 
 int ensure_scratch(DnsTrack* t, uint32_t n) {
     if (n <= t->scratch_n) return FB_OK;
-    hipFree(t->scratch);
-    t->scratch = nullptr;
     t->scratch_n = 0;
     const uint64_t m = pow2_at_least(std::max<uint32_t>(n, 1024u));
     // 8-B arrays first: key, ntag, sorted; then the 4-B ones; kind last
     const uint64_t bytes = m * (3ull * 8 + 7ull * 4 + 2ull * FB_DNS_MAX_ADDRS * 4 + 1);
-    if (hipMalloc(&t->scratch, bytes) != hipSuccess) {
-        t->scratch = nullptr;
-        return set_err(FB_ERR_NOMEM, "DNS tracker scratch for %u messages", n);
-    }
-    uint8_t* p = static_cast<uint8_t*>(t->scratch);
+    if (t->scratch.alloc(bytes) != hipSuccess) return set_err(FB_ERR_NOMEM, "DNS tracker scratch for %u messages", n);
+    uint8_t* p = t->scratch;
     auto take = [&](uint64_t b) {
         uint8_t* q = p;
         p += b;
@@ -573,14 +557,8 @@ int ensure_sort_tmp(DnsTrack* t, uint32_t n) {
     HIP_TRY(rocprim::exclusive_scan(nullptr, scan_b, t->a.flag, t->a.rank, 0u, (size_t)n, rocprim::plus<uint32_t>(),
                                     (hipStream_t) nullptr));
     const size_t want = std::max(sort_b, scan_b);
-    if (want <= t->sort_tmp_bytes) return FB_OK;
-    hipFree(t->sort_tmp);
-    t->sort_tmp_bytes = 0;
-    if (hipMalloc(&t->sort_tmp, want) != hipSuccess) {
-        t->sort_tmp = nullptr;
+    if (want > t->sort_tmp.size() && t->sort_tmp.alloc(want) != hipSuccess)
         return set_err(FB_ERR_NOMEM, "DNS tracker sort scratch");
-    }
-    t->sort_tmp_bytes = want;
     return FB_OK;
 }
 
@@ -622,12 +600,11 @@ int dnstrack_create(DnsTrack** out, const fb_dns_track_config* cfg) {
     DnsTrack* t = new (std::nothrow) DnsTrack;
     if (!t) return set_err(FB_ERR_NOMEM, "DNS tracker");
     t->hash_mask = hm;
-    const bool ok = alloc_store(&t->store, &t->store_len, nc) && alloc_name_index(t->ix, nc) && alloc_addr_table(t->at, ac) &&
-                    hipMalloc(&t->pend_name, kIds * 4ull) == hipSuccess && hipMalloc(&t->pend_time, kIds * 8ull) == hipSuccess &&
-                    hipMalloc(&t->d_ctr, kCtrWords * 8ull) == hipSuccess &&
+    const bool ok = alloc_store(t->store, nc) && alloc_name_index(t->ix, nc) && alloc_addr_table(t->at, ac) &&
+                    alloc_each(t->pend_name, kIds, t->pend_time, kIds, t->d_ctr, kCtrWords) == hipSuccess &&
                     hipMemset(t->pend_name, 0, kIds * 4ull) == hipSuccess &&
                     hipMemset(t->pend_time, 0xFF, kIds * 8ull) == hipSuccess &&
-                    hipMemset(t->store, 0, FB_DNS_MAX_NAME) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+                    hipMemset(t->store.names, 0, FB_DNS_MAX_NAME) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
     if (!ok) {
         dnstrack_free(t);
         return set_err(FB_ERR_NOMEM, "DNS tracker tables (%llu names, %llu addresses)", (unsigned long long)nc, (unsigned long long)ac);
@@ -638,25 +615,13 @@ int dnstrack_create(DnsTrack** out, const fb_dns_track_config* cfg) {
     return FB_OK;
 }
 
-void dnstrack_free(DnsTrack* t) {
-    if (!t) return;
-    hipFree(t->store);
-    hipFree(t->store_len);
-    free_name_index(t->ix);
-    free_addr_table(t->at);
-    hipFree(t->pend_name);
-    hipFree(t->pend_time);
-    hipFree(t->scratch);
-    hipFree(t->sort_tmp);
-    hipFree(t->d_ctr);
-    delete t;
-}
+void dnstrack_free(DnsTrack* t) { delete t; }
 
 int dnstrack_clear(DnsTrack* t, hipStream_t s) {
     HIP_TRY(hipMemsetAsync(t->ix.tag, 0, t->ix.slots * 8ull, s));
     HIP_TRY(hipMemsetAsync(t->ix.meta, 0, t->ix.slots * 8ull, s));
     HIP_TRY(hipMemsetAsync(t->ix.first, 0xFF, t->ix.slots * 4ull, s));
-    HIP_TRY(hipMemsetAsync(t->store_len, 0, (t->name_cap + 1ull) * 2ull, s));
+    HIP_TRY(hipMemsetAsync(t->store.len, 0, (t->name_cap + 1ull) * 2ull, s));
     HIP_TRY(hipMemsetAsync(t->at.tag, 0, t->at.slots * 8ull, s));
     HIP_TRY(hipMemsetAsync(t->at.stamp, 0, t->at.slots * 4ull, s));
     HIP_TRY(hipMemsetAsync(t->at.val, 0, t->at.slots * 8ull, s));
@@ -698,7 +663,7 @@ int dnstrack_track(DnsTrack* t, const fb_dns_msg* msgs, const char* names, const
     // the probe positions depend on its size.)
     for (int pass = 0; pass < 2; ++pass) {
         HIP_TRY(hipMemsetAsync(t->d_ctr, 0, kCtrWords * 8ull, s));
-        hipLaunchKernelGGL(k_dns_classify, g, b, 0, s, a, t->ix);
+        hipLaunchKernelGGL(k_dns_classify, g, b, 0, s, a, t->ix.view());
         HIP_TRY(hipGetLastError());
         rc = read_ctr(t, h, s);
         if (rc) return rc;
@@ -712,7 +677,7 @@ int dnstrack_track(DnsTrack* t, const fb_dns_msg* msgs, const char* names, const
     unsigned long long unresolved = h[cQueries];
     while (unresolved) {
         HIP_TRY(hipMemsetAsync(t->d_ctr + cUnresolved, 0, 8, s));
-        hipLaunchKernelGGL(k_dns_name_round, g, b, 0, s, a, t->ix, t->store, t->store_len, t->launch++);
+        hipLaunchKernelGGL(k_dns_name_round, g, b, 0, s, a, t->ix.view(), t->store.names.get(), t->store.len.get(), t->launch++);
         HIP_TRY(hipGetLastError());
         rc = read_ctr(t, h, s);
         if (rc) return rc;
@@ -722,25 +687,25 @@ int dnstrack_track(DnsTrack* t, const fb_dns_msg* msgs, const char* names, const
         unresolved = h[cUnresolved];
     }
     if (h[cQueries]) {
-        hipLaunchKernelGGL(k_dns_name_flag, g, b, 0, s, a, t->ix);
+        hipLaunchKernelGGL(k_dns_name_flag, g, b, 0, s, a, t->ix.view());
         HIP_TRY(hipGetLastError());
-        size_t tmp = t->sort_tmp_bytes;
-        HIP_TRY(rocprim::exclusive_scan(t->sort_tmp, tmp, a.flag, a.rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
-        hipLaunchKernelGGL(k_dns_name_publish, g, b, 0, s, a, t->ix, t->store, t->store_len, (uint32_t)t->names, t->launch++);
+        size_t tmp = t->sort_tmp.size();
+        HIP_TRY(rocprim::exclusive_scan(t->sort_tmp.get(), tmp, a.flag, a.rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
+        hipLaunchKernelGGL(k_dns_name_publish, g, b, 0, s, a, t->ix.view(), t->store.names.get(), t->store.len.get(), (uint32_t)t->names, t->launch++);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_dns_name_ids, g, b, 0, s, a, t->ix);
+        hipLaunchKernelGGL(k_dns_name_ids, g, b, 0, s, a, t->ix.view());
         HIP_TRY(hipGetLastError());
     }
     // pending: sort the setters, take, carry
     {
-        size_t tmp = t->sort_tmp_bytes;
-        HIP_TRY(rocprim::radix_sort_keys(t->sort_tmp, tmp, a.key, t->sorted, (size_t)n, 0u, 49u, s));
+        size_t tmp = t->sort_tmp.size();
+        HIP_TRY(rocprim::radix_sort_keys(t->sort_tmp.get(), tmp, a.key, t->sorted, (size_t)n, 0u, 49u, s));
     }
-    hipLaunchKernelGGL(k_dns_take, g, b, 0, s, a, t->sorted, t->pend_name);
+    hipLaunchKernelGGL(k_dns_take, g, b, 0, s, a, t->sorted, t->pend_name.get());
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_dns_carry, g, b, 0, s, a, t->sorted, t->pend_name, t->pend_time);
+    hipLaunchKernelGGL(k_dns_carry, g, b, 0, s, a, t->sorted, t->pend_name.get(), t->pend_time.get());
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_dns_addr_init, ga, b, 0, s, a, t->at);
+    hipLaunchKernelGGL(k_dns_addr_init, ga, b, 0, s, a, t->at.view());
     HIP_TRY(hipGetLastError());
     rc = read_ctr(t, h, s);
     if (rc) return rc;
@@ -748,7 +713,7 @@ int dnstrack_track(DnsTrack* t, const fb_dns_msg* msgs, const char* names, const
     unresolved = h[cAddrItems];
     while (unresolved) {
         HIP_TRY(hipMemsetAsync(t->d_ctr + cUnresolved, 0, 8, s));
-        hipLaunchKernelGGL(k_dns_addr_round, ga, b, 0, s, a, t->at, t->launch++, (unsigned long long)t->messages);
+        hipLaunchKernelGGL(k_dns_addr_round, ga, b, 0, s, a, t->at.view(), t->launch++, (unsigned long long)t->messages);
         HIP_TRY(hipGetLastError());
         rc = read_ctr(t, h, s);
         if (rc) return rc;
@@ -778,7 +743,7 @@ int dnstrack_track(DnsTrack* t, const fb_dns_msg* msgs, const char* names, const
 
 int dnstrack_expire(DnsTrack* t, unsigned long long now, uint64_t* dropped, hipStream_t s) {
     HIP_TRY(hipMemsetAsync(t->d_ctr + cCount, 0, 8, s));
-    hipLaunchKernelGGL(k_dns_expire, grid_for(kIds), dim3(256), 0, s, t->pend_name, t->pend_time, now, 1u, t->d_ctr + cCount);
+    hipLaunchKernelGGL(k_dns_expire, grid_for(kIds), dim3(256), 0, s, t->pend_name.get(), t->pend_time.get(), now, 1u, t->d_ctr + cCount);
     HIP_TRY(hipGetLastError());
     unsigned long long h = 0;
     HIP_TRY(hipMemcpyAsync(&h, t->d_ctr + cCount, 8, hipMemcpyDeviceToHost, s));
@@ -789,7 +754,7 @@ int dnstrack_expire(DnsTrack* t, unsigned long long now, uint64_t* dropped, hipS
 
 int dnstrack_info(DnsTrack* t, fb_dns_track_info* out, hipStream_t s) {
     HIP_TRY(hipMemsetAsync(t->d_ctr + cCount, 0, 8, s));
-    hipLaunchKernelGGL(k_dns_expire, grid_for(kIds), dim3(256), 0, s, t->pend_name, t->pend_time, 0ull, 0u, t->d_ctr + cCount);
+    hipLaunchKernelGGL(k_dns_expire, grid_for(kIds), dim3(256), 0, s, t->pend_name.get(), t->pend_time.get(), 0ull, 0u, t->d_ctr + cCount);
     HIP_TRY(hipGetLastError());
     unsigned long long h = 0;
     HIP_TRY(hipMemcpyAsync(&h, t->d_ctr + cCount, 8, hipMemcpyDeviceToHost, s));
@@ -807,7 +772,7 @@ int dnstrack_info(DnsTrack* t, fb_dns_track_info* out, hipStream_t s) {
 
 int dnstrack_export_resolutions(DnsTrack* t, fb_dns_resolution* out, uint64_t cap, uint64_t* d_n, hipStream_t s) {
     HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
-    hipLaunchKernelGGL(k_dns_export_resolutions, dim3(sweep_grid(t->at.slots, 1024ull)), dim3(256), 0, s, t->at, out,
+    hipLaunchKernelGGL(k_dns_export_resolutions, dim3(sweep_grid(t->at.slots, 1024ull)), dim3(256), 0, s, t->at.view(), out,
                        (unsigned long long)cap, (unsigned long long*)d_n);
     HIP_TRY(hipGetLastError());
     return FB_OK;
@@ -821,7 +786,7 @@ int dnstrack_export_pending(DnsTrack* t, uint32_t* name_id, uint64_t* time, hipS
 
 int dnstrack_names(DnsTrack* t, const uint32_t* ids, uint64_t n, char* out, uint16_t* len, hipStream_t s) {
     if (n == 0) return FB_OK;
-    hipLaunchKernelGGL(k_dns_names, grid_for(n * kNameDwords), dim3(256), 0, s, t->store, t->store_len, (uint32_t)t->names, ids,
+    hipLaunchKernelGGL(k_dns_names, grid_for(n * kNameDwords), dim3(256), 0, s, t->store.names.get(), t->store.len.get(), (uint32_t)t->names, ids,
                        (unsigned long long)n, reinterpret_cast<uint32_t*>(out), len);
     HIP_TRY(hipGetLastError());
     return FB_OK;
@@ -834,8 +799,8 @@ DnsTables dnstrack_tables(const DnsTrack* t) {
     d.aval = t->at.val;
     d.aslots = t->at.slots;
     d.hash_mask = t->hash_mask;
-    d.names = t->store;
-    d.name_len = t->store_len;
+    d.names = t->store.names;
+    d.name_len = t->store.len;
     d.n_names = (uint32_t)t->names;
     return d;
 }

@@ -3,8 +3,11 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/flodbadd_gpu.h"
+#include "fb_devmem.h"
 
 namespace fbk {
+
+static_assert(kDevmemNoMem == FB_ERR_NOMEM && kDevmemHip == FB_ERR_HIP, "fb_devmem.h reports fb_err codes");
 
 // Sets the thread-local text fb_last_error() returns; returns `code`.
 int set_err(int code, const char* fmt, ...);

@@ -33,17 +33,17 @@ using namespace fbk;
 namespace {
 
 struct RingSlot {
-    uint8_t* h_frames = nullptr;
-    uint32_t* h_offsets = nullptr;
-    fb_dns_out* h_dns = nullptr;
-    fb_batch_stats* h_stats = nullptr;
-    uint8_t* d_frames = nullptr;
-    uint32_t* d_offsets = nullptr;
-    fb_pkt_out* d_out = nullptr;   // segmented records (ceil(max_packets / 64) * 64 slots)
-    uint32_t* d_seg = nullptr;     // segment counts
-    fb_dns_out* d_dns = nullptr;   // the batch's DNS side records, compacted
-    fb_batch_stats* d_stats = nullptr;
-    hipEvent_t ev_h2d = nullptr, ev_done = nullptr;
+    PinnedBuf<uint8_t> h_frames;
+    PinnedBuf<uint32_t> h_offsets;
+    PinnedBuf<fb_dns_out> h_dns;
+    PinnedBuf<fb_batch_stats> h_stats;
+    DevBuf<uint8_t> d_frames;
+    DevBuf<uint32_t> d_offsets;
+    DevBuf<fb_pkt_out> d_out;   // segmented records (ceil(max_packets / 64) * 64 slots)
+    DevBuf<uint32_t> d_seg;     // segment counts
+    DevBuf<fb_dns_out> d_dns;   // the batch's DNS side records, compacted
+    DevBuf<fb_batch_stats> d_stats;
+    DevEvent ev_h2d, ev_done;
     uint32_t n = 0;
     uint64_t bytes = 0;
     uint64_t seq0 = 0;   // ring-wide index of the batch's first frame
@@ -125,8 +125,8 @@ struct fb_ring {
     fb_ring_config cfg{};
     std::vector<RingSlot> slots;
     uint32_t cur = 0;          // the batch being filled
-    hipStream_t copy = nullptr, compute = nullptr;
-    hipStream_t dnsq = nullptr;  // DNS side-record read-back (never queued behind later H2D copies)
+    DevStream copy, compute;
+    DevStream dnsq;            // DNS side-record read-back (never queued behind later H2D copies)
     fb_batch_stats total{};
     uint64_t batches = 0;
     uint64_t seq = 0;          // frames accepted so far
@@ -139,37 +139,16 @@ struct fb_ring {
 
 namespace {
 
-void free_slot(RingSlot& s) {
-    (void)hipHostFree(s.h_frames);
-    (void)hipHostFree(s.h_offsets);
-    (void)hipHostFree(s.h_dns);
-    (void)hipHostFree(s.h_stats);
-    (void)hipFree(s.d_frames);
-    (void)hipFree(s.d_offsets);
-    (void)hipFree(s.d_out);
-    (void)hipFree(s.d_seg);
-    (void)hipFree(s.d_dns);
-    (void)hipFree(s.d_stats);
-    if (s.ev_h2d) (void)hipEventDestroy(s.ev_h2d);
-    if (s.ev_done) (void)hipEventDestroy(s.ev_done);
-    s = RingSlot();
-}
-
 bool alloc_slot(RingSlot& s, const fb_ring_config& c) {
-    const uint64_t np = c.max_packets;
+    const uint64_t np = c.max_packets, bytes = std::max<uint64_t>(c.max_bytes, 1);
     const uint64_t nseg = (np + FB_SEG_FRAMES - 1) / FB_SEG_FRAMES;
-    return hipHostMalloc((void**)&s.h_frames, std::max<uint64_t>(c.max_bytes, 1), hipHostMallocDefault) == hipSuccess &&
-           hipHostMalloc((void**)&s.h_offsets, (np + 1) * 4, hipHostMallocDefault) == hipSuccess &&
-           hipHostMalloc((void**)&s.h_dns, np * sizeof(fb_dns_out), hipHostMallocDefault) == hipSuccess &&
-           hipHostMalloc((void**)&s.h_stats, sizeof(fb_batch_stats), hipHostMallocDefault) == hipSuccess &&
-           hipMalloc((void**)&s.d_frames, std::max<uint64_t>(c.max_bytes, 1)) == hipSuccess &&
-           hipMalloc((void**)&s.d_offsets, (np + 1) * 4) == hipSuccess &&
-           hipMalloc((void**)&s.d_out, nseg * FB_SEG_FRAMES * sizeof(fb_pkt_out)) == hipSuccess &&
-           hipMalloc((void**)&s.d_seg, nseg * 4) == hipSuccess &&
-           hipMalloc((void**)&s.d_dns, np * sizeof(fb_dns_out)) == hipSuccess &&
-           hipMalloc((void**)&s.d_stats, sizeof(fb_batch_stats)) == hipSuccess &&
-           hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming) == hipSuccess;
+    return s.h_frames.alloc(bytes, hipHostMallocDefault) == hipSuccess &&
+           s.h_offsets.alloc(np + 1, hipHostMallocDefault) == hipSuccess &&
+           s.h_dns.alloc(np, hipHostMallocDefault) == hipSuccess &&
+           s.h_stats.alloc(1, hipHostMallocDefault) == hipSuccess &&
+           alloc_each(s.d_frames, bytes, s.d_offsets, np + 1, s.d_out, nseg * FB_SEG_FRAMES, s.d_seg, nseg, s.d_dns, np,
+                      s.d_stats, 1) == hipSuccess &&
+           s.ev_h2d.create() == hipSuccess && s.ev_done.create() == hipSuccess;
 }
 
 void add_stats(fb_batch_stats& t, const fb_batch_stats& b) {
@@ -281,9 +260,7 @@ fb_ring* fb_ring_create(fb_ctx* ctx, const fb_ring_config* cfg) {
     r->cfg = c;
     if (c.copy_threads > 1u) r->pool = new (std::nothrow) CopyPool(std::min<uint32_t>(c.copy_threads, 64u) - 1u);
     r->slots.resize(c.slots);
-    bool ok = hipStreamCreateWithFlags(&r->copy, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&r->compute, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&r->dnsq, hipStreamNonBlocking) == hipSuccess;
+    bool ok = r->copy.create() == hipSuccess && r->compute.create() == hipSuccess && r->dnsq.create() == hipSuccess;
     ok = ok && (c.copy_threads <= 1u || r->pool);
     for (auto& s : r->slots) ok = ok && alloc_slot(s, c);
     if (!ok) {
@@ -299,10 +276,6 @@ int fb_ring_destroy(fb_ring* r) {
     DeviceGuard g(r->device);
     if (r->compute) (void)hipStreamSynchronize(r->compute);
     if (r->copy) (void)hipStreamSynchronize(r->copy);
-    for (auto& s : r->slots) free_slot(s);
-    if (r->copy) (void)hipStreamDestroy(r->copy);
-    if (r->compute) (void)hipStreamDestroy(r->compute);
-    if (r->dnsq) (void)hipStreamDestroy(r->dnsq);
     delete r->pool;
     delete r;
     return FB_OK;
