@@ -363,6 +363,10 @@ int fb_set_session_records(fb_ctx* ctx, int emit);
  *   d_dns   : >= n fb_dns_out, class-DNS records, packet order
  *   d_class : n bytes, fb_class of every frame
  *   d_stats : one fb_batch_stats (overwritten, not accumulated)
+ * d_frames (here, in fb_process_dev, in the frame-taking *_seg_* calls and in fb_seg_batch) may
+ * have any byte alignment: the kernels address the frames by offsets relative to it and check
+ * every load against frames_bytes, and no byte at or past frames_bytes takes part in a result,
+ * whatever lies there in memory.
  * One pass (k_parse_dense): 512-frame tiles whose batch-wide offsets come from a decoupled
  * look-back; a look-back that finds a predecessor tile unpublished for long computes that tile's
  * counts itself instead of waiting on it, so the call never depends on every workgroup being
