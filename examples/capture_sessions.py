@@ -16,7 +16,8 @@ frames injected on `lo` through a second AF_PACKET socket, `--flows` client port
 batch goes through the GPU path (`FlodbaddGpuCapture.process_frames`: parse + classify + session
 table upsert); `--capture-only` skips the GPU (e.g. to write the batch with `--save`).  `--zeek` makes
 the capture timed (each frame's receive time is its capture timestamp) and prints the sessions as
-Zeek conn.log lines, the text of the reference's `format_sessions_zeek`, formatted on the GPU.
+Zeek conn.log lines, the text of the reference's `format_sessions_zeek`, formatted on the GPU; with
+`--history-on-device` the history strings of those lines never leave the GPU (the device store).
 """
 import argparse
 import os
@@ -105,6 +106,8 @@ def main():
     ap.add_argument("--capture-only", action="store_true", help="no GPU: capture (and --save) only")
     ap.add_argument("--zeek", action="store_true",
                     help="print the sessions as Zeek conn.log lines (format_sessions_zeek), formatted on the GPU")
+    ap.add_argument("--history-on-device", action="store_true",
+                    help="with --zeek: keep the history strings in the device store (fb_hist_store_*), not on the host")
     a = ap.parse_args()
     times = [] if a.zeek else None
     try:
@@ -122,7 +125,8 @@ def main():
     from flodbadd_amd.capture import FlodbaddGpuCapture
     from flodbadd_amd.sessions import SessionFilter
     # (a conn.log line prints the session's start time and history: a timed capture that keeps the strings)
-    cap = FlodbaddGpuCapture(0, session_filter=SessionFilter.All, flow_capacity=1 << 16, timed=a.zeek, track_history=a.zeek)
+    cap = FlodbaddGpuCapture(0, session_filter=SessionFilter.All, flow_capacity=1 << 16, timed=a.zeek, track_history=a.zeek,
+                             history_on_device=a.zeek and a.history_on_device)
     try:
         t0 = time.perf_counter()
         r = cap.process_frames(frames, offs, ts=np.array(times, dtype=np.uint64) if a.zeek else None)

@@ -119,6 +119,15 @@ ZEEK_STATS_FIELDS = ["lines", "bytes", "lines_written", "ts_inexact", "hist_mism
 ZEEK_STATS_DTYPE = np.dtype([(f, "<u8") for f in ZEEK_STATS_FIELDS] + [("reserved", "<u8", (3,))])
 assert ZEEK_STATS_DTYPE.itemsize == 64
 FB_ZEEK_FIXED_MAX, FB_ZEEK_STEP, FB_ZEEK_STAGE_BYTES, FB_ZEEK_COOP_HIST = 312, 256, 40000, 64
+# device-resident history (fb_hist_store_*, fb_histstore.hip): the config and the counters, the characters of
+# a block, and the thresholds from which a wave appends a run / decodes a chain together
+HIST_STORE_CONFIG_DTYPE = np.dtype([("block_capacity", "<u8"), ("max_blocks", "<u8"), ("flags", "<u4"),
+                                    ("reserved", "<u4", (3,))])
+HIST_STORE_INFO_FIELDS = ["blocks_capacity", "blocks_high_water", "blocks_free", "blocks_in_use", "chars", "flows",
+                          "appends", "missed_updates"]
+HIST_STORE_INFO_DTYPE = np.dtype([(f, "<u8") for f in HIST_STORE_INFO_FIELDS])
+assert (HIST_STORE_CONFIG_DTYPE.itemsize, HIST_STORE_INFO_DTYPE.itemsize) == (32, 64)
+FB_HIST_BLOCK_CHARS, FB_HIST_COOP_RUN, FB_HIST_COOP_GATHER = 120, 32, 64
 FB_SEGMENT_TIMEOUT_MS = 5000
 FB_CFG_TIMED = 2
 FB_QUEUE_SHARED = 1
@@ -355,6 +364,12 @@ GPU_SYMBOLS = [
     ("fb_flow_export_view_dev", _I, [_P, _P, _P, _U64, _P, _P]),
     ("fb_flow_export_view", _I, [_P, _P, _P, _U64, _PU64, _P]),
     ("fb_format_zeek_dev", _I, [_P, _P, _U64, _P, _P, _U64, _P, _U64, _P, _P, _P]),
+    ("fb_format_zeek_hist_dev", _I, [_P, _P, _U64, _P, _P, _P, _U64, _P, _P, _P]),
+    ("fb_hist_store_enable", _I, [_P, _P]),
+    ("fb_hist_store_append_dev", _I, [_P, _P]),
+    ("fb_hist_store_lengths_dev", _I, [_P, _P, _U64, _U64, _P, _P]),
+    ("fb_hist_store_gather_dev", _I, [_P, _P, _U64, _U64, _P, _P, _U64, _P]),
+    ("fb_hist_store_info_get", _I, [_P, _P]),
     ("fb_dns_track_enable", _I, [_P, _P]),
     ("fb_dns_track_clear", _I, [_P]),
     ("fb_dns_track_dev", _I, [_P, _P, _P, _P, _U32, _P, _P, _P, _P, _P]),

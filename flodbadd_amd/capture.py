@@ -79,7 +79,8 @@ class ZeekLog:
 class FlodbaddGpuCapture:
     def __init__(self, device=0, session_filter=SessionFilter.GlobalOnly, flow_capacity=1 << 20,
                  service_bitmap=None, lan_v6=(), own_ips=(), max_batch_packets=1 << 20, track_history=False,
-                 grow=True, timed=False, track_dns=False, dns_name_capacity=0, dns_addr_capacity=0, dns_hash_mask=0):
+                 grow=True, timed=False, track_dns=False, dns_name_capacity=0, dns_addr_capacity=0, dns_hash_mask=0,
+                 history_on_device=False, history_block_capacity=0, history_max_blocks=0):
         """timed: capture-time session state (FB_CFG_TIMED): every batch then comes with its frames'
         capture timestamps (`ts`, ns) and the sessions carry start / last / end times and the
         segment state with the reference's 5-s timeout (src/packets.rs:137-200).
@@ -87,7 +88,12 @@ class FlodbaddGpuCapture:
         parses and tracks its batch's DNS records on the device, update_sessions runs the domain pass, and the
         sessions carry src_domain / dst_domain.  dns_name_capacity / dns_addr_capacity: names and addresses
         before the first growth (0: the library's defaults); dns_hash_mask: fb_dns_track_config.hash_mask,
-        a testing knob."""
+        a testing knob.
+        history_on_device (with track_history): the history strings live in the context's device store
+        (fb_hist_store_enable) instead of self.histories: every update is followed by one asynchronous append,
+        the getters gather the strings of the flows they return, and export_zeek formats from the store with no
+        history byte crossing the bus.  history_block_capacity / history_max_blocks: fb_hist_store_config (0:
+        the library's defaults)."""
         lib = N.gpu_lib()
         self._keep = []
         cfg = N.FbConfig()
@@ -121,6 +127,11 @@ class FlodbaddGpuCapture:
         # from fb_flow_history_dev when track_history is set
         self.track_history = bool(track_history) and flow_capacity > 0
         self.histories = {}
+        self.history_on_device = self.track_history and bool(history_on_device)
+        if self.history_on_device:
+            hc = np.zeros(1, dtype=N.HIST_STORE_CONFIG_DTYPE)
+            hc[0]["block_capacity"], hc[0]["max_blocks"] = int(history_block_capacity), int(history_max_blocks)
+            N.check(lib.fb_hist_store_enable(self.ctx, N.ptr(hc)))
         self._generation = 0  # table growths seen (slots move when the table grows)
         # whitelist conformance (src/capture.rs:101-106: no list active, conformance true, no exceptions)
         self._lan_v6 = list(lan_v6)
@@ -506,9 +517,53 @@ class FlodbaddGpuCapture:
     def _pull_history(self, n_slots):
         if not self.track_history:
             return
+        if self.history_on_device:  # one asynchronous call: no wait, no download, nothing keyed on the host
+            N.check(N.gpu_lib().fb_hist_store_append_dev(self.ctx, None))
+            return
         self._follow_growth()
         for slot, run in self.flow_history(n_slots).items():
             self.histories[slot] = self.histories.get(slot, "") + run
+
+    def history_store_info(self):
+        """fb_hist_store_info_get: the device store's counters (history_on_device)."""
+        info = np.zeros(1, dtype=N.HIST_STORE_INFO_DTYPE)
+        N.check(N.gpu_lib().fb_hist_store_info_get(self.ctx, N.ptr(info)))
+        return stats_dict(info, N.HIST_STORE_INFO_FIELDS)
+
+    def _gather_histories(self, d_slots, stride, n):
+        """The store's characters of n slots read on the device (d_slots / stride as fb_hist_store_lengths_dev
+        takes them): lengths, one 8-byte read of the total, an exactly sized gather -> (d_chars, d_off, total)."""
+        lib = N.gpu_lib()
+        d_off = N.DeviceBuffer(8 * (n + 1))
+        N.check(lib.fb_hist_store_lengths_dev(self.ctx, d_slots, stride, n, d_off.ptr, None))
+        total = np.zeros(1, dtype=np.uint64)
+        N.check(lib.fb_memcpy_d2h(N.ptr(total), C.c_void_p(d_off.ptr.value + 8 * n), 8, None))
+        N.check(lib.fb_stream_sync(None))
+        total = int(total[0])
+        d_chars = N.DeviceBuffer(max(total, 1))
+        N.check(lib.fb_hist_store_gather_dev(self.ctx, d_slots, stride, n, d_off.ptr, d_chars.ptr, total, None))
+        return d_chars, d_off, total
+
+    def flow_histories(self, slots=None):
+        """The history strings the device store holds (history_on_device) -> {slot: str} for `slots` (an array
+        of table slots; None: every slot of the table), flows without characters left out."""
+        if not self.history_on_device:
+            raise ValueError("flow_histories reads the device store (history_on_device=True)")
+        if slots is None:
+            n, d_slots, sl = int(self.table_info()["capacity"]), None, None
+        else:
+            sl = np.ascontiguousarray(slots, dtype=np.uint32)
+            n = len(sl)
+            if n == 0:
+                return {}
+            d_slots = N.DeviceBuffer(sl.nbytes).upload(sl)
+        d_chars, d_off, total = self._gather_histories(d_slots.ptr if d_slots else None, 4, n)
+        if total == 0:
+            return {}
+        off = d_off.download(np.zeros(n + 1, dtype=np.uint64)).astype(np.int64)
+        text = d_chars.download(np.zeros(total, dtype=np.uint8), total).tobytes().decode("ascii")
+        has = np.flatnonzero(off[1:] > off[:-1])
+        return {int(i if sl is None else sl[i]): text[off[i]:off[i + 1]] for i in has}
 
     def flow_count(self):
         n = C.c_uint64(0)
@@ -618,7 +673,11 @@ class FlodbaddGpuCapture:
         views = self.export_view(view_set, since, session_filter)
         if keep is not None and len(views):
             views = views[keep(views)]
-        out = views_to_sessions(views, self.histories if self.track_history else None, self._bl_names, timed=self.timed,
+        if self.history_on_device:  # the strings of the selected flows only, gathered from the store
+            histories = self.flow_histories(views["rec"]["slot"])
+        else:
+            histories = self.histories if self.track_history else None
+        out = views_to_sessions(views, histories, self._bl_names, timed=self.timed,
                                 whitelist=whitelist, blacklist=blacklist, domains=self._domains())
         for info in out if (overlay_host_ok and self._wl_host_ok) else ():  # the flows the pass left to the host
             if info.session in self._wl_host_ok and info.is_whitelisted is WhitelistState.NonConforming:
@@ -638,7 +697,7 @@ class FlodbaddGpuCapture:
         st = np.zeros(1, dtype=N.AGE_STATS_DTYPE)
         N.check(N.gpu_lib().fb_flow_age(self.ctx, int(now_ns), N.ptr(prm), N.FB_AGE_PURGE if purge else 0, N.ptr(st),
                                         None))
-        if self.track_history:
+        if self.track_history and not self.history_on_device:  # (the device store's plane follows by itself)
             self._follow_growth()
         return stats_dict(st, N.AGE_STATS_FIELDS)
 
@@ -684,7 +743,13 @@ class FlodbaddGpuCapture:
         n = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cnt)
         d_hist = d_hoff = None
         n_slots = hist_bytes = 0
-        if self.track_history:
+        if self.history_on_device and n:
+            # the selected records' histories gathered from the store, indexed by record: no history byte
+            # crosses the bus in either direction
+            d_slot0 = C.c_void_p(d_views.ptr.value + N.FLOW_VIEW_DTYPE.fields["rec"][1] +
+                                 N.FLOW_REC_DTYPE.fields["slot"][1])
+            d_hist, d_hoff, hist_bytes = self._gather_histories(d_slot0, N.FLOW_VIEW_DTYPE.itemsize, n)
+        elif self.track_history and not self.history_on_device:
             n_slots = int(self.table_info()["capacity"])
             chars, off = pack_histories(self.histories, n_slots)
             hist_bytes = len(chars)
@@ -694,9 +759,13 @@ class FlodbaddGpuCapture:
             d_hoff.upload(off)
         text_cap = n * N.FB_ZEEK_FIXED_MAX + hist_bytes
         d_text, d_off, d_stats = N.DeviceBuffer(max(text_cap, 1)), N.DeviceBuffer(8 * (n + 1)), N.DeviceBuffer(64)
-        N.check(lib.fb_format_zeek_dev(self.ctx, d_views.ptr, n, d_hist.ptr if d_hist else None,
-                                       d_hoff.ptr if d_hoff else None, n_slots, d_text.ptr, text_cap, d_off.ptr,
-                                       d_stats.ptr, None))
+        if self.history_on_device and n:
+            N.check(lib.fb_format_zeek_hist_dev(self.ctx, d_views.ptr, n, d_hist.ptr, d_hoff.ptr, d_text.ptr, text_cap,
+                                                d_off.ptr, d_stats.ptr, None))
+        else:
+            N.check(lib.fb_format_zeek_dev(self.ctx, d_views.ptr, n, d_hist.ptr if d_hist else None,
+                                           d_hoff.ptr if d_hoff else None, n_slots, d_text.ptr, text_cap, d_off.ptr,
+                                           d_stats.ptr, None))
         st = stats_dict(d_stats.download(np.zeros(1, dtype=N.ZEEK_STATS_DTYPE)), N.ZEEK_STATS_FIELDS)
         if st["hist_mismatch"]:
             raise N.FbError(N.FB_ERR_INTERNAL, "%d flows whose history length differs from the table's hist_len"
@@ -1084,7 +1153,8 @@ class FlodbaddGpuCapture:
         """src/capture.rs:396 (`stop()` clears the table, capture.rs:383)."""
         N.check(N.gpu_lib().fb_flow_clear(self.ctx, None))
         N.check(N.gpu_lib().fb_stream_sync(None))
-        self.histories = {}
+        if not self.history_on_device:  # (fb_flow_clear emptied the device store)
+            self.histories = {}
         self._wl_host_ok = set()
         self._bl_marked = False
         self._dom_ran = False

@@ -129,7 +129,8 @@ struct EnrichDev {
 // Per-slot planes: arrays beside the table, one element per slot, that a flow's element follows through
 // every slot move.  Described once here; the functions below (plane_ensure .. plane_copy_out) are the
 // only code that allocates, moves, clears or frees one, so a new plane is one entry and its pass.
-enum PlaneId : uint32_t { kPlaneTime, kPlaneStatus, kPlaneWl, kPlaneBl, kPlaneAn, kPlaneMod, kPlaneDom, kPlanes };
+enum PlaneId : uint32_t { kPlaneTime, kPlaneStatus, kPlaneWl, kPlaneBl, kPlaneAn, kPlaneMod, kPlaneDom, kPlaneHist,
+                          kPlanes };
 struct PlaneDesc {
     size_t elem;       // bytes per slot
     const char* name;  // in error text
@@ -149,6 +150,8 @@ static const PlaneDesc kPlaneDesc[kPlanes] = {
     // the passes' last_modified stamps (fb_set_pass_time; read by fb_view.hip): made by the first stamped pass
     {8, "stamp plane", true, false, launch_plane_remap<unsigned long long>},
     {sizeof(fb_flow_domain), "domain plane", true, false, launch_plane_remap<uint2>},   // fb_domains.hip
+    // the history store's {head, tail, len, reserved} (fb_histstore.hip): made by fb_hist_store_enable
+    {sizeof(uint4), "history plane", true, false, launch_plane_remap<uint4>},
 };
 static_assert(sizeof(fb_flow_domain) == sizeof(uint2), "one name-id pair per slot");
 // the counter words of one synchronous pass over the table (pass_begin / pass_end)
@@ -224,6 +227,11 @@ struct fb_ctx {
     EnrichDev en;   // fb_set_asn_tables / fb_set_blacklists
     // DNS tracker (fb_dns_track_enable, fb_dnstrack.hip); null: tracking is off (freed by fb_destroy)
     DnsTrack* dns = nullptr;
+    // history store (fb_hist_store_enable, fb_histstore.hip); null: off (freed by fb_destroy).  hs_updates:
+    // non-empty update calls since enable; hs_seen: the one the last append call looked at; hs_applied: the
+    // updates an append ran for
+    HistStore* hs = nullptr;
+    uint64_t hs_updates = 0, hs_seen = 0, hs_applied = 0;
     StreamScratch mscratch;  // multi-GPU merge scratch (export owner counts / merge tables)
     DevBuf<unsigned long long> d_n;
     // ordered per-flow state: update calls since create/clear
@@ -663,6 +671,7 @@ int fb_destroy(fb_ctx* c) {
     DeviceGuard g(c->device);
     (void)hipDeviceSynchronize();
     dnstrack_free(c->dns);
+    histstore_free(c->hs);
     delete c;
     return FB_OK;
 }
@@ -1566,6 +1575,7 @@ static int flow_update(fb_ctx* c, const fb_pkt_out* d_recs, const uint32_t* d_se
         c->next_ts = nullptr;
     }
     ++c->flow_batch;
+    if (c->hs) ++c->hs_updates;
     c->last_set = set;
     c->last_recs = d_recs;
     c->last_part = p.rec_part;
@@ -1917,6 +1927,9 @@ int fb_flow_age(fb_ctx* c, uint64_t now_ns, const fb_age_params* params, uint32_
         c->last_part = nullptr;
         c->mbox->flows = h[7];
         c->mbox->max_part = h[8];
+        if (c->hs && c->tb.plane[kPlaneHist])  // the removed flows' blocks, read off the plane before it moves
+            rc = histstore_free_sweep(c->hs, c->plane<uint4>(kPlaneHist), c->d_remap, c->tb.cap, s);
+        if (rc) return rc;
         rc = planes_follow_purge(c, s);
         if (rc) return rc;
     }
@@ -2415,8 +2428,8 @@ int fb_flow_export_view(fb_ctx* c, const fb_view_query* q, fb_flow_view* out, ui
 }
 
 // ---- Zeek conn.log export (fb_zeek.hip) -----------------------------------------------------------
-int fb_format_zeek_dev(fb_ctx* c, const fb_flow_view* d_views, uint64_t n, const uint8_t* d_hist,
-                       const uint64_t* d_hist_off, uint64_t n_slots, uint8_t* d_text, uint64_t text_cap,
+static int format_zeek(fb_ctx* c, const fb_flow_view* d_views, uint64_t n, const uint8_t* d_hist,
+                       const uint64_t* d_hist_off, uint64_t n_slots, bool by_record, uint8_t* d_text, uint64_t text_cap,
                        uint64_t* d_line_off, fb_zeek_stats* d_stats, void* stream) {
     if (!c || !d_views || !d_line_off || !d_stats)
         return set_err(FB_ERR_INVAL, "ctx, d_views, d_line_off and d_stats are required");
@@ -2443,12 +2456,133 @@ int fb_format_zeek_dev(fb_ctx* c, const fb_flow_view* d_views, uint64_t n, const
     a.hist = d_hist;
     a.hist_off = reinterpret_cast<const unsigned long long*>(d_hist_off);
     a.n_slots = n_slots;
+    a.by_record = by_record;
     a.text = d_text;
     a.cap = text_cap;
     a.off = reinterpret_cast<unsigned long long*>(d_line_off);
     a.stats = d_stats;
     HIP_TRY(launch_zeek(a, !c->zeek_direct, c->zeek_tmp.get(), c->zeek_tmp.capacity(), s));
     return c->zeek_tmp.release(s);
+}
+
+int fb_format_zeek_dev(fb_ctx* c, const fb_flow_view* d_views, uint64_t n, const uint8_t* d_hist,
+                       const uint64_t* d_hist_off, uint64_t n_slots, uint8_t* d_text, uint64_t text_cap,
+                       uint64_t* d_line_off, fb_zeek_stats* d_stats, void* stream) {
+    return format_zeek(c, d_views, n, d_hist, d_hist_off, n_slots, false, d_text, text_cap, d_line_off, d_stats, stream);
+}
+
+int fb_format_zeek_hist_dev(fb_ctx* c, const fb_flow_view* d_views, uint64_t n, const uint8_t* d_hist,
+                            const uint64_t* d_hist_off, uint8_t* d_text, uint64_t text_cap, uint64_t* d_line_off,
+                            fb_zeek_stats* d_stats, void* stream) {
+    return format_zeek(c, d_views, n, d_hist, d_hist_off, n, true, d_text, text_cap, d_line_off, d_stats, stream);
+}
+
+// ---- device-resident history (fb_histstore.hip) ---------------------------------------------------------
+static int hs_ready(fb_ctx* c) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    if (!c->hs) return set_err(FB_ERR_INVAL, "the history store is not enabled (fb_hist_store_enable)");
+    return FB_OK;
+}
+
+int fb_hist_store_enable(fb_ctx* c, const fb_hist_store_config* cfg) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (c->hs) return set_err(FB_ERR_INVAL, "the history store is already enabled");
+    if (c->flow_batch != 0)
+        return set_err(FB_ERR_INVAL, "the table has taken %u update calls since create / clear: their characters "
+                       "are not known to the store", c->flow_batch);
+    static const fb_hist_store_config kDefault = {};
+    if (!cfg) cfg = &kDefault;
+    if (cfg->flags || cfg->reserved[0] || cfg->reserved[1] || cfg->reserved[2])
+        return set_err(FB_ERR_INVAL, "flags and reserved must be 0");
+    DeviceGuard g(c->device);
+    int rc = drain_updates(c);
+    if (!rc) rc = plane_ensure(c, kPlaneHist, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    rc = histstore_create(&c->hs, cfg, c->grow, c->flow_recs);
+    c->hs_updates = c->hs_seen = c->hs_applied = 0;
+    return rc;
+}
+
+int fb_hist_store_append_dev(fb_ctx* c, void* stream) {
+    int rc = hs_ready(c);
+    if (rc) return rc;
+    if (c->hs_seen == c->hs_updates) return FB_OK;  // this update has had its append (or there was none)
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    rc = join_updates(c, s);
+    if (rc) return rc;
+    const uint32_t n = c->last_recs ? c->last_slots : 0u;
+    if (n == 0) return FB_OK;  // the update's slots have moved since (a purge): it stays a missed update
+    // everything that can fail, wait or allocate comes before the first kernel
+    rc = histstore_admit(c->hs, n, s);
+    if (rc) return rc;
+    const uint64_t cnt_bytes = flow_history_cnt_bytes(c->last_chunks);
+    if (cnt_bytes > c->d_hist_cnt.size() || c->flow_recs > histstore_scratch_slots(c->hs)) {
+        rc = drain_updates(c);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(s));
+        if (cnt_bytes > c->d_hist_cnt.size() && c->d_hist_cnt.alloc(cnt_bytes) != hipSuccess)
+            return set_err(FB_ERR_NOMEM, "history block counts (%llu bytes)", (unsigned long long)cnt_bytes);
+        rc = histstore_scratch(c->hs, c->flow_recs);
+        if (rc) return rc;
+    }
+    if (c->ev_hist.create() != hipSuccess) return set_err(FB_ERR_HIP, "history event");
+    rc = plane_ensure(c, kPlaneHist, s);  // (dropped by a purge whose move failed: every history starts again)
+    if (rc) return rc;
+    HIP_TRY(launch_flow_history(c->last_p, c->last_chunks, histstore_run_slots(c->hs), histstore_run_chars(c->hs),
+                                histstore_run_count(c->hs), c->tb.hist_slow,
+                                cnt_bytes ? reinterpret_cast<uint32_t*>(c->d_hist_cnt.get()) : nullptr, s));
+    rc = histstore_append(c->hs, c->plane<uint4>(kPlaneHist), c->tb.cap, n, n, s);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c->ev_hist, s));
+    c->hist_pending = true;
+    c->hs_seen = c->hs_updates;
+    ++c->hs_applied;
+    return FB_OK;
+}
+
+int fb_hist_store_lengths_dev(fb_ctx* c, const void* d_slots, uint64_t stride_bytes, uint64_t n, uint64_t* d_off,
+                              void* stream) {
+    int rc = hs_ready(c);
+    if (rc) return rc;
+    if (!d_off || (d_slots && (stride_bytes < 4 || (stride_bytes & 3u) || (reinterpret_cast<uintptr_t>(d_slots) & 3u))))
+        return set_err(FB_ERR_INVAL, "d_off is required; d_slots and stride_bytes must be multiples of 4");
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    rc = join_updates(c, s);
+    if (rc) return rc;
+    return histstore_lengths(c->hs, c->plane<uint4>(kPlaneHist), c->tb.cap, d_slots, stride_bytes, n, d_off, s);
+}
+
+int fb_hist_store_gather_dev(fb_ctx* c, const void* d_slots, uint64_t stride_bytes, uint64_t n, const uint64_t* d_off,
+                             uint8_t* d_chars, uint64_t cap, void* stream) {
+    int rc = hs_ready(c);
+    if (rc) return rc;
+    if (!d_off || (cap && !d_chars) ||
+        (d_slots && (stride_bytes < 4 || (stride_bytes & 3u) || (reinterpret_cast<uintptr_t>(d_slots) & 3u))))
+        return set_err(FB_ERR_INVAL, "d_off and d_chars are required; d_slots and stride_bytes must be multiples of 4");
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    rc = join_updates(c, s);
+    if (rc) return rc;
+    return histstore_gather(c->hs, c->plane<uint4>(kPlaneHist), c->tb.cap, d_slots, stride_bytes, n, d_off, d_chars, cap, s);
+}
+
+int fb_hist_store_info_get(fb_ctx* c, fb_hist_store_info* info) {
+    int rc = hs_ready(c);
+    if (rc) return rc;
+    if (!info) return set_err(FB_ERR_INVAL, "info is NULL");
+    memset(info, 0, sizeof(*info));
+    DeviceGuard g(c->device);
+    rc = drain_updates(c);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (appends run on the caller's streams)
+    rc = histstore_info(c->hs, c->plane<uint4>(kPlaneHist), c->tb.cap, info, nullptr);
+    info->appends = c->hs_applied;
+    info->missed_updates = c->hs_updates - c->hs_applied;
+    return rc;
 }
 
 // ---- multi-GPU merge (fb_merge.hip) ---------------------------------------------------------------
@@ -2592,6 +2726,7 @@ int fb_flow_clear(fb_ctx* c, void* stream) {
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->tb.slots, 0, c->tb.cap * sizeof(FlowSlot), (hipStream_t)stream));
     rc = planes_clear(c, (hipStream_t)stream);
+    if (!rc && c->hs) rc = histstore_clear(c->hs, (hipStream_t)stream);  // (the plane went with planes_clear)
     if (rc) return rc;
     c->flow_batch = 0;
     c->clear_seq = c->upd_seq;

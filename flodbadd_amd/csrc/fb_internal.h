@@ -927,6 +927,7 @@ struct ZeekArgs {
     const uint8_t* hist;
     const unsigned long long* hist_off;
     unsigned long long n_slots;
+    bool by_record = false;  // fb_format_zeek_hist_dev: hist_off is indexed by the record's position (n_slots = n)
     uint8_t* text;
     unsigned long long cap;
     unsigned long long* off;
@@ -999,6 +1000,27 @@ int dnstrack_export_pending(DnsTrack* t, uint32_t* name_id, uint64_t* time, hipS
 int dnstrack_names(DnsTrack* t, const uint32_t* ids, uint64_t n, char* out, uint16_t* len, hipStream_t s);
 int dnstrack_lookup(DnsTrack* t, const fb_ip* ips, uint64_t n, uint32_t* name_id, hipStream_t s);
 DnsTables dnstrack_tables(const DnsTrack* t);
+
+// Device-resident history (fb_histstore.hip, fb_hist_store_*).  The per-slot plane element
+// {head, tail, len, reserved} belongs to the context (kPlaneHist); the handle owns the block pool, the free
+// stack, the control words, the mailbox and the append's run scratch.  Every function returns an fb_err.
+struct HistStore;
+int histstore_create(HistStore** h, const fb_hist_store_config* cfg, bool can_grow, uint64_t rec_slots);
+void histstore_free(HistStore* h);
+int histstore_scratch(HistStore* h, uint64_t rec_slots);
+uint64_t histstore_scratch_slots(const HistStore* h);
+uint8_t* histstore_run_chars(HistStore* h);
+uint32_t* histstore_run_slots(HistStore* h);
+uint32_t* histstore_run_count(HistStore* h);
+int histstore_admit(HistStore* h, uint64_t bound, hipStream_t s);
+int histstore_append(HistStore* h, uint4* plane, uint64_t tcap, uint32_t rec_slots, uint64_t bound, hipStream_t s);
+int histstore_free_sweep(HistStore* h, const uint4* plane, const uint32_t* remap, uint64_t tcap, hipStream_t s);
+int histstore_clear(HistStore* h, hipStream_t s);
+int histstore_lengths(HistStore* h, const uint4* plane, uint64_t tcap, const void* d_slots, uint64_t stride, uint64_t n,
+                      uint64_t* d_off, hipStream_t s);
+int histstore_gather(HistStore* h, const uint4* plane, uint64_t tcap, const void* d_slots, uint64_t stride, uint64_t n,
+                     const uint64_t* d_off, uint8_t* d_chars, uint64_t cap, hipStream_t s);
+int histstore_info(HistStore* h, const uint4* plane, uint64_t tcap, fb_hist_store_info* out, hipStream_t s);
 
 // Domain pass over the table (fb_domains.hip, fb_flow_domains): populate_domain_names (src/capture.rs:
 // 1307-1411) restricted to the passive resolutions.  dom: two name ids per slot (0: none); status: the

@@ -39,15 +39,17 @@ struct Hist {
     bool mismatch;
 };
 // The history of a record: the blob's range of its slot (the blob decides; rec.hist_len only counts as a
-// mismatch), empty without a blob or for a slot the offsets do not cover.
-__device__ __forceinline__ Hist hist_of(const ZeekArgs& a, const fb_flow_rec& r) {
+// mismatch), empty without a blob or for a slot the offsets do not cover.  The offsets are indexed by the
+// record's slot, or (fb_format_zeek_hist_dev) by its position i in the views.
+__device__ __forceinline__ Hist hist_of(const ZeekArgs& a, const fb_flow_rec& r, unsigned long long i) {
     Hist h = {nullptr, 0u, false};
     if (!a.hist) return h;
-    if ((unsigned long long)r.slot >= a.n_slots) {
+    const unsigned long long at = a.by_record ? i : (unsigned long long)r.slot;
+    if (at >= a.n_slots) {
         h.mismatch = true;
         return h;
     }
-    const unsigned long long o0 = a.hist_off[r.slot], o1 = a.hist_off[r.slot + 1ull];
+    const unsigned long long o0 = a.hist_off[at], o1 = a.hist_off[at + 1ull];
     if (o1 > o0 && o1 - o0 <= 0xFFFFFFFFull) {
         h.p = a.hist + o0;
         h.len = (uint32_t)(o1 - o0);
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(256) void k_zeek_len(const ZeekArgs a) {
         bool inexact = false, mismatch = false;
         if (i < a.n) {
             const fb_flow_view v = a.views[i];  // (a copy: every load of the record issues before the first use)
-            const Hist h = hist_of(a, v.rec);
+            const Hist h = hist_of(a, v.rec, i);
             a.off[i + 1ull] = fbzeek::zeek_line_len(v, h.len);
             inexact = fbzeek::zeek_inexact(v);
             mismatch = h.mismatch;
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(256) void k_zeek_write(const ZeekArgs a) {
         if (fits) {
             const fb_flow_view v = a.views[i];  // (a copy: every load of the record issues before the first use)
             line = staged ? stage + mis + (uint32_t)(start - r0) : a.text + start;
-            h = hist_of(a, v.rec);
+            h = hist_of(a, v.rec, i);
             coop = h.len >= FB_ZEEK_COOP_HIST;
             fbzeek::zeek_line_write(v, coop ? nullptr : h.p, h.len, line, &hist_at);
         }

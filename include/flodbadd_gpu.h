@@ -561,7 +561,8 @@ int fb_flow_join(fb_ctx* ctx, void* stream);
  * string, batch after batch, reproduces the reference's history.  Both arrays need room for the
  * last update's record slots: the n frames / packets of its batch (dense), ceil(n/64)*64
  * (segmented); slots past *d_n_hist are scratch.  The update's d_recs (and d_seg, d_stats) must
- * still be valid.  DEVICE pointers, asynchronous on `stream`.
+ * still be valid.  DEVICE pointers, asynchronous on `stream`.  A host that does not want the strings
+ * itself enables the device store instead: fb_hist_store_append_dev appends the same runs on the device.
  */
 int fb_flow_history_dev(fb_ctx* ctx, uint8_t* d_hist, uint32_t* d_hist_slot, uint32_t* d_n_hist,
                         void* stream);
@@ -1219,6 +1220,77 @@ typedef struct fb_zeek_stats {
 int fb_format_zeek_dev(fb_ctx* ctx, const fb_flow_view* d_views, uint64_t n, const uint8_t* d_hist,
                        const uint64_t* d_hist_off, uint64_t n_slots, uint8_t* d_text, uint64_t text_cap,
                        uint64_t* d_line_off, fb_zeek_stats* d_stats, void* stream);
+/* The same lines from history indexed by RECORD: d_hist_off has n + 1 entries and record i's characters are
+ * d_hist[d_hist_off[i] .. d_hist_off[i + 1]) -- what fb_hist_store_lengths_dev / fb_hist_store_gather_dev
+ * write for the view records' slots.  Everything else (both write paths, hist_mismatch = stored length !=
+ * rec.hist_len, the text_cap rule, the errors) is fb_format_zeek_dev's. */
+int fb_format_zeek_hist_dev(fb_ctx* ctx, const fb_flow_view* d_views, uint64_t n, const uint8_t* d_hist,
+                            const uint64_t* d_hist_off, uint8_t* d_text, uint64_t text_cap, uint64_t* d_line_off,
+                            fb_zeek_stats* d_stats, void* stream);
+
+/* ---- device-resident session history (fb_histstore.hip) -------------------------------
+ * SessionStats.history (src/packets.rs:187-198, 410-426) kept on the device, opt-in: after
+ * fb_hist_store_enable, fb_hist_store_append_dev after every update appends that update's characters
+ * (fb_flow_history_dev's runs) to per-flow chains of 64-byte blocks -- a u32 link and 60 bytes of 4-bit
+ * codes (1 + the FB_HIST_CHARS index, low nibble first): FB_HIST_BLOCK_CHARS characters a block.  A flow's
+ * chain follows it through table growths and purges (a purge returns the removed flows' blocks to the
+ * store's free stack; fb_flow_clear empties the store).  A context that never enables the store behaves
+ * exactly as before, and so does every other entry point with a store.
+ * Memory: 16 B per table slot, 64 B per started block (a flow of L characters holds ceil(L / 120)); the pool
+ * starts at block_capacity blocks and doubles (one allocation, one device-to-device copy, ids unchanged) when
+ * the blocks in use plus the record slots of the appends in flight could pass it.  With FB_CFG_FIXED_TABLE
+ * the store never allocates or frees device memory after fb_hist_store_enable (the rule a live resident
+ * queue needs): an append the pool cannot be shown to hold fails with FB_ERR_TABLE_FULL instead, before any
+ * of its kernels has run, and the update scratch it sizes its run scratch by must not grow either (enable
+ * after the largest batch's scratch exists, or keep batches within it).
+ * FB_HIST_COOP_RUN: the run length (characters one flow gained in one update) from which a wavefront
+ * appends the run together instead of one lane; FB_HIST_COOP_GATHER: the stored length from which a
+ * wavefront decodes a chain together in fb_hist_store_gather_dev. */
+#define FB_HIST_BLOCK_CHARS 120u
+#ifndef FB_HIST_COOP_RUN /* (a build may override it to measure another value; 2 .. FB_HIST_BLOCK_CHARS) */
+#define FB_HIST_COOP_RUN 32u
+#endif
+#define FB_HIST_COOP_GATHER 64u
+typedef struct fb_hist_store_config {
+    uint64_t block_capacity; /*  0: blocks of the first pool (0 = 2^20)                                   */
+    uint64_t max_blocks;     /*  8: the pool never grows past this (0 = 2^32 - 2)                         */
+    uint32_t flags;          /* 16: must be 0                                                             */
+    uint32_t reserved[3];    /* 20: must be 0                                                             */
+} fb_hist_store_config;      /* 32 bytes */
+typedef struct fb_hist_store_info {
+    uint64_t blocks_capacity;   /*  0: blocks the pool holds                                              */
+    uint64_t blocks_high_water; /*  8: ids ever taken from the bump cursor                                */
+    uint64_t blocks_free;       /* 16: ids on the free stack                                              */
+    uint64_t blocks_in_use;     /* 24: high water - free = the sum of ceil(len / 120) over the flows      */
+    uint64_t chars;             /* 32: characters stored                                                  */
+    uint64_t flows;             /* 40: slots with a non-empty history                                     */
+    uint64_t appends;           /* 48: appends that ran since enable                                      */
+    uint64_t missed_updates;    /* 56: update calls since enable that no append followed                  */
+} fb_hist_store_info;           /* 64 bytes */
+/* Enables the store (cfg NULL = defaults).  FB_ERR_INVAL without a flow table, for non-zero flags /
+ * reserved, when the store is already enabled, or when the table has taken an update since create /
+ * fb_flow_clear (the store cannot know the earlier characters). */
+int fb_hist_store_enable(fb_ctx* ctx, const fb_hist_store_config* cfg);
+/* Appends the LAST update's history characters.  Same preconditions as fb_flow_history_dev (the update's
+ * d_recs, d_seg and d_stats still valid; joins the update stream); asynchronous on `stream` with no device
+ * wait unless the pool may be too small (above).  A second append for the same update, or an append after an
+ * empty update, appends nothing and returns FB_OK; so does one whose update's slots have since moved (a
+ * purge), which stays counted in missed_updates.  FB_ERR_INVAL without a store. */
+int fb_hist_store_append_dev(fb_ctx* ctx, void* stream);
+/* d_off[0 .. n]: the exclusive scan of the stored lengths of n slots, d_off[n] the total.  d_slots NULL:
+ * slots 0 .. n - 1; else slot i is the u32 at (const char*)d_slots + i * stride_bytes (4 for a packed
+ * array; sizeof(fb_flow_view) with d_slots = &d_views[0].rec.slot for view records).  A slot at or past the
+ * table's capacity has length 0.  DEVICE pointers, asynchronous. */
+int fb_hist_store_lengths_dev(fb_ctx* ctx, const void* d_slots, uint64_t stride_bytes, uint64_t n, uint64_t* d_off,
+                              void* stream);
+/* The characters of the same slots, decoded to FB_HIST_CHARS letters: slot i's at d_chars[d_off[i] ..
+ * d_off[i + 1]).  A range that ends past `cap` is not written at all and nothing at or past d_chars + cap
+ * is stored.  With d_slots NULL and n = the table's capacity the pair (d_chars, d_off) is what
+ * fb_format_zeek_dev takes.  DEVICE pointers, asynchronous. */
+int fb_hist_store_gather_dev(fb_ctx* ctx, const void* d_slots, uint64_t stride_bytes, uint64_t n, const uint64_t* d_off,
+                             uint8_t* d_chars, uint64_t cap, void* stream);
+/* The store's counters.  Synchronous (waits for the updates and appends in flight). */
+int fb_hist_store_info_get(fb_ctx* ctx, fb_hist_store_info* info);
 
 /* ---- multi-GPU session table (BASELINE configs[4]) ------------------------------
  * The reference runs one capture task per interface into ONE shared DashMap (src/capture.rs:946-1016,
