@@ -17,7 +17,9 @@ M1, M2, M3 = np.uint64(0xBF58476D1CE4E5B9), np.uint64(0xFF51AFD7ED558CCD), np.ui
 
 
 def flow_hash(words):
-    """fb_flow_hash (fb_internal.h flow_hash_words) over [n,10] uint32 key words, vectorised."""
+    """fb_flow_hash (fb_internal.h flow_hash_words) over [n,10] uint32 key words, vectorised.  A copy kept
+    for this experiment alone: the tested restatement is tests/keyspace.py's flow_hash (against
+    orc_flow_hash and the library's fb_flow_hash)."""
     w = words.astype(np.uint64)
     h = np.full(len(w), M3, dtype=np.uint64)
     with np.errstate(over="ignore"):
