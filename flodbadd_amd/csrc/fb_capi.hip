@@ -172,6 +172,22 @@ struct FlowTable {
     DevBuf<uint8_t> plane[kPlanes];       // [cap * kPlaneDesc[p].elem]
 };
 
+// What a fused parse writes and the update of the same batch reads, per record slot: the table partition
+// and the update entry (RecScratch buffers).  A value of one call, handed from the entry point to its
+// parse and its update; empty: no fused hand-off.
+struct FusedParts { uint32_t* part = nullptr; uint4* ent = nullptr; };
+// The last table update, as the history calls need it: valid until the update's scratch is reallocated,
+// its slots move (a growth, a purge, a clear) or an empty update follows.
+struct LastUpdate {
+    FlowParams p;
+    uint32_t slots = 0, chunks = 0;
+    bool valid = false;
+    void invalidate() { valid = false; }
+    uint32_t live_slots() const { return valid ? slots : 0u; }  // record slots whose history can still be read
+};
+// Record slots of a segmented batch of n frames: whole segments.
+static constexpr uint32_t seg_slots(uint32_t n) { return (n + FB_SEG_FRAMES - 1) / FB_SEG_FRAMES * FB_SEG_FRAMES; }
+
 struct fb_ctx {
     int device = 0;
     std::unique_ptr<DevConfig> h_cfg;  // host shadow
@@ -248,25 +264,12 @@ struct fb_ctx {
     DevEvent ev_upd[2];                         // after the update of async batch k (k & 1)
     uint64_t async_k = 0;                       // async batches issued
     uint32_t upd_word[2] = {4u, 4u};            // error word (launch & 3) of the async update in slot k & 1 (4: none)
-    uint32_t last_set = 0;                // the update scratch set of the last update (history)
-    // Borrowed, never freed here: the caller's buffers and event, and positions inside rs.
+    // Borrowed, never freed here: the caller's buffers and event.
     hipEvent_t stage_event = nullptr;  // fb_set_stage_event (caller-owned): recorded between the
                                        // parse and the update of fb_process[_seg]_dev
-    const unsigned long long* next_ts = nullptr;  // fb_set_frame_times: the next update's frame times
-    const fb_pkt_out* part_recs = nullptr;  // the records part_buf was written for (one update)
-    uint32_t* part_buf = nullptr;           // the partition buffer the last fused parse wrote
-    uint32_t* part_target = nullptr;        // the buffer the next fused parse writes (null: rs.rec_part)
-    uint4* ent_buf = nullptr;               // the entries the last fused parse wrote (with part_buf)
-    uint4* ent_target = nullptr;            // the entries the next fused parse writes (null: rs.rec_ent)
+    const unsigned long long* next_ts = nullptr;  // fb_set_frame_times arms it, take_frame_times alone reads + clears it
     const void* async_prev[3] = {nullptr, nullptr, nullptr};  // the last async batch's records, counts, stats
-    // ... the last update, for fb_flow_history_dev
-    const fb_pkt_out* last_recs = nullptr;
-    const uint32_t* last_part = nullptr;  // the fused parse's per-record words of the last update
-    const uint32_t* last_seg = nullptr;
-    const fb_batch_stats* last_stats = nullptr;
-    uint32_t last_slots = 0;
-    uint32_t last_chunks = 0;
-    FlowParams last_p;                    // the last update's parameters (fb_flow_history_dev)
+    LastUpdate last;                      // all an update leaves for later calls (the history calls read it)
     DevBuf<uint8_t> d_hist_cnt;           // per-block slot counts of hot history partitions (lazy), bytes
     Staging st;                           // host-mode staging (ensure_staging)
 };
@@ -437,6 +440,27 @@ static int export_to_host(fb_ctx* c, void* out, uint64_t cap, size_t rec, uint64
     return FB_OK;
 }
 
+// fb_flow_history_dev / fb_hist_store_append_dev: the history characters of the last update (c->last,
+// valid: the caller saw live_slots() != 0) into the caller's three outputs, on `s`, which the caller has
+// ordered after the pipelined updates.  `then` runs after the kernel (the store appends what it wrote);
+// the event the next update waits for comes after both.
+template <typename Then>
+static int last_history(fb_ctx* c, uint32_t* d_slot, uint8_t* d_chars, uint32_t* d_n, hipStream_t s, Then then) {
+    const uint64_t cnt_bytes = flow_history_cnt_bytes(c->last.chunks);
+    if (cnt_bytes > c->d_hist_cnt.size()) {
+        HIP_TRY(hipStreamSynchronize(s));
+        if (c->d_hist_cnt.alloc(cnt_bytes) != hipSuccess)
+            return set_err(FB_ERR_NOMEM, "history block counts (%llu bytes)", (unsigned long long)cnt_bytes);
+    }
+    if (c->ev_hist.create() != hipSuccess) return set_err(FB_ERR_HIP, "history event");
+    HIP_TRY(launch_flow_history(c->last.p, c->last.chunks, d_slot, d_chars, d_n, c->tb.hist_slow,
+                                cnt_bytes ? reinterpret_cast<uint32_t*>(c->d_hist_cnt.get()) : nullptr, s));
+    if (const int rc = then()) return rc;
+    HIP_TRY(hipEventRecord(c->ev_hist, s));
+    c->hist_pending = true;
+    return FB_OK;
+}
+
 namespace fbk {
 bool build_blacklist_tables(const fb_cidr* nets, uint32_t n, std::vector<uint32_t>& p4,
                             std::vector<unsigned long long>& m4, std::vector<uint4>& p6,
@@ -464,7 +488,8 @@ static int alloc_upd_scratch(fb_ctx* c, UpdScratch& u, hipStream_t s) {
     return FB_OK;
 }
 
-// Session-table update scratch for batches of up to `recs` records (grown, never shrunk).
+// Session-table update scratch for batches of up to `recs` records (grown, never shrunk).  A growth
+// replaces RecScratch, so a fused entry point calls this for its batch before it picks its FusedParts.
 static int ensure_flow_scratch(fb_ctx* c, uint64_t recs, hipStream_t s) {
     if (!c->tb.slots) return FB_OK;
     recs = std::max<uint64_t>(recs, kFlowChunk);
@@ -475,12 +500,8 @@ static int ensure_flow_scratch(fb_ctx* c, uint64_t recs, hipStream_t s) {
     HIP_TRY(hipStreamSynchronize(s));
     const bool had_set1 = c->us[1].entries != nullptr;
     for (UpdScratch& u : c->us) u = UpdScratch();
-    c->part_recs = nullptr;
-    c->part_buf = nullptr;
-    c->ent_buf = nullptr;
     c->comb_cap = 0;
-    c->last_recs = nullptr;  // its scratch is gone
-    c->last_part = nullptr;
+    c->last.invalidate();  // its scratch is gone
     c->flow_recs = 0;
     const hipError_t e = alloc_group(c->rs, [&](RecScratch& r) {
         return alloc_each(r.hword, recs, r.rec_part, recs, r.rec_ent, recs * kUpdEntU4, r.agg_slot, recs / 2 + 1);
@@ -494,8 +515,6 @@ static int ensure_flow_scratch(fb_ctx* c, uint64_t recs, hipStream_t s) {
     if (!rc && had_set1) rc = alloc_upd_scratch(c, c->us[1], s);
     return rc;
 }
-
-static int empty_update(fb_ctx* c);
 
 static int upload_cfg(fb_ctx* c, hipStream_t s) {
     if (!c->cfg_dirty) return FB_OK;
@@ -709,11 +728,13 @@ int fb_set_frame_times(fb_ctx* c, const uint64_t* d_ts) {
     return FB_OK;
 }
 
-// Every update call of a timed context consumes the frame times set before it (checked before the
-// call's parse, so a refused call changes nothing).
-static int timed_ready(fb_ctx* c) {
+// Every update call of a timed context takes the frame times armed before it: once, after its own argument
+// checks and before any device work, so it consumes them whether it then succeeds or fails.  Untimed: null.
+static int take_frame_times(fb_ctx* c, const unsigned long long** ts) {
     if (c->timed && !c->next_ts)
         return set_err(FB_ERR_INVAL, "a timed context needs fb_set_frame_times before each update call");
+    *ts = c->next_ts;
+    c->next_ts = nullptr;
     return FB_OK;
 }
 
@@ -754,10 +775,10 @@ int fb_set_own_ips(fb_ctx* c, const fb_ip* ips, uint32_t n) {
     return FB_OK;
 }
 
-// Launch of the segmented streaming kernel over `sb` (frames, or the parsed packets `parsed`).
-// `want_parts`: one frame batch whose session table update follows (fb_process_seg_dev) -- the
-// kernel also writes each SESSION record slot's table partition, so the update's histogram pass
-// reads 4 B per record instead of the record.
+// Launch of the segmented streaming kernel over `sb` (frames, or the parsed packets `parsed`), on at most
+// `grid_max` blocks.  `fp` non-empty: one frame batch whose session table update follows (the fused entry
+// points, which order `s` after the updates still reading `fp`) -- the kernel also writes each SESSION record
+// slot's table partition there, so the update's histogram pass reads 4 B per record instead of the record.
 #ifdef FB_SEG_TRACE
 static unsigned long long* g_strace = nullptr;
 // diagnostic builds only: the last k_parse_seg launch's per-block trace (4 x 2048 words), after a sync
@@ -767,12 +788,9 @@ extern "C" __attribute__((visibility("default"))) int fb_seg_trace_last(unsigned
 }
 #endif
 static int launch_seg(fb_ctx* c, const SegBatches& sb, uint32_t n_max, const fb_parsed_pkt* parsed, hipStream_t s,
-                      bool want_parts = false, SegPass pass = SegPass::kSegments, fb_pkt_out* dense_out = nullptr,
-                      fb_dns_out* dense_dns = nullptr) {
+                      FusedParts fp, uint32_t grid_max, SegPass pass = SegPass::kSegments,
+                      fb_pkt_out* dense_out = nullptr, fb_dns_out* dense_dns = nullptr) {
     int rc = reset_launch_scratch(c, s);
-    // a fused parse rewrites d_rec_part, which a pipelined update may still read (the pipelined
-    // call itself writes its own slot's buffer and orders that wait itself)
-    if (!rc && want_parts && !c->part_target) rc = join_updates(c, s);
     if (!rc) rc = upload_cfg(c, s);
     if (!rc) rc = ensure_flow_scratch(c, n_max, s);
     if (rc) return rc;
@@ -784,14 +802,10 @@ static int launch_seg(fb_ctx* c, const SegBatches& sb, uint32_t n_max, const fb_
     p.dense_dns = dense_dns;
     p.parsed = parsed;
     p.n = parsed ? sb.b[0].n : 0u;
-    p.rec_part = (want_parts && sb.count == 1u && c->tb.slots) ? (c->part_target ? c->part_target : c->rs.rec_part.get())
-                                                              : nullptr;
-    p.rec_ent = p.rec_part ? (c->ent_target ? c->ent_target : c->rs.rec_ent.get()) : nullptr;
+    p.rec_part = fp.part;
+    p.rec_ent = fp.ent;
     p.no_records = p.rec_part && !c->emit_records ? 1u : 0u;
     p.part_shift = c->tb.shift;
-    c->part_recs = p.rec_part ? sb.b[0].out : nullptr;
-    c->part_buf = p.rec_part;
-    c->ent_buf = p.rec_ent;
     p.cfg = c->d_cfg;
     p.tick = c->d_tick;
     if (pass != SegPass::kDenseOut) {
@@ -803,7 +817,7 @@ static int launch_seg(fb_ctx* c, const SegBatches& sb, uint32_t n_max, const fb_
     p.error = c->d_error + (launch & 3u);
     p.error_next = c->d_error + ((launch + 1u) & 3u);
     const uint32_t waves = parse_seg_block_threads() / 64u;
-    const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(c->seg_grid, (sb.total_segs + waves - 1) / waves));
+    const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(grid_max, (sb.total_segs + waves - 1) / waves));
 #ifdef FB_SEG_TRACE
     if (!g_strace && hipMalloc(&g_strace, 8u * 4u * 2048u) != hipSuccess) return set_err(FB_ERR_NOMEM, "trace");
     HIP_TRY(hipMemsetAsync(g_strace, 0, 8u * 4u * 2048u, s));
@@ -863,7 +877,7 @@ int fb_parse_classify_seg_batches_dev(fb_ctx* c, const fb_seg_batch* batches, ui
     sb.count = count;
     sb.total_segs = (uint32_t)segs;
     DeviceGuard g(c->device);
-    return launch_seg(c, sb, n_max, nullptr, (hipStream_t)stream);
+    return launch_seg(c, sb, n_max, nullptr, (hipStream_t)stream, {}, c->seg_grid);
 }
 
 #ifdef FB_DN_TRACE
@@ -1147,7 +1161,7 @@ extern "C" __attribute__((visibility("default"))) int fb_seg_queue_trace_last(un
 
 static int parse_seg(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes, const uint32_t* d_offsets, uint32_t n,
                      fb_pkt_out* d_out, uint32_t* d_seg, uint8_t* d_class, fb_batch_stats* d_stats, void* stream,
-                     bool want_parts) {
+                     FusedParts fp, uint32_t grid_max) {
     if (!c || !d_stats) return set_err(FB_ERR_INVAL, "ctx and d_stats are required");
     if (n > FB_MAX_BATCH_PACKETS) return set_err(FB_ERR_INVAL, "n %u > FB_MAX_BATCH_PACKETS", n);
     if (frames_bytes > 0xFFFFFFFFull) return set_err(FB_ERR_INVAL, "frames_bytes must be < 4 GiB");
@@ -1160,13 +1174,14 @@ static int parse_seg(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes, 
         return FB_OK;
     }
     return launch_seg(c, one_batch(d_frames, frames_bytes, d_offsets, n, d_out, d_seg, d_class, d_stats), n, nullptr,
-                      s, want_parts);
+                      s, fp, grid_max);
 }
 
 int fb_parse_classify_seg_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes, const uint32_t* d_offsets,
                               uint32_t n, fb_pkt_out* d_out, uint32_t* d_seg, uint8_t* d_class,
                               fb_batch_stats* d_stats, void* stream) {
-    return parse_seg(c, d_frames, frames_bytes, d_offsets, n, d_out, d_seg, d_class, d_stats, stream, false);
+    if (!c) return set_err(FB_ERR_INVAL, "ctx and d_stats are required");
+    return parse_seg(c, d_frames, frames_bytes, d_offsets, n, d_out, d_seg, d_class, d_stats, stream, {}, c->seg_grid);
 }
 
 int fb_process_parsed_seg_dev(fb_ctx* c, const fb_parsed_pkt* d_in, uint32_t n, fb_pkt_out* d_out, uint32_t* d_seg,
@@ -1180,7 +1195,7 @@ int fb_process_parsed_seg_dev(fb_ctx* c, const fb_parsed_pkt* d_in, uint32_t n, 
         HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(fb_batch_stats), s));
         return FB_OK;
     }
-    return launch_seg(c, one_batch(nullptr, 0, nullptr, n, d_out, d_seg, d_class, d_stats), n, d_in, s);
+    return launch_seg(c, one_batch(nullptr, 0, nullptr, n, d_out, d_seg, d_class, d_stats), n, d_in, s, {}, c->seg_grid);
 }
 
 int fb_seg_compact_dev(fb_ctx* c, const fb_pkt_out* d_seg_out, const uint32_t* d_seg, uint32_t n, fb_pkt_out* d_out,
@@ -1222,8 +1237,6 @@ static int parse_dense_single(fb_ctx* c, const uint8_t* d_frames, uint64_t frame
         c->sc.dense_epoch = 0u;
     }
     c->last_n = n;
-    c->part_recs = nullptr;
-    c->part_buf = nullptr;
     ParseParams p;
     memset(&p, 0, sizeof(p));
     p.cfg = c->d_cfg;
@@ -1273,7 +1286,7 @@ static int parse_dense(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes
     int rc = ensure_compact_scratch(c, n, s);
     if (rc) return rc;
     rc = launch_seg(c, one_batch(d_frames, frames_bytes, d_offsets, n, nullptr, c->sc.cseg, d_class, d_stats), n, d_in,
-                    s, false, SegPass::kCount);
+                    s, {}, c->seg_grid, SegPass::kCount);
     if (rc || (!d_out && !d_dns)) return rc;
     const uint32_t nseg = (n + FB_SEG_FRAMES - 1) / FB_SEG_FRAMES;
     SegScanScratch sc;
@@ -1281,7 +1294,7 @@ static int parse_dense(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes
     if (rc) return rc;
     HIP_TRY(launch_seg_scan(c->sc.cseg, nseg, c->sc.cpre, sc, s));
     return launch_seg(c, one_batch(d_frames, frames_bytes, d_offsets, n, nullptr, nullptr, nullptr, nullptr), n, d_in, s,
-                      false, SegPass::kDenseOut, d_out, d_dns);
+                      {}, c->seg_grid, SegPass::kDenseOut, d_out, d_dns);
 }
 
 int fb_parse_classify_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes,
@@ -1361,47 +1374,10 @@ int fb_parse_classify(fb_ctx* c, const uint8_t* frames, uint64_t frames_bytes, c
     return FB_OK;
 }
 
-int fb_process_parsed(fb_ctx* c, const fb_parsed_pkt* in, uint32_t n, fb_pkt_out* out, uint32_t* n_out,
-                      uint8_t* cls, fb_batch_stats* stats, void* stream) {
-    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
-    if (n > FB_MAX_BATCH_PACKETS) return set_err(FB_ERR_INVAL, "n too large");
-    if (n && !in) return set_err(FB_ERR_INVAL, "NULL input");
-    if (c->tb.slots) {
-        if (int rc = timed_ready(c)) return rc;
-    }
-    DeviceGuard g(c->device);
-    hipStream_t s = (hipStream_t)stream;
-    int rc = ensure_staging(c, n, (uint64_t)n * sizeof(fb_parsed_pkt));
-    if (rc) return rc;
-    const fb_parsed_pkt* d_in = reinterpret_cast<const fb_parsed_pkt*>(c->st.frames.get());
-    if (n) HIP_TRY(hipMemcpyAsync(c->st.frames, in, (uint64_t)n * sizeof(fb_parsed_pkt), hipMemcpyHostToDevice, s));
-    rc = fb_process_parsed_dev(c, d_in, n, c->st.pk.out, cls ? c->st.pk.cls.get() : nullptr, c->st.stats, s);
-    if (rc) return rc;
-    if (n && c->tb.slots) {
-        rc = fb_flow_update_dev(c, c->st.pk.out, c->st.stats, s);
-        if (rc) return rc;
-    } else if (c->tb.slots) {
-        empty_update(c);
-    }
-    fb_batch_stats st;
-    HIP_TRY(hipMemcpyAsync(&st, c->st.stats, sizeof(st), hipMemcpyDeviceToHost, s));
-    rc = check_error_word(c, s);  // synchronises the stream
-    if (rc) return rc;
-    if (out && st.n_session)
-        HIP_TRY(hipMemcpyAsync(out, c->st.pk.out, st.n_session * sizeof(fb_pkt_out), hipMemcpyDeviceToHost, s));
-    if (cls && n) HIP_TRY(hipMemcpyAsync(cls, c->st.pk.cls, n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (n_out) *n_out = (uint32_t)st.n_session;
-    if (stats) *stats = st;
-    return FB_OK;
-}
-
 // An update call without records still counts as one (the high word of flow positions).
 static int empty_update(fb_ctx* c) {
     ++c->flow_batch;
-    c->next_ts = nullptr;
-    c->last_recs = nullptr;
-    c->last_part = nullptr;
+    c->last.invalidate();
     return FB_OK;
 }
 
@@ -1435,8 +1411,7 @@ static int grow_table(fb_ctx* c, hipStream_t s, uint32_t k) {
     c->flow_recs = 0;
     rc = ensure_flow_scratch(c, recs, s);
     if (!rc && had_set1) rc = alloc_upd_scratch(c, c->us[1], s);
-    c->last_recs = nullptr;  // the last update's slots moved: its history is no longer available
-    c->last_part = nullptr;
+    c->last.invalidate();  // the last update's slots moved: its history is no longer available
     return rc;
 }
 
@@ -1453,7 +1428,7 @@ static int grow_table(fb_ctx* c, hipStream_t s, uint32_t k) {
 static constexpr uint64_t kGrowPart = kFlowSlots * 7u / 8u;
 static constexpr double kMailboxWaitS = 120.0;
 static int maybe_grow(fb_ctx* c, hipStream_t s) {
-    if (!c->tb.slots || !c->grow || c->part_recs) return FB_OK;  // (a fused parse already bucketed for this geometry)
+    if (!c->tb.slots || !c->grow) return FB_OK;
     const volatile FlowMailbox* m = c->mbox;
     const uint64_t issued = c->upd_seq - c->clear_seq;              // updates since create / clear
     const uint64_t need = c->clear_seq + (issued >= 2u ? issued - 1u : issued);
@@ -1490,15 +1465,19 @@ static int maybe_grow(fb_ctx* c, hipStream_t s) {
 // One table update.  `split` (the pipelined call): the bucketing kernels (K1, K1c) run on `s_bucket`
 // -- the caller's stream (possibly the null stream), right after the parse that wrote the batch's
 // partitions, into update scratch set `set` -- and the rest (K1t, K2, the stats fold) on `s` after
-// an event; otherwise everything runs on `s` with set 0.
+// an event; otherwise everything runs on `s` with set 0.  `ts`: the frame times the entry point took.
+// `fp`: what this batch's fused parse wrote -- the entry point grew the table and sized the scratch
+// (for seg_slots(n), which rounds to the same chunks as the parse's n) before it, so neither changes here.
 static int flow_update(fb_ctx* c, const fb_pkt_out* d_recs, const uint32_t* d_seg, uint32_t n_slots,
-                       fb_batch_stats* d_stats, hipStream_t s, bool split = false, hipStream_t s_bucket = nullptr,
-                       uint32_t set = 0) {
+                       fb_batch_stats* d_stats, hipStream_t s, const unsigned long long* ts, FusedParts fp = {},
+                       bool split = false, hipStream_t s_bucket = nullptr, uint32_t set = 0) {
     if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     DeviceGuard g(c->device);
     if (!split) s_bucket = s;
+    static_assert(kFlowChunk % FB_SEG_FRAMES == 0, "a chunk is whole segments");
+    if (fp.part && n_slots > c->flow_recs) return set_err(FB_ERR_INTERNAL, "fused update without scratch for its batch");
     int rc = split ? FB_OK : join_updates(c, s);
-    if (!rc && !split) rc = maybe_grow(c, s);  // (skipped after a fused parse: it bucketed for this geometry)
+    if (!rc && !split && !fp.part) rc = maybe_grow(c, s);
     if (!rc) rc = ensure_flow_scratch(c, n_slots, s_bucket);
     if (!rc && set == 1u && !c->us[1].entries) rc = alloc_upd_scratch(c, c->us[1], s_bucket);
     if (rc) return rc;
@@ -1542,12 +1521,11 @@ static int flow_update(fb_ctx* c, const fb_pkt_out* d_recs, const uint32_t* d_se
     p.order = FB_K2_ORDER ? u.order.get() : nullptr;
     p.agg_slot = c->rs.agg_slot;
     p.hot_cap = (uint32_t)(c->flow_recs / 16 + 16);
-    p.rec_part = (d_seg && c->part_recs == d_recs) ? c->part_buf : nullptr;  // written by this batch's parse
-    p.ent = p.rec_part ? c->ent_buf : nullptr;                                  // (with its update entries)
+    p.rec_part = fp.part;
+    p.ent = fp.ent;
     p.char_call = c->tb.char_call;
-    c->part_recs = nullptr;
+    const uint32_t slots = std::min(p.max_recs, n_slots);
     if (c->timed) {  // the capture-time pass's scratch (K2 writes its sort input into it)
-        const uint32_t slots = p.max_recs < n_slots ? p.max_recs : n_slots;
         uint32_t bits = 0;
         while ((1ull << bits) < c->tb.cap) ++bits;
         const uint64_t need = time_scratch_bytes(slots, bits);
@@ -1568,48 +1546,44 @@ static int flow_update(fb_ctx* c, const fb_pkt_out* d_recs, const uint32_t* d_se
     HIP_TRY(launch_flow_finish(d_stats, c->tb.partials, c->tb.parts, c->d_error + (c->epoch & 3u), c->mbox.dev(),
                                ++c->upd_seq, s));
     if (c->timed) {  // the capture-time pass over the placed records (fb_time.hip)
-        const uint32_t slots = p.max_recs < n_slots ? p.max_recs : n_slots;
-        HIP_TRY(launch_time_update(p, slots, c->tb.cap, c->plane<FlowTime>(kPlaneTime), c->next_ts, c->tscratch.get(), s));
+        HIP_TRY(launch_time_update(p, slots, c->tb.cap, c->plane<FlowTime>(kPlaneTime), ts, c->tscratch.get(), s));
         rc = c->tscratch.release(s);
         if (rc) return rc;
-        c->next_ts = nullptr;
     }
     ++c->flow_batch;
     if (c->hs) ++c->hs_updates;
-    c->last_set = set;
-    c->last_recs = d_recs;
-    c->last_part = p.rec_part;
-    c->last_seg = d_seg;
-    c->last_stats = d_stats;
-    c->last_slots = p.max_recs < n_slots ? p.max_recs : n_slots;
-    c->last_chunks = chunks;
-    c->last_p = p;
+    c->last.p = p;
+    c->last.slots = slots;
+    c->last.chunks = chunks;
+    c->last.valid = true;
     return FB_OK;
 }
 
 int fb_flow_update_dev(fb_ctx* c, const fb_pkt_out* d_recs, fb_batch_stats* d_stats, void* stream) {
     if (!c || !d_recs || !d_stats) return set_err(FB_ERR_INVAL, "ctx, d_recs and d_stats are required");
-    if (int rc = timed_ready(c)) return rc;
-    return flow_update(c, d_recs, nullptr, c->last_n, d_stats, (hipStream_t)stream);
+    const unsigned long long* ts = nullptr;
+    if (int rc = take_frame_times(c, &ts)) return rc;
+    return flow_update(c, d_recs, nullptr, c->last_n, d_stats, (hipStream_t)stream, ts);
 }
 
 int fb_flow_update_records_dev(fb_ctx* c, const fb_pkt_out* d_recs, uint32_t max_n, fb_batch_stats* d_stats,
                                void* stream) {
     if (!c || !d_stats || (max_n && !d_recs)) return set_err(FB_ERR_INVAL, "ctx, d_recs and d_stats are required");
     if (max_n > FB_MAX_BATCH_PACKETS) return set_err(FB_ERR_INVAL, "max_n %u > FB_MAX_BATCH_PACKETS", max_n);
-    if (int rc = timed_ready(c)) return rc;
+    const unsigned long long* ts = nullptr;
+    if (int rc = take_frame_times(c, &ts)) return rc;
     if (max_n == 0) return empty_update(c);
-    return flow_update(c, d_recs, nullptr, max_n, d_stats, (hipStream_t)stream);
+    return flow_update(c, d_recs, nullptr, max_n, d_stats, (hipStream_t)stream, ts);
 }
 
 int fb_flow_update_seg_dev(fb_ctx* c, const fb_pkt_out* d_out, const uint32_t* d_seg, uint32_t n,
                            fb_batch_stats* d_stats, void* stream) {
     if (!c || !d_out || !d_seg || !d_stats) return set_err(FB_ERR_INVAL, "ctx, d_out, d_seg and d_stats are required");
     if (n > FB_MAX_BATCH_PACKETS) return set_err(FB_ERR_INVAL, "n %u > FB_MAX_BATCH_PACKETS", n);
-    if (int rc = timed_ready(c)) return rc;
+    const unsigned long long* ts = nullptr;
+    if (int rc = take_frame_times(c, &ts)) return rc;
     if (n == 0) return empty_update(c);
-    const uint32_t slots = (n + FB_SEG_FRAMES - 1) / FB_SEG_FRAMES * FB_SEG_FRAMES;
-    return flow_update(c, d_out, d_seg, slots, d_stats, (hipStream_t)stream);
+    return flow_update(c, d_out, d_seg, seg_slots(n), d_stats, (hipStream_t)stream, ts);
 }
 
 int fb_process_seg_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes, const uint32_t* d_offsets,
@@ -1617,17 +1591,21 @@ int fb_process_seg_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes
                        void* stream) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
     if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
-    int rc = timed_ready(c);
+    if (n > FB_MAX_BATCH_PACKETS) return set_err(FB_ERR_INVAL, "n %u > FB_MAX_BATCH_PACKETS", n);
+    const unsigned long long* ts = nullptr;
+    int rc = take_frame_times(c, &ts);
     if (rc) return rc;
-    {
-        DeviceGuard g(c->device);
-        rc = maybe_grow(c, (hipStream_t)stream);  // before the parse writes partitions of this geometry
-    }
-    if (!rc) rc = parse_seg(c, d_frames, frames_bytes, d_offsets, n, d_out, d_seg, d_class, d_stats, stream, true);
-    if (rc == FB_OK && c->stage_event) rc = hipEventRecord(c->stage_event, (hipStream_t)stream) == hipSuccess
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    rc = maybe_grow(c, s);  // before the parse writes partitions of this geometry
+    if (!rc) rc = ensure_flow_scratch(c, seg_slots(n), s);  // ... and before the buffers it writes are picked
+    // the parse rewrites them, and a pipelined update may still read them (an empty batch has no parse)
+    if (!rc && n) rc = join_updates(c, s);
+    const FusedParts fp{c->rs.rec_part.get(), c->rs.rec_ent.get()};
+    if (!rc) rc = parse_seg(c, d_frames, frames_bytes, d_offsets, n, d_out, d_seg, d_class, d_stats, stream, fp, c->seg_grid);
+    if (rc == FB_OK && c->stage_event) rc = hipEventRecord(c->stage_event, s) == hipSuccess
                                                 ? FB_OK : set_err(FB_ERR_HIP, "stage event record failed");
-    if (rc == FB_OK) rc = n == 0 ? empty_update(c) : fb_flow_update_seg_dev(c, d_out, d_seg, n, d_stats, stream);
-    c->part_recs = nullptr;  // the partitions serve this update only
+    if (rc == FB_OK) rc = n == 0 ? empty_update(c) : flow_update(c, d_out, d_seg, seg_slots(n), d_stats, s, ts, fp);
     return rc;
 }
 
@@ -1641,7 +1619,8 @@ int fb_process_seg_async_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
     if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     if (n > FB_MAX_BATCH_PACKETS) return set_err(FB_ERR_INVAL, "n %u > FB_MAX_BATCH_PACKETS", n);
-    if (int rc = timed_ready(c)) return rc;
+    const unsigned long long* ts = nullptr;
+    if (int rc = take_frame_times(c, &ts)) return rc;
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     if (!c->upd && (c->upd.create() != hipSuccess || c->ev_parsed.create() != hipSuccess ||
@@ -1649,7 +1628,7 @@ int fb_process_seg_async_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames
         return set_err(FB_ERR_HIP, "update stream / events");
     const uint32_t slot = (uint32_t)(c->async_k & 1u);
     int rc = maybe_grow(c, s);  // before this batch's parse writes partitions (drains the pipeline if it grows)
-    if (!rc) rc = ensure_flow_scratch(c, (n + FB_SEG_FRAMES - 1) / FB_SEG_FRAMES * FB_SEG_FRAMES, s);
+    if (!rc) rc = ensure_flow_scratch(c, seg_slots(n), s);
     if (rc) return rc;
     if (!c->rs.rec_part2 && c->rs.rec_part2.alloc(c->flow_recs) != hipSuccess)
         return set_err(FB_ERR_NOMEM, "second partition buffer");
@@ -1662,23 +1641,15 @@ int fb_process_seg_async_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames
     // update too (no overlap: rotate two buffer sets to get it)
     if (c->async_k >= 1 && (d_out == c->async_prev[0] || d_seg == c->async_prev[1] || d_stats == c->async_prev[2]))
         HIP_TRY(hipStreamWaitEvent(s, c->ev_upd[slot ^ 1u], 0));
-    c->part_target = slot ? c->rs.rec_part2.get() : c->rs.rec_part.get();
-    c->ent_target = slot ? c->rs.rec_ent2.get() : c->rs.rec_ent.get();
-    const uint32_t grid_full = c->seg_grid;
-    c->seg_grid = c->seg_grid_async;
-    rc = parse_seg(c, d_frames, frames_bytes, d_offsets, n, d_out, d_seg, d_class, d_stats, stream, true);
-    c->seg_grid = grid_full;
-    c->part_target = nullptr;
-    c->ent_target = nullptr;
+    const FusedParts fp = slot ? FusedParts{c->rs.rec_part2.get(), c->rs.rec_ent2.get()}
+                               : FusedParts{c->rs.rec_part.get(), c->rs.rec_ent.get()};
+    rc = parse_seg(c, d_frames, frames_bytes, d_offsets, n, d_out, d_seg, d_class, d_stats, stream, fp, c->seg_grid_async);
     if (rc == FB_OK && c->stage_event) rc = hipEventRecord(c->stage_event, s) == hipSuccess
                                                 ? FB_OK : set_err(FB_ERR_HIP, "stage event record failed");
     if (rc) return rc;
     // the bucketing kernels follow the parse on `stream` (into scratch set k & 1, which update k-2
     // -- waited for above -- was the last to read); the update stream takes over after them
-    rc = n == 0 ? empty_update(c)
-                : flow_update(c, d_out, d_seg, (n + FB_SEG_FRAMES - 1) / FB_SEG_FRAMES * FB_SEG_FRAMES, d_stats,
-                              c->upd, true, s, slot);
-    c->part_recs = nullptr;
+    rc = n == 0 ? empty_update(c) : flow_update(c, d_out, d_seg, seg_slots(n), d_stats, c->upd, ts, fp, true, s, slot);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(c->ev_upd[slot], c->upd));
     c->upd_word[slot] = c->epoch & 3u;  // the word flow_update handed this update
@@ -1701,12 +1672,48 @@ int fb_process_dev(fb_ctx* c, const uint8_t* d_frames, uint64_t frames_bytes, co
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
     if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
     if (!d_out) return set_err(FB_ERR_INVAL, "d_out is required");
-    if (int rc = timed_ready(c)) return rc;
+    const unsigned long long* ts = nullptr;
+    if (int rc = take_frame_times(c, &ts)) return rc;
     int rc = fb_parse_classify_dev(c, d_frames, frames_bytes, d_offsets, n, d_out, d_dns, d_class, d_stats, stream);
     if (rc) return rc;
     if (c->stage_event) HIP_TRY(hipEventRecord(c->stage_event, (hipStream_t)stream));
     if (n == 0) return empty_update(c);
-    return fb_flow_update_dev(c, d_out, d_stats, stream);
+    return flow_update(c, d_out, nullptr, c->last_n, d_stats, (hipStream_t)stream, ts);
+}
+
+int fb_process_parsed(fb_ctx* c, const fb_parsed_pkt* in, uint32_t n, fb_pkt_out* out, uint32_t* n_out,
+                      uint8_t* cls, fb_batch_stats* stats, void* stream) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    if (n > FB_MAX_BATCH_PACKETS) return set_err(FB_ERR_INVAL, "n too large");
+    if (n && !in) return set_err(FB_ERR_INVAL, "NULL input");
+    const unsigned long long* ts = nullptr;
+    int rc = c->tb.slots ? take_frame_times(c, &ts) : FB_OK;
+    if (rc) return rc;
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    rc = ensure_staging(c, n, (uint64_t)n * sizeof(fb_parsed_pkt));
+    if (rc) return rc;
+    const fb_parsed_pkt* d_in = reinterpret_cast<const fb_parsed_pkt*>(c->st.frames.get());
+    if (n) HIP_TRY(hipMemcpyAsync(c->st.frames, in, (uint64_t)n * sizeof(fb_parsed_pkt), hipMemcpyHostToDevice, s));
+    rc = fb_process_parsed_dev(c, d_in, n, c->st.pk.out, cls ? c->st.pk.cls.get() : nullptr, c->st.stats, s);
+    if (rc) return rc;
+    if (n && c->tb.slots) {
+        rc = flow_update(c, c->st.pk.out, nullptr, c->last_n, c->st.stats, s, ts);
+        if (rc) return rc;
+    } else if (c->tb.slots) {
+        empty_update(c);
+    }
+    fb_batch_stats st;
+    HIP_TRY(hipMemcpyAsync(&st, c->st.stats, sizeof(st), hipMemcpyDeviceToHost, s));
+    rc = check_error_word(c, s);  // synchronises the stream
+    if (rc) return rc;
+    if (out && st.n_session)
+        HIP_TRY(hipMemcpyAsync(out, c->st.pk.out, st.n_session * sizeof(fb_pkt_out), hipMemcpyDeviceToHost, s));
+    if (cls && n) HIP_TRY(hipMemcpyAsync(cls, c->st.pk.cls, n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (n_out) *n_out = (uint32_t)st.n_session;
+    if (stats) *stats = st;
+    return FB_OK;
 }
 
 int fb_flow_history_dev(fb_ctx* c, uint8_t* d_hist, uint32_t* d_hist_slot, uint32_t* d_n_hist, void* stream) {
@@ -1716,24 +1723,12 @@ int fb_flow_history_dev(fb_ctx* c, uint8_t* d_hist, uint32_t* d_hist_slot, uint3
     hipStream_t s = (hipStream_t)stream;
     int jr = join_updates(c, s);
     if (jr) return jr;
-    const uint32_t n = c->last_recs ? c->last_slots : 0u;
-    if (n == 0) {
+    if (c->last.live_slots() == 0) {
         HIP_TRY(hipMemsetAsync(d_n_hist, 0, 4, s));
         return FB_OK;
     }
     if (!d_hist || !d_hist_slot) return set_err(FB_ERR_INVAL, "d_hist and d_hist_slot are required");
-    const uint64_t cnt_bytes = flow_history_cnt_bytes(c->last_chunks);
-    if (cnt_bytes > c->d_hist_cnt.size()) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (c->d_hist_cnt.alloc(cnt_bytes) != hipSuccess)
-            return set_err(FB_ERR_NOMEM, "history block counts (%llu bytes)", (unsigned long long)cnt_bytes);
-    }
-    if (c->ev_hist.create() != hipSuccess) return set_err(FB_ERR_HIP, "history event");
-    HIP_TRY(launch_flow_history(c->last_p, c->last_chunks, d_hist_slot, d_hist, d_n_hist, c->tb.hist_slow,
-                                cnt_bytes ? reinterpret_cast<uint32_t*>(c->d_hist_cnt.get()) : nullptr, s));
-    HIP_TRY(hipEventRecord(c->ev_hist, s));
-    c->hist_pending = true;
-    return FB_OK;
+    return last_history(c, d_hist_slot, d_hist, d_n_hist, s, [] { return FB_OK; });
 }
 
 // ---- enrichment ----------------------------------------------------------------------------
@@ -1923,8 +1918,7 @@ int fb_flow_age(fb_ctx* c, uint64_t now_ns, const fb_age_params* params, uint32_
     if (h[6]) {  // flows were removed: survivors of their partitions may have moved
         c->d_remap.swap(c->d_age_remap);  // (the old map is reallocated if its size is not the table's)
         ++c->generation;
-        c->last_recs = nullptr;  // the last update's slots moved: its history is no longer available
-        c->last_part = nullptr;
+        c->last.invalidate();  // the last update's slots moved: its history is no longer available
         c->mbox->flows = h[7];
         c->mbox->max_part = h[8];
         if (c->hs && c->tb.plane[kPlaneHist])  // the removed flows' blocks, read off the plane before it moves
@@ -2513,31 +2507,24 @@ int fb_hist_store_append_dev(fb_ctx* c, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     rc = join_updates(c, s);
     if (rc) return rc;
-    const uint32_t n = c->last_recs ? c->last_slots : 0u;
+    const uint32_t n = c->last.live_slots();
     if (n == 0) return FB_OK;  // the update's slots have moved since (a purge): it stays a missed update
-    // everything that can fail, wait or allocate comes before the first kernel
+    // everything that can fail, wait or allocate comes before the first kernel (last_history's: before its own)
     rc = histstore_admit(c->hs, n, s);
     if (rc) return rc;
-    const uint64_t cnt_bytes = flow_history_cnt_bytes(c->last_chunks);
-    if (cnt_bytes > c->d_hist_cnt.size() || c->flow_recs > histstore_scratch_slots(c->hs)) {
-        rc = drain_updates(c);
+    if (flow_history_cnt_bytes(c->last.chunks) > c->d_hist_cnt.size() || c->flow_recs > histstore_scratch_slots(c->hs)) {
+        rc = drain_updates(c);  // before either is reallocated (last_history grows the block counts)
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(s));
-        if (cnt_bytes > c->d_hist_cnt.size() && c->d_hist_cnt.alloc(cnt_bytes) != hipSuccess)
-            return set_err(FB_ERR_NOMEM, "history block counts (%llu bytes)", (unsigned long long)cnt_bytes);
         rc = histstore_scratch(c->hs, c->flow_recs);
         if (rc) return rc;
     }
-    if (c->ev_hist.create() != hipSuccess) return set_err(FB_ERR_HIP, "history event");
     rc = plane_ensure(c, kPlaneHist, s);  // (dropped by a purge whose move failed: every history starts again)
     if (rc) return rc;
-    HIP_TRY(launch_flow_history(c->last_p, c->last_chunks, histstore_run_slots(c->hs), histstore_run_chars(c->hs),
-                                histstore_run_count(c->hs), c->tb.hist_slow,
-                                cnt_bytes ? reinterpret_cast<uint32_t*>(c->d_hist_cnt.get()) : nullptr, s));
-    rc = histstore_append(c->hs, c->plane<uint4>(kPlaneHist), c->tb.cap, n, n, s);
+    rc = last_history(c, histstore_run_slots(c->hs), histstore_run_chars(c->hs), histstore_run_count(c->hs), s, [&] {
+        return histstore_append(c->hs, c->plane<uint4>(kPlaneHist), c->tb.cap, n, n, s);
+    });
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(c->ev_hist, s));
-    c->hist_pending = true;
     c->hs_seen = c->hs_updates;
     ++c->hs_applied;
     return FB_OK;
@@ -2730,8 +2717,7 @@ int fb_flow_clear(fb_ctx* c, void* stream) {
     if (rc) return rc;
     c->flow_batch = 0;
     c->clear_seq = c->upd_seq;
-    c->last_recs = nullptr;
-    c->last_part = nullptr;
+    c->last.invalidate();
     return FB_OK;
 }
 

@@ -328,8 +328,11 @@ int fb_set_stage_event(fb_ctx* ctx, void* event);
  * d_ts[i] = frame i's capture time in ns since the Unix epoch (pcap header time, as the reference's
  * Utc::now() would read it), indexed by the records' pkt_index -- a DEVICE pointer that must stay
  * valid until that call's work completes on its stream (for fb_process_seg_async_dev: until
- * fb_flow_join or a later call's wait on it).  Consumed by that call; an update call on a timed
- * context without it fails with FB_ERR_INVAL before doing anything. */
+ * fb_flow_join or a later call's wait on it).  An update call that gets past the checks of its own
+ * arguments consumes the pointer, whether it then succeeds or fails (a later refusal by its parse, an
+ * allocation, a launch): the call after it needs fb_set_frame_times again.  A call refused for its own
+ * arguments leaves the pointer armed, and an update call on a timed context with nothing armed fails
+ * with FB_ERR_INVAL before doing anything.  Untimed contexts: fb_set_frame_times itself is refused. */
 int fb_set_frame_times(fb_ctx* ctx, const uint64_t* d_ts);
 /* Test / diagnostic knobs of one context (never needed in production; each takes effect for the
  * next call): FB_DEBUG_DENSE_STEAL_POLLS -- the polls a dense look-back waits for a predecessor's

@@ -343,6 +343,37 @@ def test_clear_enable_rules_repeated_and_missing_appends():
 
 
 # ---- 7. Zeek from the store --------------------------------------------------------------------------------
+@pytest.mark.parametrize("step", ["empty", "clear", "purge"])
+def test_no_history_of_an_update_whose_record_is_gone(step):
+    """The record of the last update dies with an empty update call, a clear and a purge that removes flows.
+    A 200-frame update (4 segments, the last one partial) whose append was left out, then the step:
+    fb_flow_history_dev reports 0 characters, and the late fb_hist_store_append_dev succeeds without applying
+    anything -- the update stays a missed one."""
+    lib = N.gpu_lib()
+    cap = make_cap(timed=True, flow_capacity=1 << 10)
+    try:
+        cap.track_history = False  # (no append after the batches below)
+        frames = interleave([frames_of(k, 0, 4) for k in range(50)])
+        feed(cap, None, frames, seg=True, ts=T0 + np.arange(len(frames), dtype=np.uint64) * 1000)
+        assert sum(len(h) for h in cap.flow_history(256).values()) == len(frames) == 200  # the record is live
+        if step == "empty":
+            feed(cap, None, [], seg=True, ts=np.zeros(0, dtype=np.uint64))
+        elif step == "clear":
+            cap.clear_all_sessions()
+        else:
+            assert cap.update_sessions_status(T0 + 2 * DAY)["purged"] == 50
+        d_n = N.DeviceBuffer(4)
+        d_n.memset(0xFF)
+        N.check(lib.fb_flow_history_dev(cap.ctx, None, None, d_n.ptr, None))
+        assert int(d_n.download(np.zeros(1, dtype=np.uint32))[0]) == 0
+        info = cap.history_store_info()
+        N.check(lib.fb_hist_store_append_dev(cap.ctx, None))
+        assert cap.history_store_info() == info
+        assert (info["appends"], info["missed_updates"], info["chars"]) == (0, 1, 0)
+    finally:
+        cap.close()
+
+
 def _zeek_batches():
     lens = [2 + k % 3 for k in range(3000)]
     for k, n in ((7, 63), (8, 64), (9, 65), (10, 119), (11, 120), (12, 121), (13, 700)):

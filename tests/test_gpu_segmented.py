@@ -258,6 +258,77 @@ def test_seg_batches_one_launch(gpu_capture):
         _check(gpu_capture, frames, offs, res=res)
 
 
+@pytest.mark.parametrize("timed", [False, True], ids=["untimed", "timed"])
+def test_fused_handoff_does_not_outlive_its_call(timed):
+    """The per-record partitions and update entries a fused parse writes serve the update of the same call
+    only.  One context, 200-frame batches (4 segments, the last one partial): a fused call into buffers X,
+    then a batch of other flows parsed unfused into the same X and applied with fb_flow_update_seg_dev (same
+    record pointer, no partitions of its own), two pipelined calls with rotating buffers (partition buffers
+    0 and 1), and a fused call again.  After every step the table equals the oracle's (on the timed context
+    every flow's time record too, with per-batch timestamps), and fb_flow_history_dev returns exactly the
+    characters the oracle's history gained in that step."""
+    from flodbadd_amd.capture import FlodbaddGpuCapture
+    from test_gpu_histstore import frames_of, interleave
+    from test_gpu_parity import rows_sorted
+    from test_gpu_timed import BASE_NS, _check as check_timed
+    lib = N.gpu_lib()
+    cap = FlodbaddGpuCapture(0, session_filter=SessionFilter.All, flow_capacity=1 << 10, timed=timed)
+    ref, cfg = coracle.Flows(), coracle.make_cfg(2)
+    n, nseg = 200, 4
+    sets = [(N.DeviceBuffer(nseg * N.SEG_BYTES), N.DeviceBuffer(nseg * 4), N.DeviceBuffer(N.STATS_DTYPE.itemsize))
+            for _ in range(2)]
+    plan = [  # (how, buffer set, (flow, its first packet) x 50: 4 packets each)
+        ("fused", 0, [(k, 0) for k in range(50)]),
+        ("unfused", 0, [(k, 0) for k in range(100, 150)]),
+        ("async", 0, [(k, 4) for k in range(25)] + [(k, 0) for k in range(200, 225)]),
+        ("async+join", 1, [(k, 4) for k in range(100, 150)]),
+        ("fused", 0, [(k, 4) for k in range(25, 50)] + [(k, 0) for k in range(300, 325)]),
+    ]
+    keep, hist = [], {}
+    try:
+        for step, (how, s, flows) in enumerate(plan):
+            frames, offs = fg.pack(interleave([frames_of(k, first, 4) for k, first in flows]))
+            assert len(offs) - 1 == n
+            ts = (BASE_NS + step * 40 * 10 ** 9 + np.arange(n) * 10 ** 6).astype(np.uint64) if timed else None
+            ref.update(coracle.parse_classify(cfg, frames, offs)[0], ts=ts)
+            d_fr, d_of = N.DeviceBuffer(frames.nbytes).upload(frames), N.DeviceBuffer(offs.nbytes).upload(offs)
+            keep += [d_fr, d_of]
+            d_out, d_seg, d_st = sets[s]
+            if timed:
+                keep.append(N.DeviceBuffer(ts.nbytes).upload(ts))
+                N.check(lib.fb_set_frame_times(cap.ctx, keep[-1].ptr))
+            args = (cap.ctx, d_fr.ptr, frames.nbytes, d_of.ptr, n, d_out.ptr, d_seg.ptr, None, d_st.ptr, None)
+            if how == "fused":
+                N.check(lib.fb_process_seg_dev(*args))
+            elif how == "unfused":
+                N.check(lib.fb_parse_classify_seg_dev(*args))
+                N.check(lib.fb_flow_update_seg_dev(cap.ctx, d_out.ptr, d_seg.ptr, n, d_st.ptr, None))
+            else:
+                N.check(lib.fb_process_seg_async_dev(*args))
+                if how == "async+join":
+                    N.check(lib.fb_flow_join(cap.ctx, None))
+            gf = cap.export_flows()  # (joins the update stream itself)
+            if timed:
+                assert check_timed(cap, ref, "step %d" % step) == len(gf)
+            else:
+                assert rows_sorted(gf) == rows_sorted(ref.export_sorted()), (step, how)
+            assert int(d_st.download(np.zeros(1, dtype=N.STATS_DTYPE))[0]["error"]) == 0
+            # the characters of this step: what the oracle's strings gained
+            after = {r.tobytes()[:40]: ref.history(r)[0] for r in ref.export_sorted()}
+            assert all(after[k].startswith(h) for k, h in hist.items())
+            want = {k: h[len(hist.get(k, "")):] for k, h in after.items() if len(h) > len(hist.get(k, ""))}
+            assert len(want) == 50 and sum(len(h) for h in want.values()) == n
+            by_slot = {int(r["slot"]): r.tobytes()[:40] for r in gf}
+            got = {by_slot[sl]: h for sl, h in cap.flow_history(nseg * 64).items()}
+            assert got == want, (step, how)
+            hist = after
+        assert cap.flow_count() == 150
+    finally:
+        N.check(lib.fb_flow_join(cap.ctx, None))
+        N.check(lib.fb_stream_sync(None))
+        cap.close()
+
+
 def test_seg_batches_rejects_bad_counts(gpu_capture):
     lib = N.gpu_lib()
     desc = np.zeros(N.FB_MAX_SEG_BATCHES + 1, dtype=N.SEG_BATCH_DTYPE)

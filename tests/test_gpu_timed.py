@@ -220,3 +220,32 @@ def test_timed_api_refusals():
     finally:
         plain.close()
         timed.close()
+
+
+def test_timed_failed_call_consumes_the_frame_times():
+    """An update call that gets past its own argument checks consumes the armed frame times even when it
+    then fails: here the parse refuses d_frames = NULL (before any device work) after fb_process_dev took
+    them, so the next call, valid but with nothing armed, is refused and leaves the table empty.  The first
+    timestamp buffer stays alive for the whole test: nothing here ever reads freed memory."""
+    lib = N.gpu_lib()
+    cap = FlodbaddGpuCapture(0, session_filter=SessionFilter.All, flow_capacity=1 << 10, timed=True)
+    try:
+        n = 200  # 4 segments, the last one partial
+        fr, of = synth.generate(4, n)
+        ts = frame_times(n, seed=3)
+        d_fr, d_of = N.DeviceBuffer(fr.nbytes).upload(fr), N.DeviceBuffer(of.nbytes).upload(of)
+        d_out, d_st = N.DeviceBuffer(n * N.PKT_OUT_DTYPE.itemsize), N.DeviceBuffer(N.STATS_DTYPE.itemsize)
+        d_ts = N.DeviceBuffer(ts.nbytes).upload(ts)
+        call = lambda frames: lib.fb_process_dev(cap.ctx, frames, fr.nbytes, d_of.ptr, n, d_out.ptr, None, None,  # noqa: E731
+                                                 d_st.ptr, None)
+        N.check(lib.fb_set_frame_times(cap.ctx, d_ts.ptr))
+        assert call(None) == N.FB_ERR_INVAL      # refused by the parse, after the times were taken
+        assert call(d_fr.ptr) == N.FB_ERR_INVAL  # a valid call, but the times are gone
+        assert cap.flow_count() == 0
+        N.check(lib.fb_set_frame_times(cap.ctx, d_ts.ptr))
+        N.check(call(d_fr.ptr))
+        ref = coracle.Flows()
+        ref.update(coracle.parse_classify(coracle.make_cfg(2), fr, of)[0], ts=ts)
+        assert _check(cap, ref) > 0
+    finally:
+        cap.close()
