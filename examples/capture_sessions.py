@@ -18,6 +18,8 @@ table upsert); `--capture-only` skips the GPU (e.g. to write the batch with `--s
 the capture timed (each frame's receive time is its capture timestamp) and prints the sessions as
 Zeek conn.log lines, the text of the reference's `format_sessions_zeek`, formatted on the GPU; with
 `--history-on-device` the history strings of those lines never leave the GPU (the device store).
+`--learn-whitelist` prints the WhitelistsJSON text of the reference's `create_custom_whitelists`, the distinct
+endpoints and their representative sessions found by one pass on the GPU.
 """
 import argparse
 import os
@@ -108,6 +110,9 @@ def main():
                     help="print the sessions as Zeek conn.log lines (format_sessions_zeek), formatted on the GPU")
     ap.add_argument("--history-on-device", action="store_true",
                     help="with --zeek: keep the history strings in the device store (fb_hist_store_*), not on the host")
+    ap.add_argument("--learn-whitelist", action="store_true",
+                    help="print the custom whitelist learned from the sessions (create_custom_whitelists), its distinct "
+                         "endpoints found on the GPU")
     a = ap.parse_args()
     times = [] if a.zeek else None
     try:
@@ -140,6 +145,8 @@ def main():
             print(ZEEK_HEADER)
             for line in cap.get_sessions_zeek().lines():
                 print(line)
+        if a.learn_whitelist:
+            print(cap.create_custom_whitelists(on_device=True))
         cap.clear_all_sessions()
     finally:
         cap.close()

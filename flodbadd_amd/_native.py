@@ -112,6 +112,15 @@ VIEW_QUERY_DTYPE = np.dtype([("since_ns", "<u8"), ("set", "<u4"), ("filter", "<u
 assert FLOW_VIEW_DTYPE.itemsize == 256 and VIEW_QUERY_DTYPE.itemsize == 24
 FB_VIEW_ALL, FB_VIEW_CURRENT, FB_VIEW_BLACKLISTED, FB_VIEW_WL_EXCEPTIONS, FB_VIEW_ANOMALOUS = 0, 1, 2, 3, 4
 FB_VIEW_MODIFIED_SINCE = 1
+# fb_learned_endpoint / fb_learn_stats (fb_flow_learn_endpoints_dev: the distinct endpoints of the selected flows,
+# each with its least session; Whitelists.from_learned builds the custom whitelist from them)
+LEARNED_ENDPOINT_DTYPE = np.dtype([("dst_ip", "<u4", (4,)), ("rep_src_ip", "<u4", (4,)), ("dst_port", "<u2"),
+                                   ("rep_src_port", "<u2"), ("protocol", "u1"), ("family", "u1"), ("reserved", "<u2"),
+                                   ("dst_name_id", "<u4"), ("rep_slot", "<u4"), ("sessions", "<u4"),
+                                   ("reserved2", "<u4", (3,))])
+LEARN_STATS_FIELDS = ["flows", "selected", "endpoints", "written", "rounds"]
+LEARN_STATS_DTYPE = np.dtype([(f, "<u8") for f in LEARN_STATS_FIELDS] + [("reserved", "<u8", (3,))])
+assert LEARNED_ENDPOINT_DTYPE.itemsize == 64 and LEARN_STATS_DTYPE.itemsize == 64
 # fb_zeek_stats (fb_format_zeek_dev: one Zeek conn.log line per fb_flow_view, formatted on the device), the
 # longest line without its history, and the kernel's thresholds (fb_zeek.hip), for the tests at them: records
 # per workgroup step, the step bytes staged in LDS, the history length the wave copies together
@@ -253,6 +262,7 @@ class FbError(RuntimeError):
 _P, _U32, _U64, _I = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 _PU32, _PU64 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 FB_DEBUG_DENSE_STEAL_POLLS, FB_DEBUG_DENSE_OFFSET_SKEW, FB_DEBUG_VIEW_DIRECT, FB_DEBUG_ZEEK_DIRECT = 1, 2, 3, 4
+FB_DEBUG_LEARN_HASH_MASK = 6  # (5 is unassigned)
 
 GPU_SYMBOLS = [
     ("fb_abi_version", _U32, []),
@@ -363,6 +373,7 @@ GPU_SYMBOLS = [
     ("fb_flow_modified_dev", _I, [_P, _P, _U64, _P]),
     ("fb_flow_export_view_dev", _I, [_P, _P, _P, _U64, _P, _P]),
     ("fb_flow_export_view", _I, [_P, _P, _P, _U64, _PU64, _P]),
+    ("fb_flow_learn_endpoints_dev", _I, [_P, _P, _P, _U64, _P, _P, _P]),
     ("fb_format_zeek_dev", _I, [_P, _P, _U64, _P, _P, _U64, _P, _U64, _P, _P, _P]),
     ("fb_format_zeek_hist_dev", _I, [_P, _P, _U64, _P, _P, _P, _U64, _P, _P, _P]),
     ("fb_hist_store_enable", _I, [_P, _P]),

@@ -19,7 +19,7 @@ from .sessions import (ZEEK_HEADER, Session, SessionFilter, WhitelistState, flow
                        pack_histories, views_to_sessions, words_to_ip)
 from .enrich import Blacklists
 from .analyzer import SessionAnalyzer, anomaly_tag_of, default_service_codes, merge_criticality, path_cut
-from .whitelists import Whitelists, is_session_in_whitelist, no_match_reason
+from .whitelists import Whitelists, dedup_endpoints, is_session_in_whitelist, no_match_reason
 
 
 def lan_v6_table(prefixes):
@@ -601,14 +601,14 @@ class FlodbaddGpuCapture:
             d.download(out, cap * out.itemsize)
         return out[:cap]
 
-    def _compact_export(self, export_fn, dtypes, *lead):
-        """A compacting export -- export_fn(ctx, *lead, one output per dtype, cap, d_n, stream) -- with room for
-        every flow: the count is read back and each output trimmed to it -> one array per dtype."""
+    def _compact_export(self, export_fn, dtypes, *lead, extra=()):
+        """A compacting export -- export_fn(ctx, *lead, one output per dtype, cap, d_n, *extra, stream) -- with room
+        for every flow: the count is read back and each output trimmed to it -> one array per dtype."""
         cap = max(self.flow_count(), 1)
         outs = [np.zeros(cap, dtype=t) for t in dtypes]
         bufs = [N.DeviceBuffer(o.nbytes) for o in outs]
         d_n = N.DeviceBuffer(8)
-        N.check(getattr(N.gpu_lib(), export_fn)(self.ctx, *lead, *(b.ptr for b in bufs), cap, d_n.ptr, None))
+        N.check(getattr(N.gpu_lib(), export_fn)(self.ctx, *lead, *(b.ptr for b in bufs), cap, d_n.ptr, *extra, None))
         m = min(int(d_n.download(np.zeros(1, dtype=np.uint64))[0]), cap)
         return tuple(b.download(o)[:m] for b, o in zip(bufs, outs))
 
@@ -647,6 +647,16 @@ class FlodbaddGpuCapture:
         n = C.c_uint64(0)
         N.check(N.gpu_lib().fb_flow_export_view(self.ctx, N.ptr(q), N.ptr(out), cnt, C.byref(n), None))
         return out[: n.value]
+
+    def learn_endpoints(self, view_set=N.FB_VIEW_ALL, since_ns=None, session_filter=None):
+        """fb_flow_learn_endpoints_dev: the distinct endpoints -- (dst_ip, family, dst_port, protocol, dst name id)
+        -- of the flows export_view would select with the same arguments, each with its least session as the
+        representative, in ascending rep_slot order -> (LEARNED_ENDPOINT_DTYPE records, the call's counters)."""
+        q = self._view_query(view_set, since_ns, session_filter)
+        st = np.zeros(1, dtype=N.LEARN_STATS_DTYPE)
+        recs, = self._compact_export("fb_flow_learn_endpoints_dev", [N.LEARNED_ENDPOINT_DTYPE], N.ptr(q),
+                                     extra=(N.ptr(st),))
+        return recs, stats_dict(st, N.LEARN_STATS_FIELDS)
 
     def _since(self, which, incremental):
         """What a getter call selects by: an incremental fetch, the flows modified since the getter's last full
@@ -1143,11 +1153,71 @@ class FlodbaddGpuCapture:
                                                     s.dst_port, s.protocol.name, a[0], a[1], a[2], proc.get(s))
         return out
 
-    def create_custom_whitelists(self, dns_resolutions=None, process_names=None):
+    def _learned(self, view_set, dns_resolutions=None):
+        """The custom_whitelist model learned on the device from the flows of view_set (learn_endpoints,
+        Whitelists.from_learned).  A capture that tracks DNS brings the flows' domains forward first
+        (update_domains: dst_domain as the reference's sessions carry it); dns_resolutions {ip: domain}, when
+        given, stands for dst_domain instead, as on the host path."""
+        if self.track_dns and dns_resolutions is None:
+            self.update_domains()
+        recs, _ = self.learn_endpoints(view_set)
+        names = self.dns_names(recs["dst_name_id"]) if (self.track_dns and dns_resolutions is None) else {}
+        w = Whitelists.from_learned(recs, names)
+        if dns_resolutions is not None:
+            info = w.whitelists["custom_whitelist"]
+            for ep in info.endpoints:
+                dom = dns_resolutions.get(ep.ip)
+                ep.domain = None if dom in ("Unknown", "Resolving") else dom
+            info.endpoints = dedup_endpoints(info.endpoints)  # (ids told apart what one dictionary entry names)
+        return w
+
+    def create_custom_whitelists(self, dns_resolutions=None, process_names=None, on_device=False):
         """create_custom_whitelists (src/capture.rs:511-531): the WhitelistsJSON text of a list learned
-        from every session of the table."""
+        from every session of the table.  on_device: the distinct endpoints and their representative
+        sessions are found by one pass on the device (learn_endpoints) instead of a download of every flow;
+        the endpoints are then in table-slot order of their representatives, and the domains those the capture
+        tracked itself (track_dns) unless dns_resolutions is given.  The device holds no process names: with a
+        non-empty process_names the host path runs, whatever on_device says."""
+        if on_device and not process_names:
+            return self._learned(N.FB_VIEW_ALL, dns_resolutions).to_json()
         sessions = flows_to_sessions(self.export_flows(SessionFilter.All))
         return Whitelists.new_from_sessions(sessions, dns_resolutions, process_names).to_json()
+
+    def augment_custom_whitelists(self, now_ns=None, dns_resolutions=None, process_names=None):
+        """augment_custom_whitelists (src/capture.rs:533-612): the current model's custom_whitelist (none: no
+        endpoints, no extends) with the endpoints learned from the current whitelist exceptions appended,
+        de-duplicated by fingerprint -- existing endpoints win --, as compact WhitelistsJSON text: one list named
+        custom_whitelist, the `extends` preserved, today's date, no signature.  With now_ns the sessions are
+        brought forward first (update_sessions), else the whitelist pass runs with the inputs given here or,
+        without any, the stored ones (as get_whitelist_exceptions).  The exceptions' endpoints are learned on
+        the device over FB_VIEW_WL_EXCEPTIONS; with process names -- which the device does not hold, and which
+        can make the host accept a session the pass marked -- on the host from get_whitelist_exceptions().
+        Without an active list there are no exceptions: the current custom list comes back re-dated."""
+        if dns_resolutions is None and process_names is None:
+            dns_resolutions, process_names = self._wl_inputs
+        if now_ns is not None:
+            self.update_sessions(now_ns, dns_resolutions, process_names)
+        else:
+            self.update_whitelist(dns_resolutions, process_names)
+        cur = self._whitelists.whitelists.get("custom_whitelist")
+        endpoints, extends = (list(cur.endpoints), cur.extends) if cur else ([], None)
+        if not self._wl_name:
+            learned = []
+        elif process_names:
+            dns = dns_resolutions
+            if dns is None and self.track_dns:
+                dns = {str(ip): name for ip, name in self.dns_resolutions().items()}
+            learned = Whitelists.new_from_sessions(self.get_whitelist_exceptions(), dns, process_names)
+        else:
+            learned = self._learned(N.FB_VIEW_WL_EXCEPTIONS, dns_resolutions)
+        if learned:
+            learned = learned.whitelists["custom_whitelist"].endpoints
+        return Whitelists().as_custom(dedup_endpoints(endpoints + learned), extends).to_json(compact=True)
+
+    @staticmethod
+    def merge_custom_whitelists(json_a, json_b):
+        """merge_custom_whitelists (src/capture.rs:614-625): Whitelists.merge_custom_whitelists."""
+        return Whitelists.merge_custom_whitelists(json_a, json_b)
 
     def clear_all_sessions(self):
         """src/capture.rs:396 (`stop()` clears the table, capture.rs:383)."""

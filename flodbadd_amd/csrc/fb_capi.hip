@@ -230,6 +230,9 @@ struct fb_ctx {
     // Zeek export (fb_format_zeek_dev, fb_zeek.hip): rocPRIM's scan storage
     bool zeek_direct = false;       // FB_DEBUG_ZEEK_DIRECT: no LDS staging of the text
     StreamScratch zeek_tmp;
+    // endpoint learning (fb_flow_learn_endpoints_dev, fb_learn.hip): the per-table-slot arrays, the endpoint index
+    StreamScratch learn_slots, learn_index;
+    unsigned long long learn_hash_mask = ~0ull;  // FB_DEBUG_LEARN_HASH_MASK
     // timed contexts (FB_CFG_TIMED, fb_time.hip): the capture-time pass's scratch
     bool timed = false;
     StreamScratch tscratch;
@@ -755,6 +758,9 @@ int fb_debug_set(fb_ctx* c, uint32_t knob, uint64_t value) {
             return FB_OK;
         case FB_DEBUG_ZEEK_DIRECT:
             c->zeek_direct = value != 0;
+            return FB_OK;
+        case FB_DEBUG_LEARN_HASH_MASK:
+            c->learn_hash_mask = value ? value : ~0ull;
             return FB_OK;
         default:
             return set_err(FB_ERR_INVAL, "unknown debug knob %u", knob);
@@ -2374,18 +2380,8 @@ static int view_query_check(const fb_ctx* c, const fb_view_query* q) {
     return FB_OK;
 }
 
-int fb_flow_export_view_dev(fb_ctx* c, const fb_view_query* q, fb_flow_view* d_out, uint64_t cap, uint64_t* d_n,
-                            void* stream) {
-    if (!c || !d_n || (cap && !d_out) || (reinterpret_cast<uintptr_t>(d_out) & 15u))
-        return set_err(FB_ERR_INVAL, "ctx and d_n are required, d_out (16-B aligned) unless cap is 0");
-    int rc = view_query_check(c, q);
-    if (rc) return rc;
-    DeviceGuard g(c->device);
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
-    rc = join_updates(c, s);
-    if (!rc && q->filter != FB_FILTER_ALL) rc = upload_cfg(c, s);  // the LAN configuration as of now
-    if (rc) return rc;
+// The table, every plane and the (checked) query as the kernels read them.
+static ViewArgs view_args(const fb_ctx* c, const fb_view_query* q) {
     ViewArgs a;
     a.table = c->tb.slots;
     a.time = c->plane<FlowTime>(kPlaneTime);
@@ -2400,6 +2396,22 @@ int fb_flow_export_view_dev(fb_ctx* c, const fb_view_query* q, fb_flow_view* d_o
     a.set = q->set;
     a.filter = q->filter;
     a.flags = q->flags;
+    return a;
+}
+
+int fb_flow_export_view_dev(fb_ctx* c, const fb_view_query* q, fb_flow_view* d_out, uint64_t cap, uint64_t* d_n,
+                            void* stream) {
+    if (!c || !d_n || (cap && !d_out) || (reinterpret_cast<uintptr_t>(d_out) & 15u))
+        return set_err(FB_ERR_INVAL, "ctx and d_n are required, d_out (16-B aligned) unless cap is 0");
+    int rc = view_query_check(c, q);
+    if (rc) return rc;
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_n, 0, 8, s));
+    rc = join_updates(c, s);
+    if (!rc && q->filter != FB_FILTER_ALL) rc = upload_cfg(c, s);  // the LAN configuration as of now
+    if (rc) return rc;
+    const ViewArgs a = view_args(c, q);
     HIP_TRY(launch_flow_view(a, d_out, cap, (unsigned long long*)d_n, !c->view_direct, s));
     return FB_OK;
 }
@@ -2419,6 +2431,23 @@ int fb_flow_export_view(fb_ctx* c, const fb_view_query* q, fb_flow_view* out, ui
     return export_to_host(c, out, m, sizeof(fb_flow_view), n, (hipStream_t)stream, "view export", [&](void* d_out) {
         return fb_flow_export_view_dev(c, q, (fb_flow_view*)d_out, m, reinterpret_cast<uint64_t*>(c->d_n.get()), stream);
     });
+}
+
+// ---- endpoint learning (fb_learn.hip) ----------------------------------------------------------------
+// Synchronous, like the passes: drains the updates in flight; it writes no plane and no stamp.
+int fb_flow_learn_endpoints_dev(fb_ctx* c, const fb_view_query* q, fb_learned_endpoint* d_out, uint64_t cap,
+                                uint64_t* d_n, fb_learn_stats* out, void* stream) {
+    if (!c || !d_n || (cap && !d_out) || (reinterpret_cast<uintptr_t>(d_out) & 15u))
+        return set_err(FB_ERR_INVAL, "ctx and d_n are required, d_out (16-B aligned) unless cap is 0");
+    int rc = view_query_check(c, q);
+    if (rc) return rc;
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    rc = drain_updates(c);
+    if (!rc && q->filter != FB_FILTER_ALL) rc = upload_cfg(c, s);  // the LAN configuration as of now
+    if (rc) return rc;
+    return learn_endpoints(view_args(c, q), c->plane<uint2>(kPlaneDom), c->learn_hash_mask, c->learn_slots,
+                           c->learn_index, d_out, cap, (unsigned long long*)d_n, out, s);
 }
 
 // ---- Zeek conn.log export (fb_zeek.hip) -----------------------------------------------------------

@@ -914,8 +914,53 @@ struct ViewArgs {
     uint32_t set, filter, flags;
 };
 static_assert(sizeof(fb_flow_view) == 256 && sizeof(fb_view_query) == 24, "view ABI");
+// Does the query select occupied slot i?  (everything but the tag test; shared by the view export and the
+// endpoint learning pass, fb_learn.hip)
+__device__ __forceinline__ bool view_take(const ViewArgs& a, unsigned long long i) {
+    switch (a.set) {
+        case FB_VIEW_CURRENT:
+            if (a.status) {
+                const uint32_t b = a.status[i];
+                if (!(b == 0u || (b & kAgeCurrent))) return false;
+            }
+            break;
+        case FB_VIEW_BLACKLISTED:
+            if (!a.bl || a.bl[i] == 0ull) return false;
+            break;
+        case FB_VIEW_WL_EXCEPTIONS:
+            if (!a.wl || !(a.wl[i] & FB_WL_NONCONFORMING)) return false;
+            break;
+        case FB_VIEW_ANOMALOUS:
+            if (!a.an || a.an[i].level < FB_AN_SUSPICIOUS) return false;
+            break;
+        default:
+            break;
+    }
+    if (a.flags & FB_VIEW_MODIFIED_SINCE) {  // (timed contexts only: a.time is set)
+        const unsigned long long act = a.time[i].last_activity_ns, st = a.mod ? a.mod[i] : 0ull;
+        if (!((act > st ? act : st) > a.since)) return false;
+    }
+    // get_sessions' read-time filter (src/capture.rs:1603-1608): is_lan_ip evaluated now
+    return a.filter == FB_FILTER_ALL || slot_local(a.cfg, a.table[i]) == (a.filter == FB_FILTER_LOCAL_ONLY);
+}
+// the launchers' argument checks (what the C ABI's query check leaves to them)
+inline bool view_args_valid(const ViewArgs& a) {
+    return a.table && a.cap != 0ull && (!(a.flags & FB_VIEW_MODIFIED_SINCE) || a.time) &&
+           (a.filter == FB_FILTER_ALL || a.cfg);
+}
 hipError_t launch_flow_view(const ViewArgs& a, fb_flow_view* out, unsigned long long out_cap, unsigned long long* d_n,
                             bool staged, hipStream_t s);
+
+// Endpoint learning (fb_learn.hip, fb_flow_learn_endpoints_dev): the distinct (dst_ip, family,
+// dst_port, protocol, dst name id) of the flows the query selects, each with its least session.  dom: the
+// domain plane or null (every id 0).  hash_mask: FB_DEBUG_LEARN_HASH_MASK.  per_slot / index: the context's
+// scratch for the per-table-slot arrays and for the endpoint index (sized once the selected flows are
+// counted).  Synchronous; returns an fb_err.
+static_assert(sizeof(fb_learned_endpoint) == 64 && sizeof(fb_learn_stats) == 64, "learn ABI");
+class StreamScratch;
+int learn_endpoints(const ViewArgs& a, const uint2* dom, unsigned long long hash_mask, StreamScratch& per_slot,
+                    StreamScratch& index, fb_learned_endpoint* out, unsigned long long out_cap, unsigned long long* d_n,
+                    fb_learn_stats* stats, hipStream_t s);
 
 // Zeek export (fb_zeek.hip, fb_format_zeek_dev): n > 0 view records, the history blob (null: none) and its
 // per-slot offsets, the text buffer and its capacity, line_off[n + 1] and the stats (zeroed by the caller).

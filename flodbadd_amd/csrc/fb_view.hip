@@ -33,36 +33,7 @@ constexpr uint32_t kViewStage = 128;            // records staged per round
 constexpr uint32_t kViewRow = 272;              // LDS bytes per staged record (256 + one 16-B column)
 constexpr uint32_t kViewCols = sizeof(fb_flow_view) / 16u;
 
-// Does the query select occupied slot i?  (everything but the tag test)
-__device__ __forceinline__ bool view_take(const ViewArgs& a, unsigned long long i) {
-    switch (a.set) {
-        case FB_VIEW_CURRENT:
-            if (a.status) {
-                const uint32_t b = a.status[i];
-                if (!(b == 0u || (b & kAgeCurrent))) return false;
-            }
-            break;
-        case FB_VIEW_BLACKLISTED:
-            if (!a.bl || a.bl[i] == 0ull) return false;
-            break;
-        case FB_VIEW_WL_EXCEPTIONS:
-            if (!a.wl || !(a.wl[i] & FB_WL_NONCONFORMING)) return false;
-            break;
-        case FB_VIEW_ANOMALOUS:
-            if (!a.an || a.an[i].level < FB_AN_SUSPICIOUS) return false;
-            break;
-        default:
-            break;
-    }
-    if (a.flags & FB_VIEW_MODIFIED_SINCE) {  // (timed contexts only: a.time is set)
-        const unsigned long long act = a.time[i].last_activity_ns, st = a.mod ? a.mod[i] : 0ull;
-        if (!((act > st ? act : st) > a.since)) return false;
-    }
-    // get_sessions' read-time filter (src/capture.rs:1603-1608): is_lan_ip evaluated now
-    return a.filter == FB_FILTER_ALL || slot_local(a.cfg, a.table[i]) == (a.filter == FB_FILTER_LOCAL_ONLY);
-}
-
-// The view record of slot i.
+// The view record of slot i.  (The predicate, view_take, is in fb_internal.h: fb_learn.hip selects by it too.)
 __device__ __forceinline__ void view_of(const ViewArgs& a, unsigned long long i, fb_flow_view& v) {
     v.rec = flow_rec_at(a.table, a.time, i);
     if (a.time) {
@@ -145,9 +116,7 @@ __global__ __launch_bounds__(256) void k_flow_view(const ViewArgs a, fb_flow_vie
 
 hipError_t launch_flow_view(const ViewArgs& a, fb_flow_view* out, unsigned long long out_cap, unsigned long long* d_n,
                             bool staged, hipStream_t s) {
-    if (!a.table || !d_n || a.cap == 0ull || (out_cap && !out)) return hipErrorInvalidValue;
-    if ((a.flags & FB_VIEW_MODIFIED_SINCE) && !a.time) return hipErrorInvalidValue;
-    if (a.filter != FB_FILTER_ALL && !a.cfg) return hipErrorInvalidValue;
+    if (!view_args_valid(a) || !d_n || (out_cap && !out)) return hipErrorInvalidValue;
     const dim3 g(sweep_grid(a.cap, 1024ull));
     hipLaunchKernelGGL(staged ? k_flow_view<true> : k_flow_view<false>, g, dim3(256), 0, s, a, out, out_cap, d_n);
     return hipGetLastError();

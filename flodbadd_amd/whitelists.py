@@ -4,6 +4,8 @@
                           may extend each other; get_all_endpoints flattens one (180-211),
                           new_from_sessions learns one from a session list (103-177).  There are no
                           built-in lists: the reference's default database is not part of this package.
+  Whitelists.from_learned the same list from the distinct endpoints the device found (fb_flow_learn_endpoints_dev);
+  Whitelists.merge_custom_whitelists  two documents merged by list name (223-299).
   Whitelists.compile      the flattened list as fb_wl_endpoint rows for fb_set_whitelist.  The device
                           sees neither a session's dst_domain nor its process, so the domains the host
                           has resolved are expanded here: dst_domain is a function of dst_ip, hence a
@@ -23,7 +25,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import _native as N
-from .sessions import ip_to_words
+from .sessions import ip_to_words, words_to_ip
 
 log = logging.getLogger(__name__)
 
@@ -62,6 +64,16 @@ class WhitelistInfo:
     name: str
     extends: Optional[List[str]] = None
     endpoints: List[WhitelistEndpoint] = field(default_factory=list)
+
+
+def dedup_endpoints(endpoints):
+    """The endpoints without those whose fingerprint an earlier one has (the first occurrence stays)."""
+    seen, out = set(), []
+    for ep in endpoints:
+        if ep.fingerprint() not in seen:
+            seen.add(ep.fingerprint())
+            out.append(ep)
+    return out
 
 
 def ascii_lower(s):
@@ -252,8 +264,9 @@ class Whitelists:
                 "whitelists": [{"name": w.name, "extends": w.extends, "endpoints": [asdict(e) for e in w.endpoints]}
                                for w in self.whitelists.values()]}
 
-    def to_json(self):
-        return json.dumps(self.to_dict(), indent=2)
+    def to_json(self, compact=False):
+        """Pretty-printed (serde_json::to_string_pretty), or compact (to_string)."""
+        return json.dumps(self.to_dict(), separators=(",", ":")) if compact else json.dumps(self.to_dict(), indent=2)
 
     def _flatten(self, name, visited):
         info = self.whitelists.get(name)
@@ -284,7 +297,7 @@ class Whitelists:
         process_names {Session: name} stand for SessionInfo.dst_domain / l7."""
         w = Whitelists()
         endpoints, seen = [], set()
-        for info in sessions:
+        for info in sessions:  # (de-duplicated as it goes: a table-sized list has millions of sessions)
             s = info.session
             dom = (dns_resolutions or {}).get(str(s.dst_ip))
             ep = WhitelistEndpoint(
@@ -294,10 +307,65 @@ class Whitelists:
             if ep.fingerprint() not in seen:
                 seen.add(ep.fingerprint())
                 endpoints.append(ep)
-        w.whitelists["custom_whitelist"] = WhitelistInfo("custom_whitelist", None, endpoints)
+        return w.as_custom(endpoints)
+
+    def as_custom(self, endpoints, extends=None):
+        """This model as new_from_sessions leaves it: one list named custom_whitelist, today's date."""
+        self.whitelists["custom_whitelist"] = WhitelistInfo("custom_whitelist", extends, endpoints)
         t = time.localtime()
-        w.date = "%s %02dth %d" % (time.strftime("%B", t), t.tm_mday, t.tm_year)  # "%B %dth %Y"
-        return w
+        self.date = "%s %02dth %d" % (time.strftime("%B", t), t.tm_mday, t.tm_year)  # "%B %dth %Y"
+        return self
+
+    @staticmethod
+    def from_learned(records, names=None):
+        """new_from_sessions from fb_learned_endpoint records (FlodbaddGpuCapture.learn_endpoints): one
+        endpoint per record, in the records' order -- domain = names[dst_name_id] ({id: str} from
+        FlodbaddGpuCapture.dns_names; id 0: None), ip, port, protocol, and the description of the record's
+        representative session.  No process: the device has none."""
+        names = names or {}
+        endpoints = []
+        for r in records:
+            fam, dst = int(r["family"]), words_to_ip(r["dst_ip"], int(r["family"]))
+            nid = int(r["dst_name_id"])
+            endpoints.append(WhitelistEndpoint(
+                domain=names[nid] if nid else None, ip=str(dst), port=int(r["dst_port"]),
+                protocol={6: "TCP", 17: "UDP"}[int(r["protocol"])],
+                description="Auto-generated from session: %s:%d -> %s:%d" % (
+                    words_to_ip(r["rep_src_ip"], fam), int(r["rep_src_port"]), dst, int(r["dst_port"]))))
+        return Whitelists().as_custom(endpoints)
+
+    @staticmethod
+    def merge_custom_whitelists(json_a, json_b):
+        """src/whitelists.rs:223-299: the lists of two WhitelistsJSON documents merged by name -- a's
+        endpoints, then b's, de-duplicated per list by fingerprint (the first occurrence stays); extends
+        from the first source that has one; date and signature from a.  The lists appear in the order of
+        their first appearance (the reference collects a HashMap: unspecified).  Compact JSON; ValueError
+        when either document does not parse."""
+        merged = {}
+        for which, text in (("first", json_a), ("second", json_b)):
+            try:
+                data = json.loads(text) if isinstance(text, (str, bytes)) else text
+                if not isinstance(data, dict):
+                    raise ValueError("not a WhitelistsJSON object")
+                model = Whitelists(data)  # the model's checks: unknown or missing fields
+                infos = [WhitelistInfo(i["name"], None if i.get("extends") is None else list(i["extends"]),
+                                       [WhitelistEndpoint.from_dict(e) for e in i["endpoints"]])
+                         for i in data["whitelists"]]
+            except (ValueError, TypeError, KeyError, AttributeError) as e:
+                raise ValueError("Failed to parse %s whitelist JSON: %s" % (which, e)) from e
+            if which == "first":
+                date, signature = model.date, model.signature
+            for info in infos:  # (a name that repeats inside one document merges too)
+                entry = merged.setdefault(info.name, WhitelistInfo(info.name, info.extends, []))
+                if entry.extends is None:
+                    entry.extends = info.extends
+                entry.endpoints.extend(info.endpoints)
+        out = Whitelists()
+        out.date, out.signature = date, signature
+        for info in merged.values():
+            info.endpoints = dedup_endpoints(info.endpoints)
+        out.whitelists = merged
+        return out.to_json(compact=True)
 
     def compile(self, name, asn_records=None, dns_resolutions=None):
         """The flattened list `name` as fb_wl_endpoint rows.  asn_records: the (as_number, country,
@@ -376,4 +444,4 @@ def rows_from_flows(flows):
 
 
 __all__ = ["WhitelistEndpoint", "WhitelistInfo", "Whitelists", "CompiledWhitelist", "domain_matches", "ip_matches",
-           "endpoint_matches", "is_session_in_whitelist", "no_match_reason", "rows_from_flows", "ascii_lower", "rust_debug", "parse_ip", "parse_net"]
+           "endpoint_matches", "is_session_in_whitelist", "no_match_reason", "rows_from_flows", "dedup_endpoints", "ascii_lower", "rust_debug", "parse_ip", "parse_net"]

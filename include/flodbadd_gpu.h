@@ -342,12 +342,17 @@ int fb_set_frame_times(fb_ctx* ctx, const uint64_t* d_ts);
  * FB_DEBUG_VIEW_DIRECT -- non-zero: fb_flow_export_view_dev stores one record per lane instead of staging
  * a step's records in LDS (same result; the shape the staged copy-out is measured against);
  * FB_DEBUG_ZEEK_DIRECT -- non-zero: fb_format_zeek_dev stores every step's lines straight to global memory,
- * the path a step too large for the LDS staging takes (same bytes). */
+ * the path a step too large for the LDS staging takes (same bytes);
+ * FB_DEBUG_LEARN_HASH_MASK -- ANDed into the fingerprint hash of fb_flow_learn_endpoints_dev before the tag
+ * and the home slot are taken from it, so the tests can force equal tags and shared probe chains without
+ * inverting the hash (as fb_dns_track_config.hash_mask); 0 restores all bits.  (Bit 63 is the tag's "used"
+ * bit, set in every tag: a mask of bit 63 alone leaves no hash bit -- one tag, one home, one probe chain.) */
 enum fb_debug_knob {
     FB_DEBUG_DENSE_STEAL_POLLS = 1,
     FB_DEBUG_DENSE_OFFSET_SKEW = 2,
     FB_DEBUG_VIEW_DIRECT = 3,
-    FB_DEBUG_ZEEK_DIRECT = 4
+    FB_DEBUG_ZEEK_DIRECT = 4,
+    FB_DEBUG_LEARN_HASH_MASK = 6 /* (5 stays unassigned: the refusal of an unknown knob is tested with it) */
 };
 int fb_debug_set(fb_ctx* ctx, uint32_t knob, uint64_t value);
 /* Whether the fused parse + upsert calls (fb_process_seg_dev, fb_process_seg_async_dev) store the
@@ -1179,6 +1184,42 @@ int fb_flow_export_view_dev(fb_ctx* ctx, const fb_view_query* query, fb_flow_vie
                             void* stream);
 int fb_flow_export_view(fb_ctx* ctx, const fb_view_query* query, fb_flow_view* out, uint64_t cap, uint64_t* n,
                         void* stream);
+
+/* ---- whitelist learning (Whitelists::new_from_sessions, src/whitelists.rs:103-177) ----
+ * The distinct endpoints of the flows a query selects.  An endpoint is the fingerprint (dst_ip, family,
+ * dst_port, protocol, dst_name_id): dst_name_id is the domain plane's id of the flow (fb_flow_domains),
+ * 0 -- the reference's None -- before any domain pass and without DNS tracking.  Each endpoint carries a
+ * representative session, the least of its flows under Session's derived Ord (inside a group: source
+ * address, then source port), so it depends neither on the table's layout nor on a race. */
+typedef struct fb_learned_endpoint {
+    uint32_t dst_ip[4];     /*  0: session_key word order                                                */
+    uint32_t rep_src_ip[4]; /* 16: the representative session's source                                   */
+    uint16_t dst_port;      /* 32 */
+    uint16_t rep_src_port;  /* 34 */
+    uint8_t protocol;       /* 36: 6 / 17                                                                */
+    uint8_t family;         /* 37: 2 / 10                                                                */
+    uint16_t reserved;      /* 38: 0                                                                     */
+    uint32_t dst_name_id;   /* 40: the domain plane's id, 0 = no domain                                  */
+    uint32_t rep_slot;      /* 44: the representative's table slot                                       */
+    uint32_t sessions;      /* 48: selected flows with this fingerprint                                  */
+    uint32_t reserved2[3];  /* 52: 0                                                                     */
+} fb_learned_endpoint;      /* 64 bytes; an output array starts at a 16-byte boundary                    */
+typedef struct fb_learn_stats {
+    uint64_t flows;     /*  0: flows in the table                                                        */
+    uint64_t selected;  /*  8: of them selected by the query                                             */
+    uint64_t endpoints; /* 16: distinct fingerprints among the selected (= *d_n)                         */
+    uint64_t written;   /* 24: records written: min(endpoints, cap)                                      */
+    uint64_t rounds;    /* 32: insert rounds the index took                                              */
+    uint64_t reserved[3];
+} fb_learn_stats; /* 64 bytes */
+/* One record per distinct endpoint of the flows `query` selects (read exactly as fb_flow_export_view_dev
+ * reads it, same FB_ERR_INVAL cases), in ascending rep_slot order; *d_n (device u64) = the distinct
+ * endpoints, only the first `cap` are written (cap may be 0).  Two calls on an unchanged table write
+ * identical bytes.  Reads the table and the planes only.  d_out, d_n: DEVICE pointers (d_out 16-B aligned);
+ * out: HOST, may be NULL.  Synchronous (the insert rounds read a counter between launches), after the
+ * updates in flight.  FB_ERR_INTERNAL if the index insert did not converge within its round bound. */
+int fb_flow_learn_endpoints_dev(fb_ctx* ctx, const fb_view_query* query, fb_learned_endpoint* d_out, uint64_t cap,
+                                uint64_t* d_n, fb_learn_stats* out, void* stream);
 
 /* ---- Zeek conn.log export (format_sessions_zeek, src/sessions.rs:694-774) ----------
  * One text line per fb_flow_view record, formatted on the device: 21 tab-separated fields and '\n'
