@@ -263,6 +263,7 @@ _P, _U32, _U64, _I = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 _PU32, _PU64 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 FB_DEBUG_DENSE_STEAL_POLLS, FB_DEBUG_DENSE_OFFSET_SKEW, FB_DEBUG_VIEW_DIRECT, FB_DEBUG_ZEEK_DIRECT = 1, 2, 3, 4
 FB_DEBUG_LEARN_HASH_MASK = 6  # (5 is unassigned)
+FB_DEBUG_DNS_LAUNCH = 7
 
 GPU_SYMBOLS = [
     ("fb_abi_version", _U32, []),

@@ -762,6 +762,9 @@ int fb_debug_set(fb_ctx* c, uint32_t knob, uint64_t value) {
         case FB_DEBUG_LEARN_HASH_MASK:
             c->learn_hash_mask = value ? value : ~0ull;
             return FB_OK;
+        case FB_DEBUG_DNS_LAUNCH:
+            if (!c->dns) return set_err(FB_ERR_INVAL, "DNS tracking is not enabled (fb_dns_track_enable)");
+            return dnstrack_set_launch(c->dns, value);
         default:
             return set_err(FB_ERR_INVAL, "unknown debug knob %u", knob);
     }

@@ -31,6 +31,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "fb_dns_hash.h"
 #include "fb_host.h"
 #include "fb_internal.h"
 
@@ -51,23 +52,7 @@ enum Ctr : uint32_t { cMsgs, cQueries, cResponses, cAddrBound, cMatched, cAddrIt
 __device__ __forceinline__ unsigned long long ld64(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// dword k of a name of `len` bytes, the bytes past the length zeroed (the parse leaves them unspecified)
-__device__ __forceinline__ uint32_t name_dword(const uint32_t* nm, uint32_t k, uint32_t len) {
-    const uint32_t w = nm[k], rest = len - 4u * k;
-    return rest >= 4u ? w : (w & ((1u << (8u * rest)) - 1u));
-}
-__device__ __forceinline__ unsigned long long name_tag(const uint32_t* nm, uint32_t len, unsigned long long hash_mask) {
-    unsigned long long h = 0x9E3779B97F4A7C15ull ^ len;
-    const uint32_t nd = (len + 3u) >> 2;
-    for (uint32_t k = 0; k < nd; ++k) {
-        h ^= name_dword(nm, k, len);
-        h *= 0xBF58476D1CE4E5B9ull;
-        h ^= h >> 31;
-    }
-    h *= 0xFF51AFD7ED558CCDull;
-    h ^= h >> 33;
-    return (h & hash_mask) | kDnsTagUsed;
-}
+// (name_dword, name_tag and dns_addr_tag: fb_dns_hash.h)
 __device__ __forceinline__ bool name_equal(const uint32_t* a, const uint32_t* b, uint32_t len) {
     const uint32_t nd = (len + 3u) >> 2;
     for (uint32_t k = 0; k < nd; ++k)
@@ -738,6 +723,16 @@ int dnstrack_track(DnsTrack* t, const fb_dns_msg* msgs, const char* names, const
         out->addrs_new = h[cAddrsNew];
         out->rounds = std::max(name_rounds, addr_rounds);
     }
+    return FB_OK;
+}
+
+// fb_debug_set FB_DEBUG_DNS_LAUNCH: the next launch's number, so that a test reaches stamps_reset without
+// 2^32 launches.  Never backwards: a slot stamped above the launch that reads it says "not yet" for ever.
+int dnstrack_set_launch(DnsTrack* t, uint64_t launch) {
+    if (launch == 0 || launch > 0xFFFFFFFFull) return set_err(FB_ERR_INVAL, "DNS tracker launch number %llu: 1 .. 2^32 - 1", (unsigned long long)launch);
+    if (launch < t->launch)
+        return set_err(FB_ERR_INVAL, "DNS tracker launch number %llu is below the current one, %u", (unsigned long long)launch, t->launch);
+    t->launch = (uint32_t)launch;
     return FB_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/flodbadd_gpu.h"
+#include "fb_dns_hash.h"
 
 namespace fbk {
 
@@ -992,7 +993,6 @@ hipError_t launch_dns_parse(const uint8_t* frames, unsigned long long frames_byt
 // aval[slot] = order << kDnsIdBits | name_id, the largest order (the last writer in packet order) kept by
 // a 64-bit atomicMax.  DnsTables is what a reader needs: the domain pass and fb_dns_lookup_dev.
 constexpr uint32_t kDnsIdBits = 24, kDnsIdMask = (1u << kDnsIdBits) - 1u;
-constexpr unsigned long long kDnsTagUsed = 1ull << 63;
 constexpr unsigned long long kDnsMaxOrder = 1ull << 40;  // orders below this fit beside an id
 struct DnsTables {
     const unsigned long long* atag;
@@ -1004,18 +1004,7 @@ struct DnsTables {
     const uint16_t* name_len;
     uint32_t n_names;
 };
-__host__ __device__ inline unsigned long long dns_addr_tag(const uint32_t w[4], uint32_t family,
-                                                           unsigned long long hash_mask) {
-    unsigned long long h = 0x9E3779B97F4A7C15ull ^ family;
-    for (int j = 0; j < 4; j += 2) {
-        h ^= (unsigned long long)w[j] | ((unsigned long long)w[j + 1] << 32);
-        h *= 0xBF58476D1CE4E5B9ull;
-        h ^= h >> 31;
-    }
-    h *= 0xFF51AFD7ED558CCDull;
-    h ^= h >> 33;
-    return (h & hash_mask) | kDnsTagUsed;
-}
+// (dns_addr_tag, name_tag and kDnsTagUsed: fb_dns_hash.h, plain C++ that host programs include too)
 // dns_resolutions.get(ip): the name id the address resolves to, 0 for none.  Read-only: no tracking call
 // runs beside it (the tracking call is synchronous).
 __device__ __forceinline__ uint32_t dns_lookup(const DnsTables& t, const uint32_t w[4], uint32_t family) {
@@ -1038,6 +1027,7 @@ int dnstrack_clear(DnsTrack* t, hipStream_t s);
 int dnstrack_track(DnsTrack* t, const fb_dns_msg* msgs, const char* names, const fb_ip* addrs, uint32_t n,
                    const fb_batch_stats* stats, const unsigned long long* ts, uint32_t* taken, fb_dns_track_stats* out,
                    hipStream_t s);
+int dnstrack_set_launch(DnsTrack* t, uint64_t launch);  // FB_DEBUG_DNS_LAUNCH: 1 .. 2^32 - 1, never backwards
 int dnstrack_expire(DnsTrack* t, unsigned long long now, uint64_t* dropped, hipStream_t s);
 int dnstrack_info(DnsTrack* t, fb_dns_track_info* out, hipStream_t s);
 int dnstrack_export_resolutions(DnsTrack* t, fb_dns_resolution* out, uint64_t cap, uint64_t* d_n, hipStream_t s);

@@ -346,13 +346,19 @@ int fb_set_frame_times(fb_ctx* ctx, const uint64_t* d_ts);
  * FB_DEBUG_LEARN_HASH_MASK -- ANDed into the fingerprint hash of fb_flow_learn_endpoints_dev before the tag
  * and the home slot are taken from it, so the tests can force equal tags and shared probe chains without
  * inverting the hash (as fb_dns_track_config.hash_mask); 0 restores all bits.  (Bit 63 is the tag's "used"
- * bit, set in every tag: a mask of bit 63 alone leaves no hash bit -- one tag, one home, one probe chain.) */
+ * bit, set in every tag: a mask of bit 63 alone leaves no hash bit -- one tag, one home, one probe chain.);
+ * FB_DEBUG_DNS_LAUNCH -- the number the DNS tracker gives its next kernel launch (the stamps of its table
+ * slots are launch numbers, and a tracker past launch 0xF0000000 restamps what it holds before its next
+ * call: a week of capture, or this knob).  FB_ERR_INVAL without fb_dns_track_enable, for 0 or a value of
+ * 2^32 and more, and for a value below the current number -- going backwards would leave published slots
+ * reading "not yet". */
 enum fb_debug_knob {
     FB_DEBUG_DENSE_STEAL_POLLS = 1,
     FB_DEBUG_DENSE_OFFSET_SKEW = 2,
     FB_DEBUG_VIEW_DIRECT = 3,
     FB_DEBUG_ZEEK_DIRECT = 4,
-    FB_DEBUG_LEARN_HASH_MASK = 6 /* (5 stays unassigned: the refusal of an unknown knob is tested with it) */
+    FB_DEBUG_LEARN_HASH_MASK = 6, /* (5 stays unassigned: the refusal of an unknown knob is tested with it) */
+    FB_DEBUG_DNS_LAUNCH = 7
 };
 int fb_debug_set(fb_ctx* ctx, uint32_t knob, uint64_t value);
 /* Whether the fused parse + upsert calls (fb_process_seg_dev, fb_process_seg_async_dev) store the

@@ -43,7 +43,8 @@ def test_structs_and_constants_match_the_header(tmp_path):
             src.append('printf("%%zu\\n", offsetof(%s, %s));' % (struct, f))
             want.append(offsets[f])
     consts = {"FB_ABI_VERSION": N.FB_ABI_VERSION, "FB_DNS_MAX_NAMES": N.FB_DNS_MAX_NAMES, "FB_DNS_MAX_NAME": N.FB_DNS_MAX_NAME,
-              "FB_DNS_MAX_ADDRS": N.FB_DNS_MAX_ADDRS}
+              "FB_DNS_MAX_ADDRS": N.FB_DNS_MAX_ADDRS, "FB_DEBUG_DNS_LAUNCH": N.FB_DEBUG_DNS_LAUNCH,
+              "FB_DEBUG_LEARN_HASH_MASK": N.FB_DEBUG_LEARN_HASH_MASK}
     for c, v in consts.items():
         src.append('printf("%%llu\\n", (unsigned long long)%s);' % c)
         want.append(v)
@@ -58,6 +59,7 @@ def test_structs_and_constants_match_the_header(tmp_path):
     got = [int(x) for x in subprocess.run([str(tmp_path / "dnstrack")], check=True, capture_output=True, text=True).stdout.split()]
     assert got == want
     assert N.FB_ABI_VERSION == 4 and N.FB_DNS_EXPIRY_NS == 30 * 10**9
+    assert (N.FB_DEBUG_LEARN_HASH_MASK, N.FB_DEBUG_DNS_LAUNCH) == (6, 7)  # (5 stays unassigned)
     assert N.DNS_RESOLUTION_DTYPE.fields["ip"][0] == N.FB_IP_DTYPE
 
 
