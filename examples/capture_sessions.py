@@ -20,6 +20,9 @@ Zeek conn.log lines, the text of the reference's `format_sessions_zeek`, formatt
 `--history-on-device` the history strings of those lines never leave the GPU (the device store).
 `--learn-whitelist` prints the WhitelistsJSON text of the reference's `create_custom_whitelists`, the distinct
 endpoints and their representative sessions found by one pass on the GPU.
+`--l7` reads this machine's sockets and processes from /proc (flodbadd_amd.l7.snapshot_from_proc), hands the
+snapshot to the GPU and prints the process the L7 pass attributed each session to -- for the injected frames
+that is whatever listens on port 8080, if anything does.
 """
 import argparse
 import os
@@ -113,6 +116,8 @@ def main():
     ap.add_argument("--learn-whitelist", action="store_true",
                     help="print the custom whitelist learned from the sessions (create_custom_whitelists), its distinct "
                          "endpoints found on the GPU")
+    ap.add_argument("--l7", action="store_true",
+                    help="attribute the sessions to this machine's processes (a /proc socket snapshot, the L7 pass on the GPU)")
     a = ap.parse_args()
     times = [] if a.zeek else None
     try:
@@ -136,10 +141,22 @@ def main():
         t0 = time.perf_counter()
         r = cap.process_frames(frames, offs, ts=np.array(times, dtype=np.uint64) if a.zeek else None)
         t1 = time.perf_counter()
+        if a.l7:
+            from flodbadd_amd.l7 import snapshot_from_proc
+            snap = snapshot_from_proc()
+            installed = cap.set_l7_sockets(snap)
+            st = cap.update_l7()
+            print("L7 pass: %d of %d sockets have a known process; %d sessions looked up, %d exact, %d fuzzy"
+                  % (installed, len(snap.sockets), st["looked_up"], st["exact"], st["fuzzy"]))
         sessions = cap.get_sessions()  # before clearing: the reference's stop() clears them
         print("GPU parse + classify + session upsert: %d frames, %d session records in %.3f ms (host-inclusive)"
               % (n, len(r.records), (t1 - t0) * 1e3))
         print("Captured %d session(s)." % len(sessions))
+        for info in sessions if a.l7 else ():
+            if info.l7 is not None:
+                print("  %s:%d -> %s:%d  pid %d %s (%s)" % (info.session.src_ip, info.session.src_port, info.session.dst_ip,
+                                                           info.session.dst_port, info.l7.pid, info.l7.process_name,
+                                                           info.l7.username))
         if a.zeek:
             from flodbadd_amd.sessions import ZEEK_HEADER
             print(ZEEK_HEADER)

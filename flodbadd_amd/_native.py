@@ -183,6 +183,17 @@ DOM_STATS_DTYPE = np.dtype([(f, "<u8") for f in DOM_STATS_FIELDS] + [("reserved"
 assert (DNS_TRACK_CONFIG_DTYPE.itemsize, DNS_TRACK_STATS_DTYPE.itemsize, DNS_TRACK_INFO_DTYPE.itemsize,
         DNS_RESOLUTION_DTYPE.itemsize, FLOW_DOMAIN_DTYPE.itemsize, DOM_STATS_DTYPE.itemsize) == (32, 64, 64, 48, 8, 64)
 FB_DNS_IDS, FB_DNS_EXPIRY_NS, FB_DNS_MAX_NAMES, FB_DNS_NO_TIME = 65536, 30 * 10**9, (1 << 24) - 1, (1 << 64) - 1
+# the L7 pass (fb_set_l7_sockets / fb_flow_l7: src/l7.rs:208-500, 1020-1279)
+L7_SOCKET_DTYPE = np.dtype([("local_ip", "<u4", (4,)), ("remote_ip", "<u4", (4,)), ("local_port", "<u2"),
+                            ("remote_port", "<u2"), ("protocol", "u1"), ("local_family", "u1"),
+                            ("remote_family", "u1"), ("reserved0", "u1"), ("reserved1", "<u4"), ("process_id", "<u4")])
+L7_REC_DTYPE = np.dtype([("process_id", "<u4"), ("source", "u1"), ("tries", "u1"), ("reserved", "<u2")])
+L7_PARAMS_DTYPE = np.dtype([("max_retries", "<u4"), ("flags", "<u4"), ("reserved", "<u4", (2,))])
+L7_STATS_FIELDS = ["flows", "current", "looked_up", "exact", "fuzzy", "failed", "resolved", "changed"]
+L7_STATS_DTYPE = np.dtype([(f, "<u8") for f in L7_STATS_FIELDS])
+assert (L7_SOCKET_DTYPE.itemsize, L7_REC_DTYPE.itemsize, L7_PARAMS_DTYPE.itemsize, L7_STATS_DTYPE.itemsize) == (48, 8, 16, 64)
+FB_L7_NONE, FB_L7_EXACT, FB_L7_FUZZY, FB_L7_FAILED = 0, 1, 2, 3
+FB_L7_MAX_SOCKETS, FB_L7_DEFAULT_MAX_RETRIES = 1 << 22, 5
 
 FB_SEG_FRAMES = 64
 SEG_BYTES = FB_SEG_FRAMES * 56
@@ -393,6 +404,12 @@ GPU_SYMBOLS = [
     ("fb_dns_lookup_dev", _I, [_P, _P, _U64, _P, _P]),
     ("fb_flow_domains", _I, [_P, _U32, _P, _P]),
     ("fb_flow_domains_dev", _I, [_P, _P, _U64, _P]),
+    ("fb_l7_validate", _I, [_P, _U64]),
+    ("fb_set_l7_sockets", _I, [_P, _P, _U64]),
+    ("fb_flow_l7", _I, [_P, _P, _P, _P]),
+    ("fb_flow_l7_dev", _I, [_P, _P, _U64, _P]),
+    ("fb_l7_clear", _I, [_P]),
+    ("fb_l7_lookup_dev", _I, [_P, _P, _U64, _P, _P]),
 ]
 
 _gpu = None

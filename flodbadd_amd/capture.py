@@ -18,6 +18,7 @@ from . import _native as N
 from .sessions import (ZEEK_HEADER, Session, SessionFilter, WhitelistState, flows_to_sessions, ip_to_words, is_lan_ip,
                        pack_histories, views_to_sessions, words_to_ip)
 from .enrich import Blacklists
+from .l7 import ProcessInterner
 from .analyzer import SessionAnalyzer, anomaly_tag_of, default_service_codes, merge_criticality, path_cut
 from .whitelists import Whitelists, dedup_endpoints, is_session_in_whitelist, no_match_reason
 
@@ -140,6 +141,7 @@ class FlodbaddGpuCapture:
         self._wl_name = ""
         self._wl_installed = None   # (CompiledWhitelist, dns_resolutions) the device holds, or None
         self._wl_inputs = (None, None)  # the last update's dns_resolutions / process_names
+        self._wl_proc = None        # the process names that update decided its host-check flows with
         self._wl_host_ok = set()    # the Sessions the host resolved to Conforming (process names)
         self._wl_conformance = True
         # blacklist pass (src/blacklists.rs:456-731): the custom model, the name of every installed
@@ -165,6 +167,11 @@ class FlodbaddGpuCapture:
         self._dns_names = {}
         self._dns_res = (None, {})  # (writes, {ip: name id})
         self._dom_ran = False
+        # L7 pass (src/l7.rs; fb_flow_l7): the processes handed to the device so far, whether a snapshot is
+        # installed and whether a pass has run since the plane was last cleared
+        self._l7_procs = ProcessInterner()
+        self._l7_installed = False
+        self._l7_ran = False
         if self.track_dns:
             tc = np.zeros(1, dtype=N.DNS_TRACK_CONFIG_DTYPE)
             tc[0]["name_capacity"], tc[0]["addr_capacity"] = int(dns_name_capacity), int(dns_addr_capacity)
@@ -436,6 +443,71 @@ class FlodbaddGpuCapture:
         pairs = np.stack([ids["src_name_id"], ids["dst_name_id"]], axis=1)
         return pairs, self.dns_names(np.unique(pairs))
 
+    # ---- L7 pass (src/l7.rs:208-500, src/capture.rs:1414-1495; fb_flow_l7) --------------------------
+    def set_l7_sockets(self, snapshot):
+        """fb_set_l7_sockets: install an l7.SocketSnapshot -- what the reference's resolver reads from the OS
+        once per cycle -- for the passes that follow.  Returns the number of sockets installed (those with a
+        known process)."""
+        socks = snapshot.compile(self._l7_procs)
+        N.check(N.gpu_lib().fb_set_l7_sockets(self.ctx, N.ptr(socks) if len(socks) else None, len(socks)))
+        self._l7_installed = True
+        return len(socks)
+
+    def update_l7(self, max_retries=N.FB_L7_DEFAULT_MAX_RETRIES):
+        """One resolver cycle over every current session without a process (populate_l7 + resolve_l7_data);
+        returns the pass's counters (fb_l7_stats)."""
+        prm = np.zeros(1, dtype=N.L7_PARAMS_DTYPE)
+        prm[0]["max_retries"] = int(max_retries)
+        st = np.zeros(1, dtype=N.L7_STATS_DTYPE)
+        N.check(N.gpu_lib().fb_flow_l7(self.ctx, N.ptr(prm), N.ptr(st), None))
+        self._l7_ran = True
+        return stats_dict(st, N.L7_STATS_FIELDS)
+
+    def l7_records(self):
+        """fb_flow_l7_dev: the L7 element (L7_REC_DTYPE) of every table slot (index = fb_flow_rec.slot)."""
+        return self._plane("fb_flow_l7_dev", N.L7_REC_DTYPE)
+
+    def l7_lookup(self, keys):
+        """fb_l7_lookup_dev: the match of each key (records with fb_session_key's fields first, 40 bytes taken
+        of each) against the installed snapshot, as L7_REC_DTYPE records."""
+        keys = np.ascontiguousarray(keys)
+        raw = np.ascontiguousarray(keys.view(np.uint8).reshape(len(keys), keys.dtype.itemsize)[:, :40])
+        out = np.zeros(len(keys), dtype=N.L7_REC_DTYPE)
+        d_k, d_o = N.DeviceBuffer(max(raw.nbytes, 8)), N.DeviceBuffer(max(out.nbytes, 8))
+        if len(keys):
+            d_k.upload(raw)
+        N.check(N.gpu_lib().fb_l7_lookup_dev(self.ctx, d_k.ptr, len(keys), d_o.ptr, None))
+        return d_o.download(out, out.nbytes) if len(keys) else out
+
+    def clear_l7(self):
+        """fb_l7_clear: the snapshot is dropped and every session is unresolved again."""
+        N.check(N.gpu_lib().fb_l7_clear(self.ctx))
+        self._l7_installed = False
+        self._l7_ran = False
+
+    def _l7(self):
+        """views_to_sessions' `l7` (None while no L7 pass has run)."""
+        if not self._l7_ran:
+            return None
+        return self.l7_records()["process_id"], self._l7_procs.processes
+
+    def l7_process_names(self):
+        """{Session: process name} of the sessions the L7 pass has resolved: what the whitelist calls take as
+        process_names."""
+        if not (self._l7_ran and self.flow_capacity):
+            return {}
+        flows, ids = self.export_flows(SessionFilter.All), self.l7_records()["process_id"]
+        procs = self._l7_procs.processes
+        return {Session.from_key(r): procs[int(ids[int(r["slot"])])].process_name
+                for r in flows if int(ids[int(r["slot"])])}
+
+    def _process_names(self, process_names):
+        """The process names a whitelist call works with: the caller's when given, else the device's
+        attribution once an L7 pass has run, else none."""
+        if process_names is None and self._l7_ran:
+            return self.l7_process_names()
+        return process_names
+
     process = process_frames
 
     def process_frames_seg(self, frames, offsets, flow=True, ts=None):
@@ -688,7 +760,7 @@ class FlodbaddGpuCapture:
         else:
             histories = self.histories if self.track_history else None
         out = views_to_sessions(views, histories, self._bl_names, timed=self.timed,
-                                whitelist=whitelist, blacklist=blacklist, domains=self._domains())
+                                whitelist=whitelist, blacklist=blacklist, domains=self._domains(), l7=self._l7())
         for info in out if (overlay_host_ok and self._wl_host_ok) else ():  # the flows the pass left to the host
             if info.session in self._wl_host_ok and info.is_whitelisted is WhitelistState.NonConforming:
                 info.is_whitelisted = WhitelistState.Conforming
@@ -891,18 +963,24 @@ class FlodbaddGpuCapture:
 
     def update_sessions(self, now_ns=None, dns_resolutions=None, process_names=None):
         """update_sessions_internal's per-session passes in the reference's order (src/capture.rs:
-        1811-1882): the status (timed captures, when now_ns is given), the domain pass when the capture
+        1811-1882): the status (timed captures, when now_ns is given), the L7 pass when a socket snapshot is
+        installed (set_l7_sockets; src/capture.rs:1815-1822), the domain pass when the capture
         tracks DNS (src/capture.rs:1824-1848), the blacklist pass with its whitelist fallback, then the
         whitelist pass when a list is active -- with the tracked resolutions when the caller hands it
-        none.  Returns the calls' counters ({"status", "blacklist", "whitelist", "domains"}; None for a pass
-        that did not run).  With now_ns the passes stamp the sessions they change with it (set_pass_time)."""
+        none.  Returns the calls' counters ({"status", "blacklist", "whitelist", "domains"}, and "l7" on a capture
+        with a snapshot installed; None for a pass that did not run).  With now_ns the passes stamp the sessions
+        they change with it (set_pass_time)."""
         if now_ns is not None:
             self.set_pass_time(now_ns)
         age = self.update_sessions_status(now_ns) if (self.timed and now_ns is not None) else None
+        l7 = self.update_l7() if (self._l7_installed and self.flow_capacity) else None
         dom = self.update_domains() if (self.track_dns and self.flow_capacity) else None
         bl = self.update_blacklist(mark_whitelist=True)
         wl = self.update_whitelist(dns_resolutions, process_names)
-        return {"status": age, "blacklist": bl, "whitelist": wl, "domains": dom}
+        out = {"status": age, "blacklist": bl, "whitelist": wl, "domains": dom}
+        if l7 is not None:  # (only a capture with a snapshot installed has the entry)
+            out["l7"] = l7
+        return out
 
     # ---- anomaly pass (src/analyzer.rs; fb_flow_anomaly) ------------------------------------------
     def set_anomaly_model(self, forest, stats, thresholds, service_codes=None):
@@ -1095,9 +1173,11 @@ class FlodbaddGpuCapture:
         domains of dns_resolutions {ip: domain} expanded to addresses -- is installed if it is not yet
         and the table is evaluated in one pass.  process_names {Session: process name}: the flows the
         pass marks for a host check are then decided by the full endpoint_matches with their domain
-        and process.  A capture that tracks DNS uses its own resolutions when dns_resolutions is None.
+        and process.  A capture that tracks DNS uses its own resolutions when dns_resolutions is None, and one
+        whose L7 pass has run the device's process attribution when process_names is None.
         Returns the pass's counters, or None."""
         self._wl_inputs = (dns_resolutions, process_names)
+        self._wl_proc = None
         if not self._wl_name:
             return None
         if dns_resolutions is None and self.track_dns:  # the capture's own passive resolutions
@@ -1110,6 +1190,8 @@ class FlodbaddGpuCapture:
         comp = self._wl_installed[0]
         stats = self.whitelist_pass()
         self._wl_host_ok = set()
+        if stats["host_check"]:
+            process_names = self._wl_proc = self._process_names(process_names)
         if process_names and stats["host_check"]:
             marked = [Session.from_key(r) for r in self.export_whitelist_flows(N.FB_WL_HOST_CHECK)]
             for s, asn in zip(marked, self._dst_asn([s.dst_ip for s in marked])):
@@ -1143,7 +1225,7 @@ class FlodbaddGpuCapture:
         host_ok = self._wl_host_ok  # (the sessions the host resolved to Conforming are no exceptions)
         keep = (lambda v: np.array([Session.from_key(r) not in host_ok for r in v["rec"]], dtype=bool)) if host_ok else None
         out = self._view_sessions(N.FB_VIEW_WL_EXCEPTIONS, since, whitelist=False, blacklist=False, keep=keep)
-        proc = self._wl_inputs[1] or {}
+        proc = self._wl_proc or self._wl_inputs[1] or {}
         comp, dns = self._wl_installed  # (the resolutions the installed list was compiled with)
         for info, asn in zip(out, self._dst_asn([i.session.dst_ip for i in out])):
             s, a = info.session, asn or (None, None, None)
@@ -1176,8 +1258,10 @@ class FlodbaddGpuCapture:
         from every session of the table.  on_device: the distinct endpoints and their representative
         sessions are found by one pass on the device (learn_endpoints) instead of a download of every flow;
         the endpoints are then in table-slot order of their representatives, and the domains those the capture
-        tracked itself (track_dns) unless dns_resolutions is given.  The device holds no process names: with a
-        non-empty process_names the host path runs, whatever on_device says."""
+        tracked itself (track_dns) unless dns_resolutions is given.  The device's learning fingerprint holds no
+        process: with a non-empty process_names -- the caller's, or the L7 pass's attribution when the caller
+        gives none -- the host path runs, whatever on_device says."""
+        process_names = self._process_names(process_names)
         if on_device and not process_names:
             return self._learned(N.FB_VIEW_ALL, dns_resolutions).to_json()
         sessions = flows_to_sessions(self.export_flows(SessionFilter.All))
@@ -1199,6 +1283,7 @@ class FlodbaddGpuCapture:
             self.update_sessions(now_ns, dns_resolutions, process_names)
         else:
             self.update_whitelist(dns_resolutions, process_names)
+        process_names = self._process_names(process_names)
         cur = self._whitelists.whitelists.get("custom_whitelist")
         endpoints, extends = (list(cur.endpoints), cur.extends) if cur else ([], None)
         if not self._wl_name:

@@ -21,6 +21,7 @@
 
 #include "fb_host.h"
 #include "fb_internal.h"
+#include "fb_l7_index.h"
 #include "service_ports_default.inc"  // kDefaultServiceBitmap[8192] (generated at build time)
 
 using namespace fbk;
@@ -116,6 +117,14 @@ struct AnModel {
         return f;
     }
 };
+// The installed socket snapshot's index (fb_set_l7_sockets, fb_l7_index.h).
+struct L7Dev {
+    DevBuf<L7Pair> pairs;
+    DevBuf<L7Local> locals;
+    uint32_t n_pairs = 0, n_locals = 0;
+    bool active = false;
+    L7Tables tables() const { return {pairs, locals, n_pairs, n_locals}; }
+};
 // Enrichment tables (fb_set_asn_tables / fb_set_blacklists, fb_enrich.hip).
 struct EnrichDev {
     DevBuf<fb_asn_range> asn4, asn6;
@@ -130,7 +139,7 @@ struct EnrichDev {
 // every slot move.  Described once here; the functions below (plane_ensure .. plane_copy_out) are the
 // only code that allocates, moves, clears or frees one, so a new plane is one entry and its pass.
 enum PlaneId : uint32_t { kPlaneTime, kPlaneStatus, kPlaneWl, kPlaneBl, kPlaneAn, kPlaneMod, kPlaneDom, kPlaneHist,
-                          kPlanes };
+                          kPlaneL7, kPlanes };
 struct PlaneDesc {
     size_t elem;       // bytes per slot
     const char* name;  // in error text
@@ -152,10 +161,12 @@ static const PlaneDesc kPlaneDesc[kPlanes] = {
     {sizeof(fb_flow_domain), "domain plane", true, false, launch_plane_remap<uint2>},   // fb_domains.hip
     // the history store's {head, tail, len, reserved} (fb_histstore.hip): made by fb_hist_store_enable
     {sizeof(uint4), "history plane", true, false, launch_plane_remap<uint4>},
+    {sizeof(fb_l7_rec), "L7 plane", true, false, launch_plane_remap<uint2>},           // fb_l7.hip
 };
 static_assert(sizeof(fb_flow_domain) == sizeof(uint2), "one name-id pair per slot");
+static_assert(sizeof(fb_l7_rec) == sizeof(uint2), "one L7 element per slot");
 // the counter words of one synchronous pass over the table (pass_begin / pass_end)
-constexpr uint32_t kPassStatWords = std::max({kAgeStatWords, kWlCounters, kBlCounters, kAnCounters, kDomCounters});
+constexpr uint32_t kPassStatWords = std::max({kAgeStatWords, kWlCounters, kBlCounters, kAnCounters, kDomCounters, kL7Counters});
 
 // The flow table and the arrays sized by its capacity: made together (table_alloc), and replaced together by
 // a growth.  A plane is an array beside the table, one element per slot (kPlaneDesc); empty: not made yet.
@@ -244,6 +255,7 @@ struct fb_ctx {
     WlDev wl;
     AnModel an;     // anomaly pass (fb_set_anomaly_model / fb_flow_anomaly, fb_anomaly.hip)
     EnrichDev en;   // fb_set_asn_tables / fb_set_blacklists
+    L7Dev l7;       // L7 pass (fb_set_l7_sockets / fb_flow_l7, fb_l7.hip)
     // DNS tracker (fb_dns_track_enable, fb_dnstrack.hip); null: tracking is off (freed by fb_destroy)
     DnsTrack* dns = nullptr;
     // history store (fb_hist_store_enable, fb_histstore.hip); null: off (freed by fb_destroy).  hs_updates:
@@ -2226,6 +2238,95 @@ int fb_flow_domains(fb_ctx* c, uint32_t flags, fb_dom_stats* out, void* stream) 
 
 int fb_flow_domains_dev(fb_ctx* c, fb_flow_domain* d_out, uint64_t cap, void* stream) {
     return plane_copy_out(c, kPlaneDom, d_out, cap, stream);
+}
+
+// ---- L7 pass (fb_l7.hip) -----------------------------------------------------------------------------
+int fb_l7_validate(const fb_l7_socket* socks, uint64_t n) {
+    if (n && !socks) return set_err(FB_ERR_INVAL, "socks is NULL");
+    if (n > FB_L7_MAX_SOCKETS) return set_err(FB_ERR_INVAL, "%llu sockets: more than FB_L7_MAX_SOCKETS", (unsigned long long)n);
+    for (uint64_t i = 0; i < n; ++i)
+        if (!l7_socket_valid(socks[i]))
+            return set_err(FB_ERR_INVAL, "socket %llu: protocol 6 / 17, families 2 / 10 (remote: 0 for UDP), process_id >= 1, "
+                           "reserved fields 0, IPv4 addresses in word 0 alone", (unsigned long long)i);
+    return FB_OK;
+}
+
+int fb_set_l7_sockets(fb_ctx* c, const fb_l7_socket* socks, uint64_t n) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    int rc = fb_l7_validate(socks, n);
+    if (rc) return rc;
+    std::vector<L7Pair> pairs;
+    std::vector<L7Local> locals;
+    if (!build_l7_index(socks, n, pairs, locals)) return set_err(FB_ERR_INVAL, "socket snapshot");
+    DeviceGuard g(c->device);
+    L7Dev d;  // uploaded whole before it replaces the installed one
+    rc = upload_array(d.pairs, pairs.data(), pairs.size());
+    if (!rc) rc = upload_array(d.locals, locals.data(), locals.size());
+    if (rc) return rc;
+    d.n_pairs = (uint32_t)pairs.size();
+    d.n_locals = (uint32_t)locals.size();
+    d.active = true;
+    HIP_TRY(hipDeviceSynchronize());  // (no launch may still read the old one)
+    c->l7 = std::move(d);
+    return FB_OK;
+}
+
+int fb_l7_clear(fb_ctx* c) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    DeviceGuard g(c->device);
+    const int rc = drain_updates(c);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    c->l7 = L7Dev();
+    HIP_TRY(plane_zero(c, kPlaneL7, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return FB_OK;
+}
+
+// Synchronous, like fb_flow_domains: drains the updates in flight, one pass, the counters read back.
+int fb_flow_l7(fb_ctx* c, const fb_l7_params* params, fb_l7_stats* out, void* stream) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    if (!c->tb.slots) return set_err(FB_ERR_INVAL, "context was created without a flow table");
+    if (!c->l7.active) return set_err(FB_ERR_INVAL, "no socket snapshot is installed (fb_set_l7_sockets)");
+    fb_l7_params prm = {FB_L7_DEFAULT_MAX_RETRIES, 0u, {0u, 0u}};
+    if (params) prm = *params;
+    if (prm.max_retries > 255u || prm.flags || prm.reserved[0] || prm.reserved[1])
+        return set_err(FB_ERR_INVAL, "fb_l7_params: max_retries 0..255, flags and reserved words 0");
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = pass_begin(c, kL7Counters, s);
+    if (!rc) rc = plane_ensure(c, kPlaneL7, s);
+    unsigned long long* mod = nullptr;
+    if (!rc) rc = pass_stamps(c, s, &mod);
+    if (rc) return rc;
+    HIP_TRY(launch_flow_l7(c->l7.tables(), c->tb.slots, c->tb.cap, c->plane<uint8_t>(kPlaneStatus),
+                           c->plane<uint2>(kPlaneL7), prm.max_retries, c->d_pass_stats, s, mod, c->pass_time));
+    unsigned long long h[kL7Counters] = {};
+    rc = pass_end(c, h, kL7Counters, s);
+    if (rc) return rc;
+    if (out) {
+        out->flows = h[0];
+        out->current = h[1];
+        out->looked_up = h[2];
+        out->exact = h[3];
+        out->fuzzy = h[4];
+        out->failed = h[5];
+        out->resolved = h[6];
+        out->changed = h[7];
+    }
+    return FB_OK;
+}
+
+int fb_flow_l7_dev(fb_ctx* c, fb_l7_rec* d_out, uint64_t cap, void* stream) {
+    return plane_copy_out(c, kPlaneL7, d_out, cap, stream);
+}
+
+int fb_l7_lookup_dev(fb_ctx* c, const fb_session_key* d_keys, uint64_t n, fb_l7_rec* d_out, void* stream) {
+    if (!c || (n && (!d_keys || !d_out))) return set_err(FB_ERR_INVAL, "bad arguments");
+    if (!c->l7.active) return set_err(FB_ERR_INVAL, "no socket snapshot is installed (fb_set_l7_sockets)");
+    DeviceGuard g(c->device);
+    HIP_TRY(launch_l7_lookup(c->l7.tables(), d_keys, n, d_out, (hipStream_t)stream));
+    return FB_OK;
 }
 
 // ---- anomaly pass (fb_anomaly.hip) -------------------------------------------------------------------

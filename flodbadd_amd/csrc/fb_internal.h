@@ -1065,4 +1065,16 @@ hipError_t launch_flow_domains(const DnsTables& t, const FlowSlot* table, unsign
                                uint2* dom, unsigned long long* stats, hipStream_t s,
                                unsigned long long* mod = nullptr, unsigned long long now = 0ull);
 
+// L7 pass over the table (fb_l7.hip, fb_flow_l7): process attribution against the installed
+// socket snapshot's index (L7Tables, fb_l7_index.h).  l7: {process_id, source | tries << 8} per slot (zero: no
+// pass has seen the flow); status: the status plane or null (every flow current).  The call's device counters
+// are fb_l7_stats' eight fields.
+constexpr uint32_t kL7Counters = 8;
+struct L7Tables;
+hipError_t launch_flow_l7(const L7Tables& t, const FlowSlot* table, unsigned long long cap, const uint8_t* status,
+                          uint2* l7, uint32_t max_retries, unsigned long long* stats, hipStream_t s,
+                          unsigned long long* mod = nullptr, unsigned long long now = 0ull);
+hipError_t launch_l7_lookup(const L7Tables& t, const fb_session_key* keys, unsigned long long n, fb_l7_rec* out,
+                            hipStream_t s);
+
 }  // namespace fbk

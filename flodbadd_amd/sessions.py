@@ -190,6 +190,15 @@ class WhitelistState(enum.Enum):
         return WhitelistState.NonConforming if b & FB_WL_NONCONFORMING else WhitelistState.Unknown
 
 
+@dataclass(frozen=True)
+class SessionL7:
+    """SessionL7 (src/sessions.rs:30-37): the process the L7 pass attributed the session to."""
+    pid: int
+    process_name: str
+    process_path: str
+    username: str
+
+
 @dataclass
 class SessionInfo:
     """Subset of src/sessions.rs:40-61 that the GPU path owns.  is_local_* / is_self_* and
@@ -220,6 +229,21 @@ class SessionInfo:
     # on a capture that does not track DNS
     src_domain: Optional[str] = None
     dst_domain: Optional[str] = None
+
+    @property
+    def l7(self) -> Optional[SessionL7]:
+        """SessionInfo.l7 (src/sessions.rs:40-61), populate_l7 (src/capture.rs:1414-1495): the process the L7
+        pass matched the session to in the installed socket snapshot (FlodbaddGpuCapture.set_l7_sockets /
+        update_l7); None before it and for a session no socket matched.  A property like uid, not a field:
+        the field list, equality and the joins are what they were."""
+        return self.__dict__.get("_l7")
+
+    @l7.setter
+    def l7(self, value):
+        if value is None:
+            self.__dict__.pop("_l7", None)
+        else:
+            self.__dict__["_l7"] = value
 
     @property
     def uid(self):
@@ -342,11 +366,11 @@ def _per_record(plane, slots):
 
 
 def _join(flows, histories, times=None, status=None, whitelist=None, masks=None, bl_names=(), stamps=None,
-          dom_ids=None, dom_names=None):
+          dom_ids=None, dom_names=None, l7_ids=None, l7_procs=None):
     """The join behind flows_to_sessions and views_to_sessions, over per-record columns: row k of every column
     that is not None belongs to flows[k].  times: FLOW_TIME_DTYPE records; status / whitelist: bytes; masks:
     blacklist mask words of the lists bl_names; stamps: fb_flow_modified_dev stamps; dom_ids: (src, dst) name-id
-    pairs into dom_names."""
+    pairs into dom_names; l7_ids: the L7 plane's process ids into l7_procs ({process id: SessionL7})."""
     from .enrich import criticality_of  # (enrich imports this module)
     none = lambda v: None if int(v) == FB_SEEN_NONE else int(v)  # noqa: E731
     out = []
@@ -382,13 +406,15 @@ def _join(flows, histories, times=None, status=None, whitelist=None, masks=None,
             src, dst = int(dom_ids[k][0]), int(dom_ids[k][1])
             info.src_domain = dom_names[src] if src else None
             info.dst_domain = dom_names[dst] if dst else None
+        if l7_ids is not None and int(l7_ids[k]):
+            info.l7 = l7_procs[int(l7_ids[k])]
         out.append(info)
     out.sort(key=lambda i: i.session.sort_key())
     return out
 
 
 def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=None, blacklist=None, modified=None,
-                      domains=None):
+                      domains=None, l7=None):
     """fb_flow_rec records -> SessionInfo list sorted by the derived Ord of Session.  `histories`
     ({table slot: str}, FlodbaddGpuCapture.histories) supplies the history strings; the locality
     flags and dst_service come from fb_flow_rec.session_flags (stored at insert, src/packets.rs:
@@ -403,7 +429,9 @@ def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=
     fb_flow_blacklist_dev; the list names), decoded into SessionInfo.criticality.  `modified`: the stamp
     of every table slot (fb_flow_modified_dev); SessionInfo.last_modified_ns is the later of it and the
     flow's last_activity_ns.  `domains`: (the name-id pair of every table slot, fb_flow_domains_dev; {name id:
-    str}), decoded into SessionInfo.src_domain / dst_domain (id 0: None).  The per-slot arguments may be arrays
+    str}), decoded into SessionInfo.src_domain / dst_domain (id 0: None).  `l7`: (the process id of every table slot,
+    fb_flow_l7_dev's process_id column; {process id: SessionL7}), decoded into SessionInfo.l7 (id 0: None).  The
+    per-slot arguments may be arrays
     indexed by slot or {slot: value}.  Each argument's shape is decided here, once; the join itself (_join) runs
     over per-record columns."""
     if flows.dtype != FLOW_REC_DTYPE:
@@ -414,25 +442,28 @@ def flows_to_sessions(flows, histories=None, times=None, status=None, whitelist=
         times = times[np.array([row[s] for s in slots.tolist()], dtype=np.intp)]
     bl_masks, bl_names = blacklist if blacklist is not None else (None, ())
     dom_ids, dom_names = domains if domains is not None else (None, None)
+    l7_ids, l7_procs = l7 if l7 is not None else (None, None)
     return _join(flows, histories, times, _per_record(status, slots), _per_record(whitelist, slots),
-                 _per_record(bl_masks, slots), bl_names, _per_record(modified, slots), _per_record(dom_ids, slots), dom_names)
+                 _per_record(bl_masks, slots), bl_names, _per_record(modified, slots), _per_record(dom_ids, slots), dom_names,
+                 _per_record(l7_ids, slots), l7_procs)
 
 
 def views_to_sessions(views, histories=None, bl_names=None, timed=True, status=True, whitelist=True, blacklist=True,
-                      domains=None):
+                      domains=None, l7=None):
     """fb_flow_view records (fb_flow_export_view) -> the SessionInfo list flows_to_sessions builds from the
     separate exports: each view carries its flow's record, time record and per-slot plane elements -- a view row
     is the per-record join already -- so no other export is needed.  timed: the capture is timed (else the time
     records are zero and left out); status / whitelist / blacklist: decode that plane's element (a getter that
     does not decode a plane passes False here); bl_names: the list names of the blacklist masks; domains: as
-    flows_to_sessions takes it, joined by slot (the view record itself carries no domain)."""
+    flows_to_sessions takes it, joined by slot (the view record itself carries no domain); l7: likewise."""
     if views.dtype != FLOW_VIEW_DTYPE:
         raise TypeError("expected fb_flow_view records (FLOW_VIEW_DTYPE), got %s" % views.dtype)
     col = lambda f, on=True: views[f].tolist() if on else None  # noqa: E731
     dom_ids, dom_names = domains if domains is not None else (None, None)
+    l7_ids, l7_procs = l7 if l7 is not None else (None, None)
     return _join(views["rec"], histories, views["time"] if timed else None, col("status", status and timed),
                  col("wl_state", whitelist), col("bl_mask", blacklist), bl_names or [], col("stamp_ns"),
-                 _per_record(dom_ids, views["rec"]["slot"]), dom_names)
+                 _per_record(dom_ids, views["rec"]["slot"]), dom_names, _per_record(l7_ids, views["rec"]["slot"]), l7_procs)
 
 
 # ---- Zeek conn.log (format_sessions_zeek, src/sessions.rs:694-774; DESIGN.md 3.15) ------------------------
@@ -533,7 +564,7 @@ def filter_sessions(sessions: List[SessionInfo], flt: SessionFilter, lan_v6=()) 
     return list(sessions)
 
 
-__all__ = ["Protocol", "SessionFilter", "Session", "SessionPacketData", "SessionStats", "SessionStatus", "SessionInfo",
+__all__ = ["Protocol", "SessionFilter", "Session", "SessionPacketData", "SessionStats", "SessionStatus", "SessionInfo", "SessionL7",
            "WhitelistState",
            "ip_to_words", "words_to_ip", "service_name", "records_to_packets", "flows_to_sessions", "views_to_sessions",
            "filter_sessions", "ZEEK_FIELDS", "ZEEK_HEADER", "session_uid", "rust_ip_str", "format_sessions_zeek",

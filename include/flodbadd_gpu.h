@@ -790,6 +790,84 @@ int fb_flow_domains(fb_ctx* ctx, uint32_t flags, fb_dom_stats* out, void* stream
  * into DEVICE memory.  Asynchronous. */
 int fb_flow_domains_dev(fb_ctx* ctx, fb_flow_domain* d_out, uint64_t cap, void* stream);
 
+/* ---- L7 pass: process attribution against a socket snapshot (src/l7.rs:208-500, 1020-1279) ----------
+ * The host hands over what the reference's resolver task reads from the OS -- one ordered socket list
+ * with the owning process of each socket as an id of the caller's -- and one call of fb_flow_l7 is one
+ * cycle of that task over the sessions populate_l7 (src/capture.rs:1414-1495) would have queued: every
+ * CURRENT flow (fb_flow_domains' predicate) that has no process yet and is not marked failed is looked up.
+ *   exact  try_exact_match_from_index: a socket of the flow's protocol whose (local, remote) is (src, dst)
+ *          -- form A -- or (dst, src) -- form B --; UDP compares the local side only.  With src_port !=
+ *          dst_port the lowest-index form-A socket, else the lowest-index form-B socket; with equal ports
+ *          the lowest index of either.  Addresses compare as IpAddr: the family counts.
+ *   fuzzy  try_fuzzy_match, only after an exact miss: the lowest-index socket of the flow's protocol whose
+ *          local_port is src_port or dst_port and whose local address is 0.0.0.0, ::, src_ip or dst_ip
+ *          (any pairing of port and address).
+ * A socket none of whose pids is a known process makes the reference's scan continue
+ * (extract_l7_from_socket, src/l7.rs:1137-1199): the host leaves such sockets out.  A looked-up flow that
+ * matches nothing has `tries` raised by one (it stays at 255); once tries > max_retries it is
+ * FB_L7_FAILED and is not looked up again (src/l7.rs:456-470).  A flow that gets a process counts as
+ * `changed` and gets the pass time (fb_set_pass_time; src/capture.rs:1470-1474); the retry bookkeeping
+ * does not stamp.  A resolved flow is never looked up again (src/l7.rs:919-922, src/capture.rs:1452).
+ * The elements live in a per-slot plane made by the first pass; they follow their flows through a growth
+ * and a purge, and fb_flow_clear / fb_l7_clear zero them. */
+#define FB_L7_MAX_SOCKETS (1u << 22)
+#define FB_L7_DEFAULT_MAX_RETRIES 5u /* MAX_L7_RETRIES, src/l7.rs:83-89 */
+typedef struct fb_l7_socket {
+    uint32_t local_ip[4];  /*  0: session_key word order (IPv4: word 0, the others 0)                  */
+    uint32_t remote_ip[4]; /* 16                                                                       */
+    uint16_t local_port;   /* 32                                                                       */
+    uint16_t remote_port;  /* 34                                                                       */
+    uint8_t protocol;      /* 36: 6 / 17                                                               */
+    uint8_t local_family;  /* 37: 2 / 10                                                               */
+    uint8_t remote_family; /* 38: TCP 2 / 10; UDP 0 (2 / 10 accepted: the remote side is ignored)      */
+    uint8_t reserved0;     /* 39: 0                                                                    */
+    uint32_t reserved1;    /* 40: 0                                                                    */
+    uint32_t process_id;   /* 44: >= 1, the caller's id of the first pid found in its process table    */
+} fb_l7_socket; /* 48 bytes; the array is in the snapshot's list order, which is part of the input */
+enum fb_l7_source { FB_L7_NONE = 0, FB_L7_EXACT = 1, FB_L7_FUZZY = 2, FB_L7_FAILED = 3 };
+typedef struct fb_l7_rec {
+    uint32_t process_id; /* 0: 0 = no process                                                          */
+    uint8_t source;      /* 4: fb_l7_source                                                            */
+    uint8_t tries;       /* 5: lookups that matched nothing (0 once resolved)                          */
+    uint16_t reserved;   /* 6: 0                                                                       */
+} fb_l7_rec; /* 8 bytes */
+typedef struct fb_l7_params {
+    uint32_t max_retries; /* 0: 0..255; 255 never fails a flow                                         */
+    uint32_t flags;       /* 4: 0                                                                      */
+    uint32_t reserved[2]; /* 8: 0                                                                      */
+} fb_l7_params; /* 16 bytes; NULL = {FB_L7_DEFAULT_MAX_RETRIES, 0} */
+typedef struct fb_l7_stats {
+    uint64_t flows;     /*  0: flows in the table                                                      */
+    uint64_t current;   /*  8: of them current                                                         */
+    uint64_t looked_up; /* 16: of them without a process and not failed: the ones looked up            */
+    uint64_t exact;     /* 24: resolved by the exact phase in this call                                */
+    uint64_t fuzzy;     /* 32: resolved by the fuzzy phase in this call                                */
+    uint64_t failed;    /* 40: became FB_L7_FAILED in this call                                        */
+    uint64_t resolved;  /* 48: flows with a process after the call                                     */
+    uint64_t changed;   /* 56: exact + fuzzy: the flows stamped                                        */
+} fb_l7_stats; /* 64 bytes */
+/* The checks fb_set_l7_sockets makes, on the host alone: FB_ERR_INVAL for a bad protocol or family, a
+ * process_id of 0, a non-zero reserved field, an IPv4 address with a non-zero word 1-3, or
+ * n > FB_L7_MAX_SOCKETS. */
+int fb_l7_validate(const fb_l7_socket* socks, uint64_t n);
+/* Install a snapshot: the list is copied and indexed before the call returns (n == 0: a valid, empty
+ * snapshot).  FB_ERR_INVAL (fb_l7_validate) leaves the installed snapshot as it was.  Nothing is ever
+ * truncated.  Synchronous. */
+int fb_set_l7_sockets(fb_ctx* ctx, const fb_l7_socket* socks, uint64_t n);
+/* One pass.  Synchronous: waits for the updates in flight, like fb_flow_domains; timed and untimed
+ * contexts.  `params` may be NULL (the defaults), `out` may be NULL.  FB_ERR_INVAL without a flow table,
+ * without an installed snapshot, or for max_retries > 255 / non-zero flags or reserved words. */
+int fb_flow_l7(fb_ctx* ctx, const fb_l7_params* params, fb_l7_stats* out, void* stream);
+/* The element of every table slot (min(cap, capacity) records, slot order; zeros before the first pass)
+ * into DEVICE memory.  Asynchronous. */
+int fb_flow_l7_dev(fb_ctx* ctx, fb_l7_rec* d_out, uint64_t cap, void* stream);
+/* Drop the snapshot and zero the plane: every flow is unresolved again.  Synchronous. */
+int fb_l7_clear(fb_ctx* ctx);
+/* The match of n caller-supplied keys (session_key layout, as fb_flow_rec carries them) against the
+ * installed snapshot with the pass's own device function: d_out[i] = {process_id, FB_L7_EXACT / _FUZZY or
+ * 0, 0, 0}.  FB_ERR_INVAL without a snapshot.  DEVICE pointers, asynchronous. */
+int fb_l7_lookup_dev(fb_ctx* ctx, const fb_session_key* d_keys, uint64_t n, fb_l7_rec* d_out, void* stream);
+
 int fb_flow_count(fb_ctx* ctx, uint64_t* n_flows, void* stream); /* synchronous */
 /* Copy every flow (slot order) to host memory; *n = flows written (<= cap). Synchronous. */
 int fb_flow_export(fb_ctx* ctx, fb_flow_rec* out, uint64_t cap, uint64_t* n, void* stream);
