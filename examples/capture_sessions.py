@@ -22,7 +22,8 @@ Zeek conn.log lines, the text of the reference's `format_sessions_zeek`, formatt
 endpoints and their representative sessions found by one pass on the GPU.
 `--l7` reads this machine's sockets and processes from /proc (flodbadd_amd.l7.snapshot_from_proc), hands the
 snapshot to the GPU and prints the process the L7 pass attributed each session to -- for the injected frames
-that is whatever listens on port 8080, if anything does.
+that is whatever listens on port 8080, if anything does.  With `--l7 --learn-whitelist` the capture is made with
+processes_on_device=True: the learned endpoints carry their process names, and the learning stays on the GPU.
 """
 import argparse
 import os
@@ -136,7 +137,9 @@ def main():
     from flodbadd_amd.sessions import SessionFilter
     # (a conn.log line prints the session's start time and history: a timed capture that keeps the strings)
     cap = FlodbaddGpuCapture(0, session_filter=SessionFilter.All, flow_capacity=1 << 16, timed=a.zeek, track_history=a.zeek,
-                             history_on_device=a.zeek and a.history_on_device)
+                             history_on_device=a.zeek and a.history_on_device,
+                             # with both flags the learned endpoints carry their processes, found on the GPU too
+                             processes_on_device=a.l7 and a.learn_whitelist)
     try:
         t0 = time.perf_counter()
         r = cap.process_frames(frames, offs, ts=np.array(times, dtype=np.uint64) if a.zeek else None)

@@ -75,7 +75,12 @@ WL_ENDPOINT_DTYPE = np.dtype([("addr", "<u4", (4,)), ("family", "u1"), ("prefix"
                               ("owner_id", "<u4"), ("country_id", "<u4"), ("reserved2", "<u4")])
 WL_STATS_FIELDS = ["flows", "conforming", "nonconforming", "host_check", "changed"]
 WL_STATS_DTYPE = np.dtype([(f, "<u8") for f in WL_STATS_FIELDS] + [("reserved", "<u8", (3,))])
-assert WL_ENDPOINT_DTYPE.itemsize == 40 and WL_STATS_DTYPE.itemsize == 64
+# the same 40 bytes with the word at offset 36 under its second name: with FB_WL_HAS_PROCESS, the id of the
+# endpoint's lower-cased process name (fb_set_l7_process_names' match_id; 0: the device has none).  Rows travel as
+# WL_ENDPOINT_DTYPE, where the word is `reserved2`: rows.view(WL_ENDPOINT_PROC_DTYPE) names it.
+WL_ENDPOINT_PROC_DTYPE = np.dtype([(n, WL_ENDPOINT_DTYPE.fields[n][0]) if n != "reserved2" else ("process_match_id", "<u4")
+                                   for n in WL_ENDPOINT_DTYPE.names])
+assert WL_ENDPOINT_DTYPE.itemsize == 40 and WL_STATS_DTYPE.itemsize == 64 and WL_ENDPOINT_PROC_DTYPE.itemsize == 40
 FB_WL_NEVER = 0xFF
 FB_WL_HAS_PORT, FB_WL_HAS_ASN, FB_WL_HAS_OWNER, FB_WL_HAS_COUNTRY, FB_WL_HAS_DOMAIN, FB_WL_HAS_PROCESS = 1, 2, 4, 8, 16, 32
 FB_WL_CONFORMING, FB_WL_NONCONFORMING, FB_WL_HOST_CHECK, FB_WL_MASK_UNKNOWN = 1, 2, 4, 128
@@ -120,7 +125,14 @@ LEARNED_ENDPOINT_DTYPE = np.dtype([("dst_ip", "<u4", (4,)), ("rep_src_ip", "<u4"
                                    ("reserved2", "<u4", (3,))])
 LEARN_STATS_FIELDS = ["flows", "selected", "endpoints", "written", "rounds"]
 LEARN_STATS_DTYPE = np.dtype([(f, "<u8") for f in LEARN_STATS_FIELDS] + [("reserved", "<u8", (3,))])
+# the same 64 bytes with reserved2's first word under its second name: the flow's verbatim process name id
+# (fb_set_l7_process_names' name_id; 0: no process, and always 0 while no name table is installed)
+LEARNED_ENDPOINT_PROC_DTYPE = np.dtype([("dst_ip", "<u4", (4,)), ("rep_src_ip", "<u4", (4,)), ("dst_port", "<u2"),
+                                        ("rep_src_port", "<u2"), ("protocol", "u1"), ("family", "u1"), ("reserved", "<u2"),
+                                        ("dst_name_id", "<u4"), ("rep_slot", "<u4"), ("sessions", "<u4"),
+                                        ("proc_name_id", "<u4"), ("reserved3", "<u4", (2,))])
 assert LEARNED_ENDPOINT_DTYPE.itemsize == 64 and LEARN_STATS_DTYPE.itemsize == 64
+assert LEARNED_ENDPOINT_PROC_DTYPE.itemsize == 64
 # fb_zeek_stats (fb_format_zeek_dev: one Zeek conn.log line per fb_flow_view, formatted on the device), the
 # longest line without its history, and the kernel's thresholds (fb_zeek.hip), for the tests at them: records
 # per workgroup step, the step bytes staged in LDS, the history length the wave copies together
@@ -410,6 +422,7 @@ GPU_SYMBOLS = [
     ("fb_flow_l7_dev", _I, [_P, _P, _U64, _P]),
     ("fb_l7_clear", _I, [_P]),
     ("fb_l7_lookup_dev", _I, [_P, _P, _U64, _P, _P]),
+    ("fb_set_l7_process_names", _I, [_P, _P, _P, _U64]),
 ]
 
 _gpu = None

@@ -15,10 +15,10 @@ import ipaddress
 import numpy as np
 
 from . import _native as N
-from .sessions import (ZEEK_HEADER, Session, SessionFilter, WhitelistState, flows_to_sessions, ip_to_words, is_lan_ip,
+from .sessions import (ZEEK_HEADER, Protocol, Session, SessionFilter, WhitelistState, flows_to_sessions, ip_to_words, is_lan_ip,
                        pack_histories, views_to_sessions, words_to_ip)
 from .enrich import Blacklists
-from .l7 import ProcessInterner
+from .l7 import ProcessInterner, ProcessNameInterner
 from .analyzer import SessionAnalyzer, anomaly_tag_of, default_service_codes, merge_criticality, path_cut
 from .whitelists import Whitelists, dedup_endpoints, is_session_in_whitelist, no_match_reason
 
@@ -81,7 +81,7 @@ class FlodbaddGpuCapture:
     def __init__(self, device=0, session_filter=SessionFilter.GlobalOnly, flow_capacity=1 << 20,
                  service_bitmap=None, lan_v6=(), own_ips=(), max_batch_packets=1 << 20, track_history=False,
                  grow=True, timed=False, track_dns=False, dns_name_capacity=0, dns_addr_capacity=0, dns_hash_mask=0,
-                 history_on_device=False, history_block_capacity=0, history_max_blocks=0):
+                 history_on_device=False, history_block_capacity=0, history_max_blocks=0, processes_on_device=False):
         """timed: capture-time session state (FB_CFG_TIMED): every batch then comes with its frames'
         capture timestamps (`ts`, ns) and the sessions carry start / last / end times and the
         segment state with the reference's 5-s timeout (src/packets.rs:137-200).
@@ -94,7 +94,12 @@ class FlodbaddGpuCapture:
         (fb_hist_store_enable) instead of self.histories: every update is followed by one asynchronous append,
         the getters gather the strings of the flows they return, and export_zeek formats from the store with no
         history byte crossing the bus.  history_block_capacity / history_max_blocks: fb_hist_store_config (0:
-        the library's defaults)."""
+        the library's defaults).
+        processes_on_device: the whitelist check and the endpoint learning know the L7 pass's processes on the
+        device (fb_set_l7_process_names): set_l7_sockets uploads the names of its processes,
+        update_whitelist compiles the list with process ids and leaves only the flows a domain endpoint marks to
+        the host, and create_custom_whitelists(on_device=True) / augment_custom_whitelists learn endpoints with
+        their processes on the device.  A caller who passes process_names to those calls keeps the host path."""
         lib = N.gpu_lib()
         self._keep = []
         cfg = N.FbConfig()
@@ -170,6 +175,9 @@ class FlodbaddGpuCapture:
         # L7 pass (src/l7.rs; fb_flow_l7): the processes handed to the device so far, whether a snapshot is
         # installed and whether a pass has run since the plane was last cleared
         self._l7_procs = ProcessInterner()
+        self.processes_on_device = bool(processes_on_device)
+        self._proc_names = ProcessNameInterner()  # shared by the whitelist compiler and the name table's upload
+        self._wl_with_ids = False                 # the installed list was compiled with process ids
         self._l7_installed = False
         self._l7_ran = False
         if self.track_dns:
@@ -450,6 +458,9 @@ class FlodbaddGpuCapture:
         known process)."""
         socks = snapshot.compile(self._l7_procs)
         N.check(N.gpu_lib().fb_set_l7_sockets(self.ctx, N.ptr(socks) if len(socks) else None, len(socks)))
+        if self.processes_on_device:  # the names of every process handed over so far (the interners only grow)
+            m, v = self._proc_names.table(self._l7_procs.processes)
+            N.check(N.gpu_lib().fb_set_l7_process_names(self.ctx, N.ptr(m), N.ptr(v), len(m)))
         self._l7_installed = True
         return len(socks)
 
@@ -498,6 +509,19 @@ class FlodbaddGpuCapture:
             return {}
         flows, ids = self.export_flows(SessionFilter.All), self.l7_records()["process_id"]
         procs = self._l7_procs.processes
+        return {Session.from_key(r): procs[int(ids[int(r["slot"])])].process_name
+                for r in flows if int(ids[int(r["slot"])])}
+
+    def _device_processes(self, process_names):
+        """Does a whitelist call leave the processes to the device?  (processes_on_device, and the caller gave
+        no process_names of their own.)"""
+        return self.processes_on_device and process_names is None
+
+    def _slot_process_names(self, flows):
+        """{Session: process name} of the given fb_flow_rec records alone, from the L7 plane."""
+        if not (self._l7_ran and len(flows)):
+            return {}
+        ids, procs = self.l7_records()["process_id"], self._l7_procs.processes
         return {Session.from_key(r): procs[int(ids[int(r["slot"])])].process_name
                 for r in flows if int(ids[int(r["slot"])])}
 
@@ -1175,6 +1199,10 @@ class FlodbaddGpuCapture:
         pass marks for a host check are then decided by the full endpoint_matches with their domain
         and process.  A capture that tracks DNS uses its own resolutions when dns_resolutions is None, and one
         whose L7 pass has run the device's process attribution when process_names is None.
+        processes_on_device (and process_names None): the list is compiled with process ids, the pass decides
+        the process endpoints itself -- and stamps what it changes --, no {Session: name} dictionary is
+        downloaded, and only the flows a domain endpoint marks go through the host loop, with the processes
+        of just those flows.
         Returns the pass's counters, or None."""
         self._wl_inputs = (dns_resolutions, process_names)
         self._wl_proc = None
@@ -1183,17 +1211,29 @@ class FlodbaddGpuCapture:
         if dns_resolutions is None and self.track_dns:  # the capture's own passive resolutions
             dns_resolutions = {str(ip): name for ip, name in self.dns_resolutions().items()}
         want = dict(dns_resolutions or {})
-        if self._wl_installed is None or self._wl_installed[1] != want:
-            comp = self._whitelists.compile(self._wl_name, self._asn_records, want)
+        on_dev = self._device_processes(process_names)
+        if self._wl_installed is None or self._wl_installed[1] != want or self._wl_with_ids != on_dev:
+            comp = self._whitelists.compile(self._wl_name, self._asn_records, want,
+                                            process_ids=self._proc_names if on_dev else None)
             self.install_whitelist(comp)
             self._wl_installed = (comp, want)
+            self._wl_with_ids = on_dev
         comp = self._wl_installed[0]
         stats = self.whitelist_pass()
         self._wl_host_ok = set()
-        if stats["host_check"]:
-            process_names = self._wl_proc = self._process_names(process_names)
-        if process_names and stats["host_check"]:
-            marked = [Session.from_key(r) for r in self.export_whitelist_flows(N.FB_WL_HOST_CHECK)]
+        marked = None
+        if stats["host_check"] and on_dev:  # domain keys only: the processes of just those flows
+            marked = self.export_whitelist_flows(N.FB_WL_HOST_CHECK)
+            process_names = self._slot_process_names(marked)
+            host_loop = bool(process_names)
+        else:
+            if stats["host_check"]:
+                process_names = self._wl_proc = self._process_names(process_names)
+            host_loop = bool(process_names) and bool(stats["host_check"])
+        if host_loop:
+            if marked is None:
+                marked = self.export_whitelist_flows(N.FB_WL_HOST_CHECK)
+            marked = [Session.from_key(r) for r in marked]
             for s, asn in zip(marked, self._dst_asn([s.dst_ip for s in marked])):
                 a = asn or (None, None, None)
                 if is_session_in_whitelist(comp.endpoints, comp.name, want.get(str(s.dst_ip)), str(s.dst_ip), s.dst_port,
@@ -1226,6 +1266,8 @@ class FlodbaddGpuCapture:
         keep = (lambda v: np.array([Session.from_key(r) not in host_ok for r in v["rec"]], dtype=bool)) if host_ok else None
         out = self._view_sessions(N.FB_VIEW_WL_EXCEPTIONS, since, whitelist=False, blacklist=False, keep=keep)
         proc = self._wl_proc or self._wl_inputs[1] or {}
+        if self._wl_with_ids:  # the processes the device decided with: the returned sessions' own l7
+            proc = {i.session: i.l7.process_name for i in out if i.l7 is not None}
         comp, dns = self._wl_installed  # (the resolutions the installed list was compiled with)
         for info, asn in zip(out, self._dst_asn([i.session.dst_ip for i in out])):
             s, a = info.session, asn or (None, None, None)
@@ -1235,16 +1277,24 @@ class FlodbaddGpuCapture:
                                                     s.dst_port, s.protocol.name, a[0], a[1], a[2], proc.get(s))
         return out
 
-    def _learned(self, view_set, dns_resolutions=None):
+    def _learned(self, view_set, dns_resolutions=None, processes=False):
         """The custom_whitelist model learned on the device from the flows of view_set (learn_endpoints,
         Whitelists.from_learned).  A capture that tracks DNS brings the flows' domains forward first
         (update_domains: dst_domain as the reference's sessions carry it); dns_resolutions {ip: domain}, when
-        given, stands for dst_domain instead, as on the host path."""
+        given, stands for dst_domain instead, as on the host path.  processes (processes_on_device): the records
+        carry the flows' process name ids, and the endpoints come in the order of their representative sessions
+        -- the order new_from_sessions meets them in a sorted session list, so the document is the host path's."""
         if self.track_dns and dns_resolutions is None:
             self.update_domains()
         recs, _ = self.learn_endpoints(view_set)
         names = self.dns_names(recs["dst_name_id"]) if (self.track_dns and dns_resolutions is None) else {}
-        w = Whitelists.from_learned(recs, names)
+        if processes:
+            def rep_key(r):  # the representative session's place in Session's derived Ord
+                fam = int(r["family"])
+                return Session(Protocol(int(r["protocol"])), words_to_ip(r["rep_src_ip"], fam), int(r["rep_src_port"]),
+                               words_to_ip(r["dst_ip"], fam), int(r["dst_port"])).sort_key()
+            recs = recs[sorted(range(len(recs)), key=lambda k: rep_key(recs[k]))]
+        w = Whitelists.from_learned(recs, names, self._proc_names.names if processes else None)
         if dns_resolutions is not None:
             info = w.whitelists["custom_whitelist"]
             for ep in info.endpoints:
@@ -1258,9 +1308,12 @@ class FlodbaddGpuCapture:
         from every session of the table.  on_device: the distinct endpoints and their representative
         sessions are found by one pass on the device (learn_endpoints) instead of a download of every flow;
         the endpoints are then in table-slot order of their representatives, and the domains those the capture
-        tracked itself (track_dns) unless dns_resolutions is given.  The device's learning fingerprint holds no
-        process: with a non-empty process_names -- the caller's, or the L7 pass's attribution when the caller
-        gives none -- the host path runs, whatever on_device says."""
+        tracked itself (track_dns) unless dns_resolutions is given.  With processes_on_device (and no
+        process_names from the caller) the device's fingerprint holds the process and the document is the host
+        path's, endpoint for endpoint.  Otherwise it holds none: with a non-empty process_names -- the caller's,
+        or the L7 pass's attribution when the caller gives none -- the host path runs, whatever on_device says."""
+        if on_device and self._device_processes(process_names):
+            return self._learned(N.FB_VIEW_ALL, dns_resolutions, processes=True).to_json()
         process_names = self._process_names(process_names)
         if on_device and not process_names:
             return self._learned(N.FB_VIEW_ALL, dns_resolutions).to_json()
@@ -1283,11 +1336,21 @@ class FlodbaddGpuCapture:
             self.update_sessions(now_ns, dns_resolutions, process_names)
         else:
             self.update_whitelist(dns_resolutions, process_names)
-        process_names = self._process_names(process_names)
+        on_dev = self._device_processes(process_names)
+        if not on_dev:
+            process_names = self._process_names(process_names)
         cur = self._whitelists.whitelists.get("custom_whitelist")
         endpoints, extends = (list(cur.endpoints), cur.extends) if cur else ([], None)
         if not self._wl_name:
             learned = []
+        elif on_dev and not self._wl_host_ok:  # (a session the host accepted is no exception: then its list decides)
+            learned = self._learned(N.FB_VIEW_WL_EXCEPTIONS, dns_resolutions, processes=True)
+        elif on_dev:
+            dns = dns_resolutions
+            if dns is None and self.track_dns:
+                dns = {str(ip): name for ip, name in self.dns_resolutions().items()}
+            exc = self.get_whitelist_exceptions()
+            learned = Whitelists.new_from_sessions(exc, dns, {i.session: i.l7.process_name for i in exc if i.l7 is not None})
         elif process_names:
             dns = dns_resolutions
             if dns is None and self.track_dns:

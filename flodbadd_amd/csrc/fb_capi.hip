@@ -92,10 +92,19 @@ struct Staging {
 // The installed whitelist's index (fb_set_whitelist, fb_whitelist.hip).
 struct WlDev {
     DevBuf<uint32_t> a4, k4, k6, gkey, gbeg, owner, country;
+    DevBuf<unsigned long long> kp4, kp6;  // with_proc: instead of k4 / k6
     DevBuf<uint4> a6;
     DevBuf<WlRule> rules;
     uint32_t n4 = 0, n6 = 0, ng = 0, nr = 0, records = 0;
-    WlTables tables() const { return {a4, k4, a6, k6, gkey, gbeg, rules, owner, country, n4, n6, ng, nr, records}; }
+    bool with_proc = false;  // WlIndex::with_proc: the process-aware instances run
+    WlTables tables() const {
+        return {a4, k4, a6, k6, gkey, gbeg, rules, owner, country, kp4, kp6, n4, n6, ng, nr, records};
+    }
+};
+// The names of the L7 plane's process ids (fb_set_l7_process_names); n 0: no table.
+struct L7Names {
+    DevBuf<uint32_t> match_id, name_id;
+    uint32_t n = 0;
 };
 // The installed anomaly model (fb_set_anomaly_model, fb_anomaly.hip).
 struct AnModel {
@@ -256,6 +265,10 @@ struct fb_ctx {
     AnModel an;     // anomaly pass (fb_set_anomaly_model / fb_flow_anomaly, fb_anomaly.hip)
     EnrichDev en;   // fb_set_asn_tables / fb_set_blacklists
     L7Dev l7;       // L7 pass (fb_set_l7_sockets / fb_flow_l7, fb_l7.hip)
+    L7Names l7_names;  // fb_set_l7_process_names: what the whitelist pass and the endpoint learning read processes by
+    WlProcNames proc_names() const {
+        return {plane<fb_l7_rec>(kPlaneL7), l7_names.match_id, l7_names.name_id, l7_names.n};
+    }
     // DNS tracker (fb_dns_track_enable, fb_dnstrack.hip); null: tracking is off (freed by fb_destroy)
     DnsTrack* dns = nullptr;
     // history store (fb_hist_store_enable, fb_histstore.hip); null: off (freed by fb_destroy).  hs_updates:
@@ -1989,6 +2002,8 @@ int fb_set_whitelist(fb_ctx* c, const fb_wl_endpoint* eps, uint64_t n, const uin
     if (!rc) rc = upload_array(w.k4, ix.k4.data(), ix.k4.size());
     if (!rc) rc = upload_array(w.a6, ix.a6.data(), ix.a6.size());
     if (!rc) rc = upload_array(w.k6, ix.k6.data(), ix.k6.size());
+    if (!rc) rc = upload_array(w.kp4, ix.kp4.data(), ix.kp4.size());
+    if (!rc) rc = upload_array(w.kp6, ix.kp6.data(), ix.kp6.size());
     if (!rc) rc = upload_array(w.gkey, ix.gkey.data(), ix.gkey.size());
     if (!rc) rc = upload_array(w.gbeg, ix.gbeg.data(), ix.gkey.empty() ? 0 : ix.gbeg.size());
     if (!rc) rc = upload_array(w.rules, ix.rules.data(), ix.rules.size());
@@ -2000,6 +2015,7 @@ int fb_set_whitelist(fb_ctx* c, const fb_wl_endpoint* eps, uint64_t n, const uin
     w.ng = (uint32_t)ix.gkey.size();
     w.nr = (uint32_t)ix.rules.size();
     w.records = n_records;
+    w.with_proc = ix.with_proc;
     c->wl = std::move(w);
     c->wl_active = true;
     return FB_OK;
@@ -2029,8 +2045,10 @@ int fb_flow_whitelist(fb_ctx* c, uint32_t flags, fb_wl_stats* out, void* stream)
     unsigned long long* mod = nullptr;
     if (!rc) rc = pass_stamps(c, s, &mod);
     if (rc) return rc;
+    // (whether a process endpoint with an id matches or asks for the host is decided here, by the name table
+    // installed now: fb_set_whitelist and fb_set_l7_process_names may come in either order)
     HIP_TRY(launch_flow_whitelist(c->wl.tables(), c->en.tables(), c->d_cfg, c->tb.slots, c->tb.cap, c->plane<uint8_t>(kPlaneWl),
-                                  c->d_pass_stats, s, mod, c->pass_time));
+                                  c->d_pass_stats, s, mod, c->pass_time, c->wl.with_proc, c->proc_names()));
     unsigned long long h[kWlCounters] = {};
     rc = pass_end(c, h, kWlCounters, s);
     if (rc) return rc;
@@ -2268,6 +2286,31 @@ int fb_set_l7_sockets(fb_ctx* c, const fb_l7_socket* socks, uint64_t n) {
     d.active = true;
     HIP_TRY(hipDeviceSynchronize());  // (no launch may still read the old one)
     c->l7 = std::move(d);
+    return FB_OK;
+}
+
+// The arrays are checked and uploaded whole before they replace the installed table.
+int fb_set_l7_process_names(fb_ctx* c, const uint32_t* match_id, const uint32_t* name_id, uint64_t n) {
+    if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
+    if (n && (!match_id || !name_id)) return set_err(FB_ERR_INVAL, "match_id / name_id is NULL");
+    if (n > 0xFFFFFFFFull) return set_err(FB_ERR_INVAL, "%llu process ids: more than 32 bits hold", (unsigned long long)n);
+    for (uint64_t p = 1; p < n; ++p)
+        if (match_id[p] == 0u || name_id[p] == 0u)
+            return set_err(FB_ERR_INVAL, "process %llu: match_id and name_id are ids >= 1", (unsigned long long)p);
+    DeviceGuard g(c->device);
+    L7Names d;
+    if (n) {
+        std::vector<uint32_t> m(match_id, match_id + n), v(name_id, name_id + n);
+        m[0] = v[0] = 0u;  // "no process"
+        int rc = upload_array(d.match_id, m.data(), m.size());
+        if (!rc) rc = upload_array(d.name_id, v.data(), v.size());
+        if (rc) return rc;
+        d.n = (uint32_t)n;
+    }
+    const int rc = drain_updates(c);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (no launch may still read the old one)
+    c->l7_names = std::move(d);
     return FB_OK;
 }
 
@@ -2550,7 +2593,7 @@ int fb_flow_learn_endpoints_dev(fb_ctx* c, const fb_view_query* q, fb_learned_en
     rc = drain_updates(c);
     if (!rc && q->filter != FB_FILTER_ALL) rc = upload_cfg(c, s);  // the LAN configuration as of now
     if (rc) return rc;
-    return learn_endpoints(view_args(c, q), c->plane<uint2>(kPlaneDom), c->learn_hash_mask, c->learn_slots,
+    return learn_endpoints(view_args(c, q), c->plane<uint2>(kPlaneDom), c->proc_names(), c->learn_hash_mask, c->learn_slots,
                            c->learn_index, d_out, cap, (unsigned long long*)d_n, out, s);
 }
 

@@ -9,6 +9,7 @@
 
 #include "../../include/flodbadd_gpu.h"
 #include "fb_dns_hash.h"
+#include "fb_wl_match.h"
 
 namespace fbk {
 
@@ -846,54 +847,18 @@ hipError_t launch_flow_export_anomalous(const FlowSlot* table, const fb_an_rec* 
                                         unsigned long long out_cap, unsigned long long* d_n, const FlowTime* plane,
                                         hipStream_t s);
 
-// Whitelist conformance (fb_whitelist.hip, fb_flow_whitelist).  fb_set_whitelist compiles the endpoint
-// list into three structures (build_whitelist_index):
-//   exact   the endpoints that match by one address: per family the addresses ascending and, beside
-//           each, its (protocol | any, port | any) key, ascending inside an address's run (deduplicated);
-//   rules   every other endpoint the device can match -- nets, AS-only, match-all -- sorted by the same key;
-//   groups  the distinct keys of the rules and of the host-check endpoints (domain / process), ascending:
-//           gkey[g] (kWlGroupHostCheck: a domain / process endpoint has this key), the group's rules
-//           rules[gbeg[g] .. gbeg[g + 1]).
-// A flow (protocol P, destination port Q) can only match the endpoints of its four keys wl_key(0 | P,
-// none | Q): the kernel looks each up (one address search, four group searches).
-__host__ __device__ inline uint32_t wl_key(uint32_t proto, bool has_port, uint32_t port) {
-    return proto << 17 | (has_port ? 1u << 16 | port : 0u);
-}
-constexpr uint32_t kWlGroupHostCheck = 0x80000000u;
-struct WlRule {                   // 48 B: three 16-B LDS reads, and a net test of xor / and / or per word
-    uint32_t a[4];                // family 2 / 10: the network (host bits cleared); family 0: as_number,
-                                  // owner_id, country_id, 0
-    uint32_t m[4];                // the prefix mask (IPv4: word 0, the other words 0 like the key's)
-    uint32_t kind;                // family | FB_WL_HAS_ASN/OWNER/COUNTRY << 16 (family 0 only)
-    uint32_t pad[3];
-};
-static_assert(sizeof(WlRule) == 48, "whitelist rule is 48 B");
-// Staged in LDS by every workgroup when both fit (28 KiB: five 256-thread workgroups per CU), else read
-// from global memory.
+// Whitelist conformance (fb_whitelist.hip, fb_flow_whitelist).  The index fb_set_whitelist compiles the
+// endpoint list into, and the evaluation of one flow against it, are fb_wl_match.h's (shared with host
+// programs).  Staged in LDS by every workgroup when groups and rules both fit (28 KiB: five 256-thread
+// workgroups per CU), else read from global memory.
 constexpr uint32_t kWlLdsRules = 512, kWlLdsGroups = 512;
 constexpr uint32_t kWlCounters = 5;  // fb_wl_stats' first five fields
-struct WlTables {
-    const uint32_t* a4;   // [n4] exact IPv4 addresses
-    const uint32_t* k4;   // [n4] their keys
-    const uint4* a6;      // [n6] exact IPv6 addresses (session_key word order)
-    const uint32_t* k6;
-    const uint32_t* gkey; // [ng]
-    const uint32_t* gbeg; // [ng + 1]
-    const WlRule* rules;  // [nr]
-    const uint32_t* rec_owner;    // [n_records]
-    const uint32_t* rec_country;
-    uint32_t n4, n6, ng, nr, n_records;
-};
-struct WlIndex {  // host form
-    std::vector<uint32_t> a4, k4, k6, gkey, gbeg;
-    std::vector<uint4> a6;
-    std::vector<WlRule> rules;
-};
-// false: an endpoint with a bad family / prefix / protocol, or more than FB_WL_MAX_EXACT / _OTHER
-bool build_whitelist_index(const fb_wl_endpoint* eps, uint64_t n, WlIndex& ix);
+// with_proc: the list has process ids (WlIndex::with_proc) -- the process-aware instances run, reading the
+// flow's process through `names` (plane null: no L7 pass yet; n 0: no name table)
 hipError_t launch_flow_whitelist(const WlTables& w, const EnrichTables& t, const DevConfig* cfg, const FlowSlot* table,
                                  unsigned long long cap, uint8_t* state, unsigned long long* stats, hipStream_t s,
-                                 unsigned long long* mod = nullptr, unsigned long long now = 0ull);
+                                 unsigned long long* mod = nullptr, unsigned long long now = 0ull,
+                                 bool with_proc = false, const WlProcNames& names = WlProcNames());
 hipError_t launch_flow_export_whitelist(const FlowSlot* table, const uint8_t* state, unsigned long long cap,
                                         uint32_t state_mask, fb_flow_rec* out, unsigned long long out_cap,
                                         unsigned long long* d_n, const FlowTime* plane, hipStream_t s);
@@ -954,14 +919,15 @@ hipError_t launch_flow_view(const ViewArgs& a, fb_flow_view* out, unsigned long 
 
 // Endpoint learning (fb_learn.hip, fb_flow_learn_endpoints_dev): the distinct (dst_ip, family,
 // dst_port, protocol, dst name id) of the flows the query selects, each with its least session.  dom: the
-// domain plane or null (every id 0).  hash_mask: FB_DEBUG_LEARN_HASH_MASK.  per_slot / index: the context's
+// domain plane or null (every id 0).  names: with a process-name table (n != 0) the fingerprint gains the flow's
+// verbatim process name id; without one the instances of before run.  hash_mask: FB_DEBUG_LEARN_HASH_MASK.  per_slot / index: the context's
 // scratch for the per-table-slot arrays and for the endpoint index (sized once the selected flows are
 // counted).  Synchronous; returns an fb_err.
 static_assert(sizeof(fb_learned_endpoint) == 64 && sizeof(fb_learn_stats) == 64, "learn ABI");
 class StreamScratch;
-int learn_endpoints(const ViewArgs& a, const uint2* dom, unsigned long long hash_mask, StreamScratch& per_slot,
-                    StreamScratch& index, fb_learned_endpoint* out, unsigned long long out_cap, unsigned long long* d_n,
-                    fb_learn_stats* stats, hipStream_t s);
+int learn_endpoints(const ViewArgs& a, const uint2* dom, const WlProcNames& names, unsigned long long hash_mask,
+                    StreamScratch& per_slot, StreamScratch& index, fb_learned_endpoint* out, unsigned long long out_cap,
+                    unsigned long long* d_n, fb_learn_stats* stats, hipStream_t s);
 
 // Zeek export (fb_zeek.hip, fb_format_zeek_dev): n > 0 view records, the history blob (null: none) and its
 // per-slot offsets, the text buffer and its capacity, line_off[n + 1] and the stats (zeroed by the caller).

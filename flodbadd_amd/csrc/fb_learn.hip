@@ -3,8 +3,9 @@
 // (src/whitelists.rs:103-177) builds a custom whitelist from.  DESIGN.md 3.17 has the argument; one call is
 //
 //   select     one sweep: view_take (the view export's predicate) per occupied slot; a selected slot gets
-//              the 64-bit tag of its fingerprint -- (dst_ip, family, dst_port, protocol, dst name id) --,
-//              the others tag 0; the counts the index is sized by
+//              the 64-bit tag of its fingerprint -- (dst_ip, family, dst_port, protocol, dst name id) and, while
+//              a process-name table is installed (kProc), the flow's verbatim process name id
+//              --, the others tag 0; the counts the index is sized by
 //   insert     every selected flow -> an entry of the endpoint index (open addressing over the tags),
 //              concurrent inserts in ROUNDS exactly as fb_dnstrack.hip's: claim by atomicCAS on the tag, the
 //              winner writes the key and then the number of this launch as the slot's stamp, and a flow that
@@ -34,7 +35,11 @@ namespace {
 
 constexpr unsigned long long kTagUsed = 1ull << 63;
 constexpr uint32_t kEntNone = ~0u - 1u, kEntUnresolved = ~0u;  // LearnSlots::ent
-constexpr uint32_t kFpWords = 6;                               // fingerprint words
+// fingerprint words: six, or -- kProc -- eight (the process name id and a zero word: the tag hashes pairs)
+template <bool kProc>
+struct Fp {
+    static constexpr uint32_t kWords = kProc ? 8u : 6u;
+};
 constexpr unsigned long long kMinIndexSlots = 64;
 // the call's counter words
 enum Ctr : uint32_t { cFlows, cSelected, cSelectedV6, cUnresolved, cExhausted, kCtrWords = 8 };
@@ -49,7 +54,7 @@ struct LearnIndex {
     unsigned long long* tag;  // [slots] 0: empty
     uint32_t* stamp;          // [slots] the launch that claimed the slot (0: none)
     uint32_t* cnt;            // [slots] flows resolved to it
-    uint32_t* key;            // [slots * kFpWords]
+    uint32_t* key;            // [slots * fingerprint words]
     unsigned long long* min;  // [slots * 3] the least order words of the entry's flows (~0: none yet)
     unsigned long long slots; // a power of two
 };
@@ -57,12 +62,17 @@ struct LearnIndex {
 __device__ __forceinline__ unsigned long long ld64(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// The fingerprint of a slot: the four destination words, dst_port | protocol << 16 | family << 24, the name id.
-__device__ __forceinline__ void fingerprint(const FlowSlot& t, uint32_t name_id, uint32_t (&f)[kFpWords]) {
+// The fingerprint of a slot: the four destination words, dst_port | protocol << 16 | family << 24, the name id
+// -- and, eight words, the process name id.
+template <uint32_t kFpWords>
+__device__ __forceinline__ void fingerprint(const FlowSlot& t, uint32_t name_id, uint32_t proc_name_id,
+                                            uint32_t (&f)[kFpWords]) {
     f[0] = t.key[4], f[1] = t.key[5], f[2] = t.key[6], f[3] = t.key[7];
     f[4] = (t.key[8] >> 16) | (t.key[9] & 0xFFFFu) << 16;
     f[5] = name_id;
+    if constexpr (kFpWords > 6u) f[6] = proc_name_id, f[7] = 0u;
 }
+template <uint32_t kFpWords>
 __device__ __forceinline__ unsigned long long fp_tag(const uint32_t (&f)[kFpWords], unsigned long long hash_mask) {
     unsigned long long h = 0x9E3779B97F4A7C15ull;
 #pragma unroll
@@ -89,8 +99,11 @@ __device__ __forceinline__ void order_words(const FlowSlot& t, unsigned long lon
     }
 }
 
-__global__ __launch_bounds__(256) void k_learn_select(const ViewArgs a, const uint2* dom, unsigned long long hash_mask,
-                                                      const LearnSlots sl, unsigned long long* ctr) {
+template <bool kProc>
+__global__ __launch_bounds__(256) void k_learn_select(const ViewArgs a, const uint2* dom, const WlProcNames P,
+                                                      unsigned long long hash_mask, const LearnSlots sl,
+                                                      unsigned long long* ctr) {
+    constexpr uint32_t kFpWords = Fp<kProc>::kWords;
     PassCounters<3> pc;
     const unsigned long long stride = (unsigned long long)gridDim.x * 256u;
     for (unsigned long long base = (unsigned long long)blockIdx.x * 256u; base < a.cap; base += stride) {
@@ -101,7 +114,7 @@ __global__ __launch_bounds__(256) void k_learn_select(const ViewArgs a, const ui
         bool v6 = false;
         if (taken) {
             uint32_t f[kFpWords];
-            fingerprint(a.table[i], dom ? dom[i].y : 0u, f);
+            fingerprint(a.table[i], dom ? dom[i].y : 0u, kProc ? wl_flow_name_id(P, i) : 0u, f);
             tag = fp_tag(f, hash_mask);
             v6 = (f[4] >> 24) == 10u;
         }
@@ -118,14 +131,16 @@ __global__ __launch_bounds__(256) void k_learn_select(const ViewArgs a, const ui
 }
 
 // One insert round (launch number `launch`, from 1): one lane per table slot.
-__global__ __launch_bounds__(256) void k_learn_round(const FlowSlot* table, const uint2* dom, unsigned long long cap,
-                                                     const LearnSlots sl, const LearnIndex ix, uint32_t launch,
-                                                     unsigned long long* ctr) {
+template <bool kProc>
+__global__ __launch_bounds__(256) void k_learn_round(const FlowSlot* table, const uint2* dom, const WlProcNames P,
+                                                     unsigned long long cap, const LearnSlots sl, const LearnIndex ix,
+                                                     uint32_t launch, unsigned long long* ctr) {
+    constexpr uint32_t kFpWords = Fp<kProc>::kWords;
     const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
     if (i >= cap || sl.ent[i] != kEntUnresolved) return;
     const unsigned long long tag = sl.tag[i], mask = ix.slots - 1ull;
     uint32_t f[kFpWords];
-    fingerprint(table[i], dom ? dom[i].y : 0u, f);
+    fingerprint(table[i], dom ? dom[i].y : 0u, kProc ? wl_flow_name_id(P, i) : 0u, f);
     unsigned long long pos = launch == 1u ? (tag & mask) : (unsigned long long)sl.pos[i];
     for (unsigned long long step = 0; step < ix.slots; ++step) {
         unsigned long long g = ld64(ix.tag + pos);
@@ -196,9 +211,11 @@ __global__ __launch_bounds__(256) void k_learn_flag(const FlowSlot* table, unsig
     sl.pos[i] = flag;
 }
 
+template <bool kProc>
 __global__ __launch_bounds__(256) void k_learn_emit(const FlowSlot* table, unsigned long long cap, const LearnSlots sl,
                                                     const LearnIndex ix, fb_learned_endpoint* out,
                                                     unsigned long long out_cap, unsigned long long* d_n) {
+    constexpr uint32_t kFpWords = Fp<kProc>::kWords;
     const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
     if (i >= cap) return;
     const uint32_t flag = sl.pos[i], rank = sl.rank[i];
@@ -207,12 +224,13 @@ __global__ __launch_bounds__(256) void k_learn_emit(const FlowSlot* table, unsig
     const FlowSlot& t = table[i];
     const uint32_t e = sl.ent[i];
     const uint32_t* k = ix.key + (unsigned long long)e * kFpWords;
-    // the record as four 16-B stores: dst_ip | rep_src_ip | ports, protocol, family, name id, slot | sessions
+    // the record as four 16-B stores: dst_ip | rep_src_ip | ports, protocol, family, name id, slot | sessions,
+    // process name id (the entry's: its flows share it)
     uint4* o = reinterpret_cast<uint4*>(out + rank);
     o[0] = make_uint4(k[0], k[1], k[2], k[3]);
     o[1] = make_uint4(t.key[0], t.key[1], t.key[2], t.key[3]);
     o[2] = make_uint4((k[4] & 0xFFFFu) | (t.key[8] & 0xFFFFu) << 16, k[4] >> 16, k[5], (uint32_t)i);
-    o[3] = make_uint4(ix.cnt[e], 0u, 0u, 0u);
+    o[3] = make_uint4(ix.cnt[e], kProc ? k[6] : 0u, 0u, 0u);
 }
 
 inline dim3 grid_for(unsigned long long n) { return dim3((uint32_t)std::max(1ull, (n + 255ull) / 256ull)); }
@@ -220,11 +238,14 @@ inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
-int learn_endpoints(const ViewArgs& a, const uint2* dom, unsigned long long hash_mask, StreamScratch& per_slot,
-                    StreamScratch& index, fb_learned_endpoint* out, unsigned long long out_cap, unsigned long long* d_n,
-                    fb_learn_stats* stats, hipStream_t s) {
+int learn_endpoints(const ViewArgs& a, const uint2* dom, const WlProcNames& names, unsigned long long hash_mask,
+                    StreamScratch& per_slot, StreamScratch& index, fb_learned_endpoint* out, unsigned long long out_cap,
+                    unsigned long long* d_n, fb_learn_stats* stats, hipStream_t s) {
     if (stats) memset(stats, 0, sizeof(*stats));
     if (!view_args_valid(a) || !d_n || (out_cap && !out)) return set_err(FB_ERR_INVAL, "bad arguments");
+    const bool proc = names.n != 0u;  // a name table is installed: the eight-word fingerprint
+    if (proc && (!names.match_id || !names.name_id)) return set_err(FB_ERR_INVAL, "bad arguments");
+    const unsigned long long key_b = 4ull * (proc ? Fp<true>::kWords : Fp<false>::kWords);
     const unsigned long long cap = a.cap;
     // per table slot: tag (8 B), pos, ent, rank (4 B each); then the counters and the scan's storage
     size_t scan_b = 0;
@@ -250,7 +271,8 @@ int learn_endpoints(const ViewArgs& a, const uint2* dom, unsigned long long hash
     };
 
     HIP_TRY(hipMemsetAsync(ctr, 0, kCtrWords * 8ull, s));
-    hipLaunchKernelGGL(k_learn_select, dim3(sweep_grid(cap, 1024ull)), b, 0, s, a, dom, hash_mask, sl, ctr);
+    hipLaunchKernelGGL(proc ? k_learn_select<true> : k_learn_select<false>, dim3(sweep_grid(cap, 1024ull)), b, 0, s, a,
+                       dom, names, hash_mask, sl, ctr);
     HIP_TRY(hipGetLastError());
     rc = read_ctr();
     if (rc) return rc;
@@ -264,8 +286,8 @@ int learn_endpoints(const ViewArgs& a, const uint2* dom, unsigned long long hash
         LearnIndex ix;
         ix.slots = kMinIndexSlots;
         while (ix.slots < 2ull * selected) ix.slots <<= 1;
-        // per index slot: tag 8 | min 24 | stamp 4 | cnt 4 | key 24
-        rc = index.acquire(ix.slots * 64ull, s, "endpoint index");
+        // per index slot: tag 8 | min 24 | stamp 4 | cnt 4 | key 24 (32 with the process name id)
+        rc = index.acquire(ix.slots * (40ull + key_b), s, "endpoint index");
         if (rc) return rc;
         uint8_t* q = static_cast<uint8_t*>(index.get());
         ix.tag = reinterpret_cast<unsigned long long*>(q);
@@ -281,7 +303,8 @@ int learn_endpoints(const ViewArgs& a, const uint2* dom, unsigned long long hash
             if (rounds >= ix.slots + 2ull)  // never spins: the bound a converging insert cannot reach
                 return set_err(FB_ERR_INTERNAL, "endpoint index: insert did not converge in %llu rounds", rounds);
             HIP_TRY(hipMemsetAsync(ctr + cUnresolved, 0, 8, s));
-            hipLaunchKernelGGL(k_learn_round, g, b, 0, s, a.table, dom, cap, sl, ix, (uint32_t)(++rounds), ctr);
+            hipLaunchKernelGGL(proc ? k_learn_round<true> : k_learn_round<false>, g, b, 0, s, a.table, dom, names, cap,
+                               sl, ix, (uint32_t)(++rounds), ctr);
             HIP_TRY(hipGetLastError());
             rc = read_ctr();
             if (rc) return rc;
@@ -296,7 +319,8 @@ int learn_endpoints(const ViewArgs& a, const uint2* dom, unsigned long long hash
         hipLaunchKernelGGL(k_learn_flag, g, b, 0, s, a.table, cap, sl, ix);
         HIP_TRY(hipGetLastError());
         HIP_TRY(rocprim::exclusive_scan(scan_tmp, scan_b, sl.pos, sl.rank, 0u, (size_t)cap, rocprim::plus<uint32_t>(), s));
-        hipLaunchKernelGGL(k_learn_emit, g, b, 0, s, a.table, cap, sl, ix, out, out_cap, d_n);
+        hipLaunchKernelGGL(proc ? k_learn_emit<true> : k_learn_emit<false>, g, b, 0, s, a.table, cap, sl, ix, out,
+                           out_cap, d_n);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&endpoints, d_n, 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));

@@ -7,6 +7,7 @@ the reading is I/O; the matching is a function of the session and the ordered li
 
   SocketSnapshot     the ordered socket list and the process table, as the reference's two reads give them
   ProcessInterner    SessionL7 <-> the ids the device stores, stable for the life of a capture
+  ProcessNameInterner  process names <-> the ids the whitelist check and the endpoint learning compare on the device
   parse_proc_net     /proc/net/{tcp,tcp6,udp,udp6} text -> sockets with their inodes (pure)
   snapshot_from_proc a snapshot of this machine (Linux)
 """
@@ -42,6 +43,43 @@ class ProcessInterner:
             i = self._ids[l7] = len(self._ids) + 1
             self.processes[i] = l7
         return i
+
+
+def ascii_lower(s):
+    """Lower-case A-Z only: two strings are eq_ignore_ascii_case iff their ascii_lower are equal."""
+    return "".join(chr(ord(c) + 32) if "A" <= c <= "Z" else c for c in s)
+
+
+class ProcessNameInterner:
+    """Process names under the two ids fb_set_l7_process_names takes, each >= 1 and stable for as long as the
+    capture lives: name_id names the string verbatim (new_from_sessions' fingerprint compares the string itself,
+    src/whitelists.rs:144-153), match_id its ASCII-lower-cased form (process_matches is eq_ignore_ascii_case,
+    src/whitelists.rs:716-724).  The whitelist compiler and the table upload share one, so an endpoint compiled
+    before any process of its name was seen already carries the id that process will get."""
+
+    def __init__(self):
+        self._match = {}
+        self._name = {}
+        self.names = {}  # name_id -> the name verbatim
+
+    def match_id(self, name):
+        return self._match.setdefault(ascii_lower(name), len(self._match) + 1)
+
+    def name_id(self, name):
+        i = self._name.get(name)
+        if i is None:
+            i = self._name[name] = len(self._name) + 1
+            self.names[i] = name
+        return i
+
+    def table(self, processes):
+        """The (match_id, name_id) arrays of fb_set_l7_process_names for a ProcessInterner's `processes`
+        {id: SessionL7}: entry p names process id p, entry 0 is 0."""
+        n = max(processes, default=0) + 1
+        m, v = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        for p, l7 in processes.items():
+            m[p], v[p] = self.match_id(l7.process_name), self.name_id(l7.process_name)
+        return m, v
 
 
 class SocketSnapshot:
@@ -159,4 +197,4 @@ def snapshot_from_proc(proc="/proc"):
     return SocketSnapshot(sockets, processes)
 
 
-__all__ = ["SessionL7", "SocketSnapshot", "ProcessInterner", "parse_proc_net", "snapshot_from_proc", "Protocol"]
+__all__ = ["SessionL7", "SocketSnapshot", "ProcessInterner", "ProcessNameInterner", "parse_proc_net", "snapshot_from_proc", "Protocol"]

@@ -317,19 +317,23 @@ class Whitelists:
         return self
 
     @staticmethod
-    def from_learned(records, names=None):
+    def from_learned(records, names=None, process_names=None):
         """new_from_sessions from fb_learned_endpoint records (FlodbaddGpuCapture.learn_endpoints): one
         endpoint per record, in the records' order -- domain = names[dst_name_id] ({id: str} from
         FlodbaddGpuCapture.dns_names; id 0: None), ip, port, protocol, and the description of the record's
-        representative session.  No process: the device has none."""
+        representative session.  process_names {id: str} (l7.ProcessNameInterner.names): process =
+        process_names[proc_name_id] (id 0: None) of records learned while a process-name table was installed;
+        without it no endpoint has a process."""
         names = names or {}
         endpoints = []
-        for r in records:
+        pids = np.asarray(records).view(N.LEARNED_ENDPOINT_PROC_DTYPE)["proc_name_id"] if process_names is not None else None
+        for j, r in enumerate(records):
             fam, dst = int(r["family"]), words_to_ip(r["dst_ip"], int(r["family"]))
             nid = int(r["dst_name_id"])
             endpoints.append(WhitelistEndpoint(
                 domain=names[nid] if nid else None, ip=str(dst), port=int(r["dst_port"]),
                 protocol={6: "TCP", 17: "UDP"}[int(r["protocol"])],
+                process=process_names[int(pids[j])] if (pids is not None and int(pids[j])) else None,
                 description="Auto-generated from session: %s:%d -> %s:%d" % (
                     words_to_ip(r["rep_src_ip"], fam), int(r["rep_src_port"]), dst, int(r["dst_port"]))))
         return Whitelists().as_custom(endpoints)
@@ -367,13 +371,17 @@ class Whitelists:
         out.whitelists = merged
         return out.to_json(compact=True)
 
-    def compile(self, name, asn_records=None, dns_resolutions=None):
+    def compile(self, name, asn_records=None, dns_resolutions=None, process_ids=None):
         """The flattened list `name` as fb_wl_endpoint rows.  asn_records: the (as_number, country,
         owner) of every fb_asn_range.record (asn_tables_from_tsv's third result), for the interned
         owner / country ids.  dns_resolutions {ip: domain}: every domain endpoint whose pattern matches
         the domain of a resolved address also yields an exact-address row for that address with the same
         protocol, port and process flag and no AS fields (a matching domain returns true at once); the
-        domain endpoint itself keeps FB_WL_HAS_DOMAIN for the host-check bit."""
+        domain endpoint itself keeps FB_WL_HAS_DOMAIN for the host-check bit.  process_ids: an
+        l7.ProcessNameInterner -- every endpoint with a process then carries its process_match_id (the
+        word `reserved2` of the rows, N.WL_ENDPOINT_PROC_DTYPE), expanded rows included, and the device
+        matches it against the flows' processes (fb_set_l7_process_names); without it the word stays 0
+        and such an endpoint is the host's to decide."""
         eps = self.get_all_endpoints(name)
         strings = {}
 
@@ -396,6 +404,8 @@ class Whitelists:
                 r["port"] = ep.port
             if ep.process is not None:
                 flags |= N.FB_WL_HAS_PROCESS
+                if process_ids is not None:
+                    r["reserved2"] = process_ids.match_id(ep.process)
             base = r.copy()
             base["flags"] = flags  # protocol, port and the process flag: what an expanded row shares
             if ep.ip is not None:

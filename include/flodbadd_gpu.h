@@ -867,6 +867,18 @@ int fb_l7_clear(fb_ctx* ctx);
  * installed snapshot with the pass's own device function: d_out[i] = {process_id, FB_L7_EXACT / _FUZZY or
  * 0, 0, 0}.  FB_ERR_INVAL without a snapshot.  DEVICE pointers, asynchronous. */
 int fb_l7_lookup_dev(fb_ctx* ctx, const fb_session_key* d_keys, uint64_t n, fb_l7_rec* d_out, void* stream);
+/* The names of the L7 plane's process ids, for the process-aware whitelist check and learning (DESIGN.md
+ * 3.19).  For a process id p < n: match_id[p] is the caller's id (>= 1) of the ASCII-lower-cased process name
+ * -- the reference matches with eq_ignore_ascii_case (src/whitelists.rs:716-724) --, name_id[p] the caller's
+ * id (>= 1) of the name verbatim -- new_from_sessions' fingerprint compares the string itself, so "Curl" and
+ * "curl" are two endpoints but one match class.  Entry 0 stands for "no process" and is stored as 0.
+ * A flow's process is x = its fb_l7_rec.process_id when the plane exists, x != 0 and x < n; else it has none
+ * (no L7 pass yet, unresolved, FB_L7_FAILED, an id beyond the table).  The arrays are copied (HOST pointers);
+ * a second call replaces the table, n == 0 removes it.  FB_ERR_INVAL for a zero id at p >= 1 or a NULL array
+ * with n != 0; an invalid call leaves the installed table as it was.  fb_l7_clear and fb_flow_clear zero the
+ * plane and leave the table.  Without a table every pass runs as it did before this call existed.
+ * Synchronous. */
+int fb_set_l7_process_names(fb_ctx* ctx, const uint32_t* match_id, const uint32_t* name_id, uint64_t n);
 
 int fb_flow_count(fb_ctx* ctx, uint64_t* n_flows, void* stream); /* synchronous */
 /* Copy every flow (slot order) to host memory; *n = flows written (<= cap). Synchronous. */
@@ -971,7 +983,10 @@ int fb_flow_status_dev(fb_ctx* ctx, uint8_t* d_out, uint64_t cap, void* stream);
  * dst_domain and l7 are None (the device knows neither; the host expands the domains it has resolved
  * into address endpoints before fb_set_whitelist and resolves the flows marked FB_WL_HOST_CHECK):
  *   - protocol, port and process must match (src/whitelists.rs:465-491): an endpoint with a process
- *     never matches here;
+ *     never matches here -- unless it carries a process_match_id and a process-name table is installed
+ *     (fb_set_l7_process_names) when the pass runs: then process_matches is "the flow's match id equals
+ *     the endpoint's" (a flow without a process never matches), the rest of the endpoint is evaluated as the
+ *     same endpoint without a process is, and its key is no host-check key on account of the process;
  *   - a domain endpoint does not match by domain; with `ip` specified, an address match returns true at
  *     once and a mismatch fails the endpoint, whatever its AS fields say (src/whitelists.rs:503-531);
  *   - with neither domain nor ip, every specified AS field must equal the session's dst_asn
@@ -998,10 +1013,16 @@ typedef struct fb_wl_endpoint {
     uint32_t as_number;  /* 24: with FB_WL_HAS_ASN                                                     */
     uint32_t owner_id;   /* 28: with FB_WL_HAS_OWNER: the caller's id of the ASCII-lower-cased string  */
     uint32_t country_id; /* 32: with FB_WL_HAS_COUNTRY (ids < 0xFFFFFFFF)                               */
-    uint32_t reserved2;  /* 36: 0                                                                      */
+    union {              /* 36: one word under two names                                               */
+        uint32_t reserved2;        /* its name before the device knew processes: 0                     */
+        uint32_t process_match_id; /* with FB_WL_HAS_PROCESS: the caller's id (>= 1) of the ASCII-lower-cased
+                                      process name, as fb_set_l7_process_names' match_id names it; 0: the
+                                      device has no id for the name                                    */
+    };
 } fb_wl_endpoint;        /* 40 bytes */
 #define FB_WL_MAX_EXACT (1u << 24) /* endpoints that match by one address (/32, /128), per call       */
-#define FB_WL_MAX_OTHER (1u << 16) /* every other endpoint (nets, AS-only, domain-only, process)      */
+#define FB_WL_MAX_OTHER (1u << 16) /* every other endpoint (nets, AS-only, domain-only, process); an
+                                      exact-address endpoint with a process_match_id counts as exact  */
 /* Install the flattened endpoint list of the active whitelist (copied and indexed before the call
  * returns).  rec_owner_id[r] / rec_country_id[r]: the caller's id of the lower-cased owner / country
  * string of fb_asn_range.record r (the reference compares them with eq_ignore_ascii_case); NULL with
@@ -1274,7 +1295,9 @@ int fb_flow_export_view(fb_ctx* ctx, const fb_view_query* query, fb_flow_view* o
  * dst_port, protocol, dst_name_id): dst_name_id is the domain plane's id of the flow (fb_flow_domains),
  * 0 -- the reference's None -- before any domain pass and without DNS tracking.  Each endpoint carries a
  * representative session, the least of its flows under Session's derived Ord (inside a group: source
- * address, then source port), so it depends neither on the table's layout nor on a race. */
+ * address, then source port), so it depends neither on the table's layout nor on a race.  While a
+ * process-name table is installed (fb_set_l7_process_names) the fingerprint has a sixth member, the flow's
+ * verbatim process name id (proc_name_id, 0: no process). */
 typedef struct fb_learned_endpoint {
     uint32_t dst_ip[4];     /*  0: session_key word order                                                */
     uint32_t rep_src_ip[4]; /* 16: the representative session's source                                   */
@@ -1286,7 +1309,14 @@ typedef struct fb_learned_endpoint {
     uint32_t dst_name_id;   /* 40: the domain plane's id, 0 = no domain                                  */
     uint32_t rep_slot;      /* 44: the representative's table slot                                       */
     uint32_t sessions;      /* 48: selected flows with this fingerprint                                  */
-    uint32_t reserved2[3];  /* 52: 0                                                                     */
+    union {                 /* 52: three words under two sets of names                                   */
+        uint32_t reserved2[3];        /* their name before the device knew processes: 0                  */
+        struct {
+            uint32_t proc_name_id;    /* the flow's verbatim process name id (fb_set_l7_process_names), 0 =
+                                         no process; written only while a name table is installed (else 0) */
+            uint32_t reserved3[2];    /* 0                                                               */
+        };
+    };
 } fb_learned_endpoint;      /* 64 bytes; an output array starts at a 16-byte boundary                    */
 typedef struct fb_learn_stats {
     uint64_t flows;     /*  0: flows in the table                                                        */
