@@ -85,6 +85,14 @@ FB_WL_NEVER = 0xFF
 FB_WL_HAS_PORT, FB_WL_HAS_ASN, FB_WL_HAS_OWNER, FB_WL_HAS_COUNTRY, FB_WL_HAS_DOMAIN, FB_WL_HAS_PROCESS = 1, 2, 4, 8, 16, 32
 FB_WL_CONFORMING, FB_WL_NONCONFORMING, FB_WL_HOST_CHECK, FB_WL_MASK_UNKNOWN = 1, 2, 4, 128
 FB_WL_MAX_EXACT, FB_WL_MAX_OTHER = 1 << 24, 1 << 16
+# domain patterns (fb_set_whitelist_dom): fb_wl_stats with reserved[0] under its second name (the flows left to
+# the host because their name's row overflowed), fb_wl_dom_info, the row width and the pattern limits
+WL_STATS_DOM_DTYPE = np.dtype([(f, "<u8") for f in WL_STATS_FIELDS] + [("dom_overflow", "<u8"), ("reserved", "<u8", (2,))])
+WL_DOM_KINDS = ["exact", "suffix", "prefix", "general", "never"]
+WL_DOM_INFO_DTYPE = np.dtype([("patterns", "<u8", (5,)), ("names_done", "<u8"), ("names_matched", "<u8"),
+                              ("names_overflowed", "<u8")])
+assert WL_STATS_DOM_DTYPE.itemsize == 64 and WL_DOM_INFO_DTYPE.itemsize == 64
+FB_WL_MAX_GENERAL, FB_WL_NAME_MATCHES, FB_WL_MAX_PATTERNS = 1024, 8, (1 << 24) - 1
 # the kernel's staging thresholds (fb_internal.h: kWlLdsRules, kWlLdsGroups), for the tests at them
 WL_LDS_RULES, WL_LDS_GROUPS = 512, 512
 # fb_bl_stats (fb_flow_blacklist: recompute_blacklist_for_sessions, src/blacklists.rs:456-731) and the
@@ -287,6 +295,7 @@ _PU32, _PU64 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 FB_DEBUG_DENSE_STEAL_POLLS, FB_DEBUG_DENSE_OFFSET_SKEW, FB_DEBUG_VIEW_DIRECT, FB_DEBUG_ZEEK_DIRECT = 1, 2, 3, 4
 FB_DEBUG_LEARN_HASH_MASK = 6  # (5 is unassigned)
 FB_DEBUG_DNS_LAUNCH = 7
+FB_DEBUG_WL_NAME_HASH_MASK = 8
 
 GPU_SYMBOLS = [
     ("fb_abi_version", _U32, []),
@@ -377,6 +386,9 @@ GPU_SYMBOLS = [
     ("fb_flow_age", _I, [_P, _U64, _P, _U32, _P, _P]),
     ("fb_flow_status_dev", _I, [_P, _P, _U64, _P]),
     ("fb_set_whitelist", _I, [_P, _P, _U64, _P, _P, _U32]),
+    ("fb_set_whitelist_dom", _I, [_P, _P, _U64, _P, _P, _P, _U64, _P, _P, _U32]),
+    ("fb_wl_name_matches_dev", _I, [_P, _P, _U64, _P, _P, _P]),
+    ("fb_wl_dom_info_get", _I, [_P, _P]),
     ("fb_clear_whitelist", _I, [_P]),
     ("fb_flow_whitelist", _I, [_P, _U32, _P, _P]),
     ("fb_flow_whitelist_dev", _I, [_P, _P, _U64, _P]),

@@ -81,7 +81,8 @@ class FlodbaddGpuCapture:
     def __init__(self, device=0, session_filter=SessionFilter.GlobalOnly, flow_capacity=1 << 20,
                  service_bitmap=None, lan_v6=(), own_ips=(), max_batch_packets=1 << 20, track_history=False,
                  grow=True, timed=False, track_dns=False, dns_name_capacity=0, dns_addr_capacity=0, dns_hash_mask=0,
-                 history_on_device=False, history_block_capacity=0, history_max_blocks=0, processes_on_device=False):
+                 history_on_device=False, history_block_capacity=0, history_max_blocks=0, processes_on_device=False,
+                 domains_on_device=False):
         """timed: capture-time session state (FB_CFG_TIMED): every batch then comes with its frames'
         capture timestamps (`ts`, ns) and the sessions carry start / last / end times and the
         segment state with the reference's 5-s timeout (src/packets.rs:137-200).
@@ -99,7 +100,16 @@ class FlodbaddGpuCapture:
         device (fb_set_l7_process_names): set_l7_sockets uploads the names of its processes,
         update_whitelist compiles the list with process ids and leaves only the flows a domain endpoint marks to
         the host, and create_custom_whitelists(on_device=True) / augment_custom_whitelists learn endpoints with
-        their processes on the device.  A caller who passes process_names to those calls keeps the host path."""
+        their processes on the device.  A caller who passes process_names to those calls keeps the host path.
+        domains_on_device (with track_dns): the whitelist check matches domain endpoints on the device
+        (fb_set_whitelist_dom): update_whitelist compiles the list with its domain patterns
+        instead of expanding the tracked resolutions into it -- so it installs the list once per list, not once
+        per new resolution --, downloads no resolutions, and the pass decides and stamps the domain verdicts
+        from the sessions' dst_domain (the domain plane).  Only the flows of a name that matched more than
+        FB_WL_NAME_MATCHES patterns, or of a pattern the device has no id for, go through the host loop.  A
+        caller who passes dns_resolutions keeps the host path."""
+        if domains_on_device and not track_dns:
+            raise ValueError("domains_on_device needs track_dns=True")
         lib = N.gpu_lib()
         self._keep = []
         cfg = N.FbConfig()
@@ -178,6 +188,9 @@ class FlodbaddGpuCapture:
         self.processes_on_device = bool(processes_on_device)
         self._proc_names = ProcessNameInterner()  # shared by the whitelist compiler and the name table's upload
         self._wl_with_ids = False                 # the installed list was compiled with process ids
+        self.domains_on_device = bool(domains_on_device)
+        self._wl_dom = False                      # the installed list was compiled with domain patterns
+        self.wl_installs = 0                      # lists update_whitelist has installed so far
         self._l7_installed = False
         self._l7_ran = False
         if self.track_dns:
@@ -516,6 +529,19 @@ class FlodbaddGpuCapture:
         """Does a whitelist call leave the processes to the device?  (processes_on_device, and the caller gave
         no process_names of their own.)"""
         return self.processes_on_device and process_names is None
+
+    def _device_domains(self, dns_resolutions):
+        """Does a whitelist call leave the domains to the device?  (domains_on_device, and the caller gave no
+        dns_resolutions of their own.)"""
+        return self.domains_on_device and dns_resolutions is None
+
+    def _slot_domains(self, flows):
+        """{Session: dst_domain} of the given fb_flow_rec records alone, from the domain plane."""
+        if not (self._dom_ran and len(flows)):
+            return {}
+        ids = self.domain_ids()["dst_name_id"]
+        names = self.dns_names(np.unique([int(ids[int(r["slot"])]) for r in flows]))
+        return {Session.from_key(r): names[int(ids[int(r["slot"])])] for r in flows if int(ids[int(r["slot"])])}
 
     def _slot_process_names(self, flows):
         """{Session: process name} of the given fb_flow_rec records alone, from the L7 plane."""
@@ -1170,10 +1196,22 @@ class FlodbaddGpuCapture:
         return self._compact_export("fb_flow_export_whitelist_dev", [N.FLOW_REC_DTYPE], int(state_mask))[0]
 
     def install_whitelist(self, compiled):
-        """fb_set_whitelist with a CompiledWhitelist (or bare WL_ENDPOINT_DTYPE rows)."""
+        """fb_set_whitelist with a CompiledWhitelist (or bare WL_ENDPOINT_DTYPE rows); fb_set_whitelist_dom with
+        one compiled with domain_patterns."""
         rows = np.ascontiguousarray(getattr(compiled, "rows", compiled), dtype=N.WL_ENDPOINT_DTYPE)
         own = np.ascontiguousarray(getattr(compiled, "rec_owner_id", np.zeros(0)), dtype=np.uint32)
         cty = np.ascontiguousarray(getattr(compiled, "rec_country_id", np.zeros(0)), dtype=np.uint32)
+        if getattr(compiled, "ep_pattern", None) is not None:
+            epp = np.ascontiguousarray(compiled.ep_pattern, dtype=np.uint32)
+            blob = np.ascontiguousarray(compiled.pattern_bytes, dtype=np.uint8)
+            off = np.ascontiguousarray(compiled.pattern_off, dtype=np.uint64)
+            if len(epp) != len(rows):
+                raise ValueError("ep_pattern has %d entries for %d rows" % (len(epp), len(rows)))
+            N.check(N.gpu_lib().fb_set_whitelist_dom(
+                self.ctx, N.ptr(rows) if len(rows) else None, len(rows), N.ptr(epp) if len(epp) else None,
+                N.ptr(blob) if len(blob) else None, N.ptr(off), len(off) - 1, N.ptr(own) if len(own) else None,
+                N.ptr(cty) if len(own) else None, len(own)))
+            return
         N.check(N.gpu_lib().fb_set_whitelist(self.ctx, N.ptr(rows) if len(rows) else None, len(rows),
                                              N.ptr(own) if len(own) else None, N.ptr(cty) if len(own) else None,
                                              len(own)))
@@ -1183,6 +1221,28 @@ class FlodbaddGpuCapture:
         st = np.zeros(1, dtype=N.WL_STATS_DTYPE)
         N.check(N.gpu_lib().fb_flow_whitelist(self.ctx, 0, N.ptr(st), None))
         return stats_dict(st, N.WL_STATS_FIELDS)
+
+    def whitelist_name_matches(self, ids):
+        """fb_wl_name_matches_dev: (rows, flags) of the given DNS name ids -- rows[i] the ids (1-based, ascending,
+        zero-padded) of the installed domain patterns name ids[i] matches, at most FB_WL_NAME_MATCHES; flags[i]
+        bit 0: it matches more.  Brings the device's match state up to date first."""
+        a = np.ascontiguousarray(ids, dtype=np.uint32)
+        n = len(a)
+        d_ids = N.DeviceBuffer(max(a.nbytes, 4)).upload(a)
+        d_rows, d_flags = N.DeviceBuffer(max(n, 1) * N.FB_WL_NAME_MATCHES * 4), N.DeviceBuffer(max(n, 1))
+        N.check(N.gpu_lib().fb_wl_name_matches_dev(self.ctx, d_ids.ptr, n, d_rows.ptr, d_flags.ptr, None))
+        return (d_rows.download(np.zeros((n, N.FB_WL_NAME_MATCHES), dtype=np.uint32)) if n else
+                np.zeros((0, N.FB_WL_NAME_MATCHES), dtype=np.uint32),
+                d_flags.download(np.zeros(n, dtype=np.uint8)) if n else np.zeros(0, dtype=np.uint8))
+
+    def whitelist_domain_info(self):
+        """fb_wl_dom_info_get: the installed patterns per kind ({"exact", "suffix", "prefix", "general",
+        "never"}), and names_done / names_matched / names_overflowed of the names matched so far."""
+        t = np.zeros(1, dtype=N.WL_DOM_INFO_DTYPE)
+        N.check(N.gpu_lib().fb_wl_dom_info_get(self.ctx, N.ptr(t)))
+        out = {k: int(v) for k, v in zip(N.WL_DOM_KINDS, t[0]["patterns"])}
+        out.update({f: int(t[0][f]) for f in ("names_done", "names_matched", "names_overflowed")})
+        return out
 
     def _dst_asn(self, ips):
         """SessionInfo.dst_asn of destination addresses (src/packets.rs:468-485): Db::lookup on the GPU
@@ -1203,21 +1263,29 @@ class FlodbaddGpuCapture:
         the process endpoints itself -- and stamps what it changes --, no {Session: name} dictionary is
         downloaded, and only the flows a domain endpoint marks go through the host loop, with the processes
         of just those flows.
+        domains_on_device (and dns_resolutions None): the list is compiled with its domain patterns and no
+        resolutions -- a new resolution changes nothing installed --, the pass decides the domain endpoints from
+        the domain plane, and the host loop sees only the flows of an overflowed name or of a pattern without an
+        id, with the dst_domain of just those flows.
         Returns the pass's counters, or None."""
         self._wl_inputs = (dns_resolutions, process_names)
         self._wl_proc = None
         if not self._wl_name:
             return None
-        if dns_resolutions is None and self.track_dns:  # the capture's own passive resolutions
+        dom_dev = self._device_domains(dns_resolutions)
+        if dns_resolutions is None and self.track_dns and not dom_dev:  # the capture's own passive resolutions
             dns_resolutions = {str(ip): name for ip, name in self.dns_resolutions().items()}
         want = dict(dns_resolutions or {})
         on_dev = self._device_processes(process_names)
-        if self._wl_installed is None or self._wl_installed[1] != want or self._wl_with_ids != on_dev:
-            comp = self._whitelists.compile(self._wl_name, self._asn_records, want,
-                                            process_ids=self._proc_names if on_dev else None)
+        if (self._wl_installed is None or self._wl_installed[1] != want or self._wl_with_ids != on_dev
+                or self._wl_dom != dom_dev):
+            comp = self._whitelists.compile(self._wl_name, self._asn_records, None if dom_dev else want,
+                                            process_ids=self._proc_names if on_dev else None, domain_patterns=dom_dev)
             self.install_whitelist(comp)
             self._wl_installed = (comp, want)
             self._wl_with_ids = on_dev
+            self._wl_dom = dom_dev
+            self.wl_installs += 1
         comp = self._wl_installed[0]
         stats = self.whitelist_pass()
         self._wl_host_ok = set()
@@ -1230,13 +1298,21 @@ class FlodbaddGpuCapture:
             if stats["host_check"]:
                 process_names = self._wl_proc = self._process_names(process_names)
             host_loop = bool(process_names) and bool(stats["host_check"])
+        domain_of = None
+        if dom_dev and stats["host_check"]:  # what the rows could not decide: the domains of just those flows
+            if marked is None:
+                marked = self.export_whitelist_flows(N.FB_WL_HOST_CHECK)
+            domain_of = self._slot_domains(marked)
+            process_names = process_names or {}
+            host_loop = True
         if host_loop:
             if marked is None:
                 marked = self.export_whitelist_flows(N.FB_WL_HOST_CHECK)
             marked = [Session.from_key(r) for r in marked]
             for s, asn in zip(marked, self._dst_asn([s.dst_ip for s in marked])):
                 a = asn or (None, None, None)
-                if is_session_in_whitelist(comp.endpoints, comp.name, want.get(str(s.dst_ip)), str(s.dst_ip), s.dst_port,
+                dom = domain_of.get(s) if domain_of is not None else want.get(str(s.dst_ip))
+                if is_session_in_whitelist(comp.endpoints, comp.name, dom, str(s.dst_ip), s.dst_port,
                                            s.protocol.name, a[0], a[1], a[2], process_names.get(s))[0]:
                     self._wl_host_ok.add(s)
         exc = self.export_whitelist_flows(N.FB_WL_NONCONFORMING)
@@ -1273,7 +1349,8 @@ class FlodbaddGpuCapture:
             s, a = info.session, asn or (None, None, None)
             # (an exception is a session no endpoint matched: the reason needs no second scan of the list)
             info.is_whitelisted = WhitelistState.NonConforming
-            info.whitelist_reason = no_match_reason(comp.endpoints, comp.name, dns.get(str(s.dst_ip)), str(s.dst_ip),
+            dom = info.dst_domain if self._wl_dom else dns.get(str(s.dst_ip))  # (the domain the device decided with)
+            info.whitelist_reason = no_match_reason(comp.endpoints, comp.name, dom, str(s.dst_ip),
                                                     s.dst_port, s.protocol.name, a[0], a[1], a[2], proc.get(s))
         return out
 

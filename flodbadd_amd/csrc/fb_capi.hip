@@ -89,16 +89,44 @@ struct Staging {
     Pkts pk;
     DevBuf<fb_batch_stats> stats;
 };
+// The installed whitelist's domain patterns (fb_set_whitelist_dom, fb_wl_domain.hip) and the match state of the
+// DNS tracker's names against them: rows / flags hold `cap` names (and id 0), valid for the ids 1 .. upto.
+struct WlDomDev {
+    WlDomIndex host;  // what the tables were made from (the mask knob rebuilds them)
+    DevBuf<uint8_t> blob;
+    DevBuf<uint32_t> off, len[kWlDomHashed], pid[kWlDomHashed], gpid, gstar;
+    DevBuf<unsigned long long> hash[kWlDomHashed];
+    DevBuf<uint32_t> rows;
+    DevBuf<uint8_t> flags;
+    DevBuf<unsigned long long> ctr;  // [2] names with a non-empty row, names overflowed (of the ids 1 .. upto)
+    uint64_t cap = 0, upto = 0;
+    bool active() const { return host.n_patterns() != 0u; }
+    WlDomTables tables() const {
+        WlDomTables t = host.tables();  // the counts and the mask; every pointer replaced by the device's
+        t.blob = blob;
+        t.off = off;
+        for (uint32_t k = 0; k < kWlDomHashed; ++k) {
+            t.hash[k] = hash[k];
+            t.len[k] = len[k];
+            t.pid[k] = pid[k];
+        }
+        t.gpid = gpid;
+        t.gstar = gstar;
+        return t;
+    }
+};
 // The installed whitelist's index (fb_set_whitelist, fb_whitelist.hip).
 struct WlDev {
-    DevBuf<uint32_t> a4, k4, k6, gkey, gbeg, owner, country;
+    DevBuf<uint32_t> a4, k4, k6, gkey, gbeg, owner, country, dpid;
     DevBuf<unsigned long long> kp4, kp6;  // with_proc: instead of k4 / k6
+    DevBuf<unsigned long long> dkp;       // the domain endpoints with a pattern id (WlIndex::dpid / dkp)
     DevBuf<uint4> a6;
     DevBuf<WlRule> rules;
-    uint32_t n4 = 0, n6 = 0, ng = 0, nr = 0, records = 0;
+    uint32_t n4 = 0, n6 = 0, ng = 0, nr = 0, records = 0, nd = 0;
     bool with_proc = false;  // WlIndex::with_proc: the process-aware instances run
+    WlDomDev dom;
     WlTables tables() const {
-        return {a4, k4, a6, k6, gkey, gbeg, rules, owner, country, kp4, kp6, n4, n6, ng, nr, records};
+        return {a4, k4, a6, k6, gkey, gbeg, rules, owner, country, kp4, kp6, n4, n6, ng, nr, records, dpid, dkp, nd};
     }
 };
 // The names of the L7 plane's process ids (fb_set_l7_process_names); n 0: no table.
@@ -253,6 +281,7 @@ struct fb_ctx {
     // endpoint learning (fb_flow_learn_endpoints_dev, fb_learn.hip): the per-table-slot arrays, the endpoint index
     StreamScratch learn_slots, learn_index;
     unsigned long long learn_hash_mask = ~0ull;  // FB_DEBUG_LEARN_HASH_MASK
+    unsigned long long wl_name_hash_mask = ~0ull;  // FB_DEBUG_WL_NAME_HASH_MASK
     // timed contexts (FB_CFG_TIMED, fb_time.hip): the capture-time pass's scratch
     bool timed = false;
     StreamScratch tscratch;
@@ -766,6 +795,7 @@ static int take_frame_times(fb_ctx* c, const unsigned long long** ts) {
     return FB_OK;
 }
 
+static int wl_dom_set_mask(fb_ctx* c, unsigned long long mask);  // (with the whitelist calls)
 int fb_debug_set(fb_ctx* c, uint32_t knob, uint64_t value) {
     if (!c) return set_err(FB_ERR_INVAL, "ctx is NULL");
     switch (knob) {
@@ -787,6 +817,8 @@ int fb_debug_set(fb_ctx* c, uint32_t knob, uint64_t value) {
         case FB_DEBUG_LEARN_HASH_MASK:
             c->learn_hash_mask = value ? value : ~0ull;
             return FB_OK;
+        case FB_DEBUG_WL_NAME_HASH_MASK:
+            return wl_dom_set_mask(c, value ? value : ~0ull);
         case FB_DEBUG_DNS_LAUNCH:
             if (!c->dns) return set_err(FB_ERR_INVAL, "DNS tracking is not enabled (fb_dns_track_enable)");
             return dnstrack_set_launch(c->dns, value);
@@ -1983,16 +2015,93 @@ int fb_flow_status_dev(fb_ctx* c, uint8_t* d_out, uint64_t cap, void* stream) {
 // ---- whitelist conformance (fb_whitelist.hip) -----------------------------------------------------
 // The list is validated and indexed on the host first (build_whitelist_index), so a refused list
 // leaves the installed one untouched; then the old arrays are replaced (no launch may still read them).
-int fb_set_whitelist(fb_ctx* c, const fb_wl_endpoint* eps, uint64_t n, const uint32_t* rec_owner_id,
-                     const uint32_t* rec_country_id, uint32_t n_records) {
-    if (!c || (n && !eps) || (n_records && (!rec_owner_id || !rec_country_id)))
+// The pattern tables of d.host on the device (the match state is the caller's to reset).
+static int wl_dom_upload(WlDomDev& d) {
+    const WlDomIndex& h = d.host;
+    int rc = upload_array(d.blob, h.blob.data(), h.blob.size());
+    if (!rc) rc = upload_array(d.off, h.off.data(), h.off.size());
+    for (uint32_t k = 0; !rc && k < kWlDomHashed; ++k) {
+        rc = upload_array(d.hash[k], h.hash[k].data(), h.hash[k].size());
+        if (!rc) rc = upload_array(d.len[k], h.len[k].data(), h.len[k].size());
+        if (!rc) rc = upload_array(d.pid[k], h.pid[k].data(), h.pid[k].size());
+    }
+    if (!rc) rc = upload_array(d.gpid, h.gpid.data(), h.gpid.size());
+    if (!rc) rc = upload_array(d.gstar, h.gstar.data(), h.gstar.size());
+    return rc;
+}
+// No name's row is valid any more.
+static int wl_dom_forget(WlDomDev& d) {
+    d.upto = 0;
+    if (d.ctr) HIP_TRY(hipMemset(d.ctr, 0, 16));
+    return FB_OK;
+}
+// FB_DEBUG_WL_NAME_HASH_MASK: the installed pattern tables again under the new mask, every name to be matched again.
+static int wl_dom_set_mask(fb_ctx* c, unsigned long long mask) {
+    c->wl_name_hash_mask = mask;
+    WlDomDev& d = c->wl.dom;
+    if (!d.active()) return FB_OK;
+    DeviceGuard g(c->device);
+    HIP_TRY(hipDeviceSynchronize());
+    const std::vector<uint8_t> blob(d.host.blob);
+    const std::vector<uint64_t> off(d.host.off.begin(), d.host.off.end());
+    if (!build_wl_dom_index(blob.data(), off.data(), off.size() - 1u, mask, d.host))
+        return set_err(FB_ERR_INTERNAL, "domain pattern tables");
+    const int rc = wl_dom_upload(d);
+    return rc ? rc : wl_dom_forget(d);
+}
+// The names (upto, n_names] of the DNS tracker matched against the installed patterns; the rows grow with the
+// tracker's store.  Waits for what it launched: the rows are read by whatever stream comes next.
+static int wl_dom_sync(fb_ctx* c, hipStream_t s) {
+    WlDomDev& d = c->wl.dom;
+    if (!d.active() || !c->dns) return FB_OK;
+    const DnsTables t = dnstrack_tables(c->dns);
+    const uint64_t n = t.n_names;
+    if (n <= d.upto) return FB_OK;
+    if (!d.ctr) {
+        if (d.ctr.alloc(2) != hipSuccess) return set_err(FB_ERR_NOMEM, "name match counters");
+        HIP_TRY(hipMemsetAsync(d.ctr, 0, 16, s));
+    }
+    if (n > d.cap) {
+        uint64_t cap = std::max<uint64_t>(2ull * d.cap, 1024ull);
+        while (cap < n) cap *= 2ull;
+        DevBuf<uint32_t> rows;
+        DevBuf<uint8_t> flags;
+        if (alloc_each(rows, (cap + 1ull) * FB_WL_NAME_MATCHES, flags, cap + 1ull) != hipSuccess)
+            return set_err(FB_ERR_NOMEM, "name match rows (%llu names)", (unsigned long long)cap);
+        if (d.upto) {
+            HIP_TRY(hipMemcpyAsync(rows, d.rows, (d.upto + 1ull) * FB_WL_NAME_MATCHES * 4ull, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(flags, d.flags, d.upto + 1ull, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        d.rows = std::move(rows);
+        d.flags = std::move(flags);
+        d.cap = cap;
+    }
+    HIP_TRY(launch_wl_name_match(d.tables(), t.names, t.name_len, (uint32_t)d.upto + 1u, (uint32_t)n, d.rows, d.flags, d.ctr, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    d.upto = n;
+    return FB_OK;
+}
+
+int fb_set_whitelist_dom(fb_ctx* c, const fb_wl_endpoint* eps, uint64_t n, const uint32_t* ep_pattern,
+                         const uint8_t* pattern_bytes, const uint64_t* pattern_off, uint64_t n_patterns,
+                         const uint32_t* rec_owner_id, const uint32_t* rec_country_id, uint32_t n_records) {
+    if (!c || (n && !eps) || (n_records && (!rec_owner_id || !rec_country_id)) || (n_patterns && !pattern_off))
         return set_err(FB_ERR_INVAL, "bad arguments");
     if (n > (uint64_t)FB_WL_MAX_EXACT + FB_WL_MAX_OTHER)
         return set_err(FB_ERR_INVAL, "%llu endpoints: more than FB_WL_MAX_EXACT + FB_WL_MAX_OTHER", (unsigned long long)n);
+    if (n_patterns > (1u << 24) - 1u)
+        return set_err(FB_ERR_INVAL, "%llu patterns: more than 2^24 - 1", (unsigned long long)n_patterns);
+    if (n_patterns && pattern_off[n_patterns] && !pattern_bytes) return set_err(FB_ERR_INVAL, "pattern_bytes is NULL");
+    WlDomDev dom;
+    if (!build_wl_dom_index(pattern_bytes, pattern_off, n_patterns, c->wl_name_hash_mask, dom.host))
+        return set_err(FB_ERR_INVAL, "domain patterns: offsets that do not ascend from 0, 2^32 bytes or more, or more than "
+                       "%u patterns of the a*b kind", FB_WL_MAX_GENERAL);
     WlIndex ix;
-    if (!build_whitelist_index(eps, n, ix))
-        return set_err(FB_ERR_INVAL, "whitelist endpoint with a bad family, prefix, protocol or flags, or more than "
-                       "%u exact-address / %u other endpoints", FB_WL_MAX_EXACT, FB_WL_MAX_OTHER);
+    if (!build_whitelist_index(eps, n, ix, ep_pattern, n_patterns))
+        return set_err(FB_ERR_INVAL, "whitelist endpoint with a bad family, prefix, protocol or flags, more than "
+                       "%u exact-address / %u other endpoints, or a pattern id above n_patterns or without FB_WL_HAS_DOMAIN",
+                       FB_WL_MAX_EXACT, FB_WL_MAX_OTHER);
     DeviceGuard g(c->device);
     HIP_TRY(hipDeviceSynchronize());
     c->wl_active = false;
@@ -2009,6 +2118,9 @@ int fb_set_whitelist(fb_ctx* c, const fb_wl_endpoint* eps, uint64_t n, const uin
     if (!rc) rc = upload_array(w.rules, ix.rules.data(), ix.rules.size());
     if (!rc) rc = upload_array(w.owner, rec_owner_id, n_records);
     if (!rc) rc = upload_array(w.country, rec_country_id, n_records);
+    if (!rc) rc = upload_array(w.dpid, ix.dpid.data(), ix.dpid.size());
+    if (!rc) rc = upload_array(w.dkp, ix.dkp.data(), ix.dkp.size());
+    if (!rc && dom.active()) rc = wl_dom_upload(dom);
     if (rc) return rc;
     w.n4 = (uint32_t)ix.a4.size();
     w.n6 = (uint32_t)ix.a6.size();
@@ -2016,8 +2128,44 @@ int fb_set_whitelist(fb_ctx* c, const fb_wl_endpoint* eps, uint64_t n, const uin
     w.nr = (uint32_t)ix.rules.size();
     w.records = n_records;
     w.with_proc = ix.with_proc;
+    w.nd = (uint32_t)ix.dpid.size();
+    w.dom = std::move(dom);  // (no name matched yet)
     c->wl = std::move(w);
     c->wl_active = true;
+    return FB_OK;
+}
+
+int fb_set_whitelist(fb_ctx* c, const fb_wl_endpoint* eps, uint64_t n, const uint32_t* rec_owner_id,
+                     const uint32_t* rec_country_id, uint32_t n_records) {
+    return fb_set_whitelist_dom(c, eps, n, nullptr, nullptr, nullptr, 0u, rec_owner_id, rec_country_id, n_records);
+}
+
+int fb_wl_name_matches_dev(fb_ctx* c, const uint32_t* d_ids, uint64_t n, uint32_t* d_rows, uint8_t* d_flags, void* stream) {
+    if (!c || (n && (!d_ids || !d_rows || !d_flags))) return set_err(FB_ERR_INVAL, "bad arguments");
+    if (!c->wl_active) return set_err(FB_ERR_INVAL, "no whitelist is installed (fb_set_whitelist)");
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = wl_dom_sync(c, s);
+    if (rc) return rc;
+    const WlDomDev& d = c->wl.dom;
+    HIP_TRY(launch_wl_name_rows(d_ids, n, d.rows, d.flags, (uint32_t)d.upto, d_rows, d_flags, s));
+    return FB_OK;
+}
+
+int fb_wl_dom_info_get(fb_ctx* c, fb_wl_dom_info* out) {
+    if (!c || !out) return set_err(FB_ERR_INVAL, "bad arguments");
+    memset(out, 0, sizeof(*out));
+    if (!c->wl_active) return FB_OK;
+    const WlDomDev& d = c->wl.dom;
+    for (uint32_t k = 0; k < kWlDomKinds; ++k) out->patterns[k] = d.host.count[k];
+    out->names_done = d.upto;
+    if (d.ctr && d.upto) {
+        DeviceGuard g(c->device);
+        unsigned long long h[2] = {};
+        HIP_TRY(hipMemcpy(h, d.ctr, 16, hipMemcpyDeviceToHost));
+        out->names_matched = h[0];
+        out->names_overflowed = h[1];
+    }
     return FB_OK;
 }
 
@@ -2026,6 +2174,8 @@ int fb_clear_whitelist(fb_ctx* c) {
     DeviceGuard g(c->device);
     HIP_TRY(hipDeviceSynchronize());
     c->wl_active = false;
+    const int rc = wl_dom_forget(c->wl.dom);
+    if (rc) return rc;
     HIP_TRY(plane_zero(c, kPlaneWl, nullptr));  // every state back to Unknown
     HIP_TRY(hipStreamSynchronize(nullptr));
     return FB_OK;
@@ -2044,11 +2194,16 @@ int fb_flow_whitelist(fb_ctx* c, uint32_t flags, fb_wl_stats* out, void* stream)
     if (!rc) rc = plane_ensure(c, kPlaneWl, s);
     unsigned long long* mod = nullptr;
     if (!rc) rc = pass_stamps(c, s, &mod);
+    const bool with_dom = c->wl.nd != 0u;  // the names that appeared since the last call are matched first
+    if (!rc && with_dom) rc = wl_dom_sync(c, s);
     if (rc) return rc;
+    const WlDomDev& d = c->wl.dom;
+    const WlDomFlows df = {c->dns ? c->plane<fb_flow_domain>(kPlaneDom) : nullptr, d.rows, d.flags, (uint32_t)d.upto};
     // (whether a process endpoint with an id matches or asks for the host is decided here, by the name table
     // installed now: fb_set_whitelist and fb_set_l7_process_names may come in either order)
     HIP_TRY(launch_flow_whitelist(c->wl.tables(), c->en.tables(), c->d_cfg, c->tb.slots, c->tb.cap, c->plane<uint8_t>(kPlaneWl),
-                                  c->d_pass_stats, s, mod, c->pass_time, c->wl.with_proc, c->proc_names()));
+                                  c->d_pass_stats, s, mod, c->pass_time, c->wl.with_proc, c->proc_names(),
+                                  with_dom ? &df : nullptr));
     unsigned long long h[kWlCounters] = {};
     rc = pass_end(c, h, kWlCounters, s);
     if (rc) return rc;
@@ -2059,6 +2214,7 @@ int fb_flow_whitelist(fb_ctx* c, uint32_t flags, fb_wl_stats* out, void* stream)
         out->nonconforming = h[2];
         out->host_check = h[3];
         out->changed = h[4];
+        out->dom_overflow = h[5];
     }
     return FB_OK;
 }
@@ -2158,6 +2314,7 @@ int fb_dns_track_clear(fb_ctx* c) {
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
     rc = dnstrack_clear(c->dns, nullptr);
+    if (!rc) rc = wl_dom_forget(c->wl.dom);  // the ids died with the store: so did their match rows
     if (rc) return rc;
     HIP_TRY(plane_zero(c, kPlaneDom, nullptr));  // the ids died with the store
     HIP_TRY(hipStreamSynchronize(nullptr));

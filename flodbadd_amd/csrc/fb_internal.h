@@ -852,13 +852,23 @@ hipError_t launch_flow_export_anomalous(const FlowSlot* table, const fb_an_rec* 
 // programs).  Staged in LDS by every workgroup when groups and rules both fit (28 KiB: five 256-thread
 // workgroups per CU), else read from global memory.
 constexpr uint32_t kWlLdsRules = 512, kWlLdsGroups = 512;
-constexpr uint32_t kWlCounters = 5;  // fb_wl_stats' first five fields
+constexpr uint32_t kWlCounters = 6;  // fb_wl_stats' first five fields, then dom_overflow (the kDom instances')
 // with_proc: the list has process ids (WlIndex::with_proc) -- the process-aware instances run, reading the
-// flow's process through `names` (plane null: no L7 pass yet; n 0: no name table)
+// flow's process through `names` (plane null: no L7 pass yet; n 0: no name table).  dom: the list has domain
+// pattern ids (w.nd != 0) -- the kDom instances run, reading the flow's name id and the name's match row.
 hipError_t launch_flow_whitelist(const WlTables& w, const EnrichTables& t, const DevConfig* cfg, const FlowSlot* table,
                                  unsigned long long cap, uint8_t* state, unsigned long long* stats, hipStream_t s,
                                  unsigned long long* mod = nullptr, unsigned long long now = 0ull,
-                                 bool with_proc = false, const WlProcNames& names = WlProcNames());
+                                 bool with_proc = false, const WlProcNames& names = WlProcNames(),
+                                 const WlDomFlows* dom = nullptr);
+// The name-match kernel (fb_wl_domain.hip): the names first .. last (ids, 1-based) of the DNS
+// tracker's store against the pattern tables -- rows[id * FB_WL_NAME_MATCHES], flags[id]; ctr[0] += the names
+// with a non-empty row, ctr[1] += the overflowed ones.  launch_wl_name_rows: the rows of `n` given ids (zeros for
+// id 0 and past `upto`).
+hipError_t launch_wl_name_match(const WlDomTables& t, const uint32_t* names, const uint16_t* name_len, uint32_t first,
+                                uint32_t last, uint32_t* rows, uint8_t* flags, unsigned long long* ctr, hipStream_t s);
+hipError_t launch_wl_name_rows(const uint32_t* ids, unsigned long long n, const uint32_t* rows, const uint8_t* flags,
+                               uint32_t upto, uint32_t* out_rows, uint8_t* out_flags, hipStream_t s);
 hipError_t launch_flow_export_whitelist(const FlowSlot* table, const uint8_t* state, unsigned long long cap,
                                         uint32_t state_mask, fb_flow_rec* out, unsigned long long out_cap,
                                         unsigned long long* d_n, const FlowTime* plane, hipStream_t s);

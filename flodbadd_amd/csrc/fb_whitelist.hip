@@ -52,12 +52,16 @@ struct WlAsnDev {
 // kProc (the list has process ids, WlIndex::with_proc): the flow's process_match_id -- the L7 plane's element,
 // then the name table: one dependent load pair, issued before the group searches so it is in flight with them
 // -- gates the process endpoints (fb_wl_match.h).  The other instances read neither.
+// kDom (the list has domain pattern ids, WlTables::nd): the flow's dst_name_id -- the domain plane's element --
+// names the match row of its destination name (fb_wl_domain.hip), which decides the domain endpoints with an id
+// (fb_wl_match.h); a sixth counter takes the flows left to the host because their row overflowed.  The other
+// instances read neither the plane nor the rows.
 // Counters: PassCounters (fb_internal.h).
-template <bool kStaged, bool kStamp, bool kProc>
+template <bool kStaged, bool kStamp, bool kProc, bool kDom>
 __global__ __launch_bounds__(256) void k_flow_whitelist(const WlTables W, const EnrichTables E, const DevConfig* cfg,
                                                         const FlowSlot* T, unsigned long long cap, uint8_t* state,
                                                         unsigned long long* stats, unsigned long long* mod,
-                                                        unsigned long long now, const WlProcNames P) {
+                                                        unsigned long long now, const WlProcNames P, const WlDomFlows D) {
     __shared__ uint32_t s_gkey[kStaged ? kWlLdsGroups : 1u];
     __shared__ uint32_t s_gbeg[kStaged ? kWlLdsGroups + 1u : 1u];
     __shared__ uint4 s_rules[kStaged ? kWlLdsRules * 3u : 1u];
@@ -68,21 +72,31 @@ __global__ __launch_bounds__(256) void k_flow_whitelist(const WlTables W, const 
         for (uint32_t j = threadIdx.x; j < W.nr * 3u; j += 256u) s_rules[j] = src[j];
         __syncthreads();
     }
-    PassCounters<kWlCounters> cnt;
+    PassCounters<kDom ? kWlCounters : kWlCounters - 1u> cnt;
     const WlAsnDev asn = {W, E, cfg};
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < cap; base += stride) {
         const unsigned long long i = base + threadIdx.x;
         const bool occ = i < cap && T[i].tag >= 2u;
         uint32_t nb = 0u, old = 0u;
+        bool over = false;
         if (occ) {
             old = state[i];
             const uint32_t pm = kProc ? wl_flow_match_id(P, i) : 0u;
+            const uint32_t* row = nullptr;
+            uint32_t rflags = 0u;
+            if (kDom && D.plane) {  // (an id is never past the matched names: the call matched them first)
+                const uint32_t nid = D.plane[i].dst_name_id;
+                if (nid != 0u && nid <= D.n_names) {
+                    row = D.rows + (unsigned long long)nid * FB_WL_NAME_MATCHES;
+                    rflags = D.flags[nid];
+                }
+            }
             if (kStaged)
-                nb = wl_eval<kProc>(W, asn, s_gkey, s_gbeg, reinterpret_cast<const WlRule*>(s_rules), T[i].key, pm,
-                                    P.n != 0u);
+                nb = wl_eval<kProc, kDom>(W, asn, s_gkey, s_gbeg, reinterpret_cast<const WlRule*>(s_rules), T[i].key, pm,
+                                          P.n != 0u, row, rflags, &over);
             else
-                nb = wl_eval<kProc>(W, asn, W.gkey, W.gbeg, W.rules, T[i].key, pm, P.n != 0u);
+                nb = wl_eval<kProc, kDom>(W, asn, W.gkey, W.gbeg, W.rules, T[i].key, pm, P.n != 0u, row, rflags, &over);
             if (nb != old) state[i] = (uint8_t)nb;
             if (kStamp && nb != old) mod[i] = now;
         }
@@ -91,6 +105,7 @@ __global__ __launch_bounds__(256) void k_flow_whitelist(const WlTables W, const 
         cnt.add(2, (nb & FB_WL_NONCONFORMING) != 0u);
         cnt.add(3, (nb & FB_WL_HOST_CHECK) != 0u);
         cnt.add(4, occ && nb != old);
+        if (kDom) cnt.add(5, over);
     }
     cnt.flush(stats);
 }
@@ -116,7 +131,7 @@ __global__ __launch_bounds__(256) void k_flow_export_whitelist(const FlowSlot* T
 hipError_t launch_flow_whitelist(const WlTables& w, const EnrichTables& t, const DevConfig* cfg, const FlowSlot* table,
                                  unsigned long long cap, uint8_t* state, unsigned long long* stats, hipStream_t s,
                                  unsigned long long* mod, unsigned long long now, bool with_proc,
-                                 const WlProcNames& names) {
+                                 const WlProcNames& names, const WlDomFlows* dom) {
     if (!table || !state || !stats || !cfg || cap == 0ull) return hipErrorInvalidValue;
     if ((w.ng && (!w.gkey || !w.gbeg)) || (w.nr && !w.rules) || (w.n_records && (!w.rec_owner || !w.rec_country)))
         return hipErrorInvalidValue;
@@ -124,17 +139,36 @@ hipError_t launch_flow_whitelist(const WlTables& w, const EnrichTables& t, const
                      (names.n && (!names.match_id || !names.name_id)))
                   : ((w.n4 && (!w.a4 || !w.k4)) || (w.n6 && (!w.a6 || !w.k6))))
         return hipErrorInvalidValue;
+    if (dom && (!w.nd || !w.dpid || !w.dkp || (dom->n_names && (!dom->rows || !dom->flags)))) return hipErrorInvalidValue;
     const dim3 g(sweep_grid(cap, FB_WL_GRID));
     const bool staged = w.ng <= kWlLdsGroups && w.nr <= kWlLdsRules && w.ng;
-    if (with_proc) {
-        const auto k = staged ? (mod ? k_flow_whitelist<true, true, true> : k_flow_whitelist<true, false, true>)
-                              : (mod ? k_flow_whitelist<false, true, true> : k_flow_whitelist<false, false, true>);
-        hipLaunchKernelGGL(k, g, dim3(256), 0, s, w, t, cfg, table, cap, state, stats, mod, now, names);
-    } else {
-        const auto k = staged ? (mod ? k_flow_whitelist<true, true, false> : k_flow_whitelist<true, false, false>)
-                              : (mod ? k_flow_whitelist<false, true, false> : k_flow_whitelist<false, false, false>);
-        hipLaunchKernelGGL(k, g, dim3(256), 0, s, w, t, cfg, table, cap, state, stats, mod, now, WlProcNames());
+    // (a list without process ids runs the kProc false instances with an empty name table, one without pattern
+    // ids the kDom false ones with an empty WlDomFlows: the instances of before)
+    const WlProcNames pn = with_proc ? names : WlProcNames();
+    const WlDomFlows df = dom ? *dom : WlDomFlows();
+    const uint32_t inst = (staged ? 8u : 0u) | (mod ? 4u : 0u) | (with_proc ? 2u : 0u) | (dom ? 1u : 0u);
+    decltype(&k_flow_whitelist<false, false, false, false>) k = nullptr;
+    switch (inst) {
+#define FB_WL_INSTANCE(n, a, b, c, d) case n: k = k_flow_whitelist<a, b, c, d>; break;
+        FB_WL_INSTANCE(0, false, false, false, false)
+        FB_WL_INSTANCE(1, false, false, false, true)
+        FB_WL_INSTANCE(2, false, false, true, false)
+        FB_WL_INSTANCE(3, false, false, true, true)
+        FB_WL_INSTANCE(4, false, true, false, false)
+        FB_WL_INSTANCE(5, false, true, false, true)
+        FB_WL_INSTANCE(6, false, true, true, false)
+        FB_WL_INSTANCE(7, false, true, true, true)
+        FB_WL_INSTANCE(8, true, false, false, false)
+        FB_WL_INSTANCE(9, true, false, false, true)
+        FB_WL_INSTANCE(10, true, false, true, false)
+        FB_WL_INSTANCE(11, true, false, true, true)
+        FB_WL_INSTANCE(12, true, true, false, false)
+        FB_WL_INSTANCE(13, true, true, false, true)
+        FB_WL_INSTANCE(14, true, true, true, false)
+        FB_WL_INSTANCE(15, true, true, true, true)
+#undef FB_WL_INSTANCE
     }
+    hipLaunchKernelGGL(k, g, dim3(256), 0, s, w, t, cfg, table, cap, state, stats, mod, now, pn, df);
     return hipGetLastError();
 }
 

@@ -17,6 +17,12 @@
 // A flow (protocol P, destination port Q) can only match the endpoints of its four keys wl_key(0 | P,
 // none | Q): the kernel looks each up (one address search, four group searches).
 //
+// A list with domain pattern ids (fb_set_whitelist_dom) adds
+//   domains the endpoints with a pattern id, as (pattern id, key << 32 | process_match_id), ascending and
+//           deduplicated: dpid / dkp.  A flow whose destination name matched pattern p matches such an endpoint
+//           when the run of p holds one of its four keys with no process or the flow's -- one search of eight
+//           words per matched id (kDom; the other instances read neither the domain plane nor the rows).
+//
 // kProc selects the process-aware evaluation: the instances of a list without process ids (kProc false) read
 // neither the L7 plane nor a rule's process word nor kp4 / kp6 -- they are the pass as it was before the
 // device knew processes.
@@ -25,9 +31,11 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "../../include/flodbadd_gpu.h"
+#include "fb_wl_domain.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -52,7 +60,8 @@ FB_WL_HD uint32_t wl_key(uint32_t proto, bool has_port, uint32_t port) {
 // (a key has at most 22 bits: the two top bits of a group word are flags)
 constexpr uint32_t kWlGroupHostCheck = 0x80000000u;  // the host must look whatever the device knows
 constexpr uint32_t kWlGroupProcCheck = 0x40000000u;  // ... only while no process-name table is installed
-constexpr uint32_t kWlGroupFlags = kWlGroupHostCheck | kWlGroupProcCheck;
+constexpr uint32_t kWlGroupDomId = 0x20000000u;      // a domain endpoint with a pattern id has this key
+constexpr uint32_t kWlGroupFlags = kWlGroupHostCheck | kWlGroupProcCheck | kWlGroupDomId;
 struct WlRule {                   // 48 B: three 16-B LDS reads, and a net test of xor / and / or per word
     uint32_t a[4];                // family 2 / 10: the network (host bits cleared); family 0: as_number,
                                   // owner_id, country_id, 0
@@ -76,6 +85,9 @@ struct WlTables {
     const unsigned long long* kp4;  // [n4] key << 32 | process_match_id (a list with process ids: k4 / k6 empty)
     const unsigned long long* kp6;  // [n6]
     uint32_t n4, n6, ng, nr, n_records;
+    const uint32_t* dpid;            // [nd] the domain endpoints' pattern ids, ascending
+    const unsigned long long* dkp;   // [nd] key << 32 | process_match_id, ascending inside a pattern's run
+    uint32_t nd;
 };
 // The process of a flow (fb_set_l7_process_names): x = plane[slot].process_id names one when the plane exists,
 // x != 0 and x < n; its match class is match_id[x], its verbatim name name_id[x].  n == 0: no table.
@@ -192,6 +204,37 @@ FB_WL_HD bool wl_exact_match(const WlTables& W, const uint32_t ip[4], const uint
     return hit;
 }
 
+// Some domain endpoint has a pattern the flow's name matched (row: FB_WL_NAME_MATCHES ids ascending, zero-padded)
+// and one of the flow's four keys, with no process or the flow's (pm; 0: the flow has none): the run of each
+// matched id in dpid (lower and upper bound), then the (key, process) pairs inside it, as wl_exact_match.
+FB_WL_HD bool wl_domain_match(const WlTables& W, const uint32_t* row, const uint32_t keys[4], uint32_t pm) {
+    unsigned long long t[8];
+    for (int k = 0; k < 4; ++k) {
+        t[k] = (unsigned long long)keys[k] << 32;
+        t[4 + k] = t[k] | pm;
+    }
+    for (uint32_t j = 0; j < FB_WL_NAME_MATCHES; ++j) {
+        const uint32_t p = row[j];
+        if (p == 0u) break;
+        uint32_t lo = 0u, hi = W.nd, lo2 = 0u, hi2 = W.nd;  // first id >= p; first id > p
+        while (lo < hi || lo2 < hi2) {
+            const bool on1 = lo < hi, on2 = lo2 < hi2;
+            const uint32_t m1 = (lo + hi) >> 1, m2 = (lo2 + hi2) >> 1;
+            const uint32_t v1 = on1 ? W.dpid[m1] : 0u, v2 = on2 ? W.dpid[m2] : 0u;
+            if (on1) {
+                if (v1 < p) lo = m1 + 1u;
+                else hi = m1;
+            }
+            if (on2) {
+                if (p < v2) hi2 = m2;
+                else lo2 = m2 + 1u;
+            }
+        }
+        if (lo < lo2 && wl_find_any<8>(W.dkp, lo, lo2, t, pm ? 0xFFu : 0x0Fu)) return true;
+    }
+    return false;
+}
+
 // dst_asn of a flow (src/packets.rs:468-485) as the evaluation asks for it, at most once per flow:
 //   bool asn(dst, v6, as_number, owner, country)   false: None; owner / country ~0u: a string no endpoint has
 //
@@ -199,16 +242,20 @@ FB_WL_HD bool wl_exact_match(const WlTables& W, const uint32_t ip[4], const uint
 // (a workgroup's LDS copy, or global memory).  kProc: pm is the flow's process_match_id (0: None) and
 // have_names whether a process-name table is installed -- without one a process endpoint with an id is what
 // one without an id always is: it never matches and its key is a host-check key.
-template <bool kProc, class Asn>
+// kDom: row / row_flags are the match row and the flags byte of the flow's destination name (null: the flow has
+// no domain) -- a domain endpoint with a pattern id matches by it; dom_overflow: set when the flow is marked for
+// the host because the row is incomplete.
+template <bool kProc, bool kDom = false, class Asn>
 FB_WL_HD uint32_t wl_eval(const WlTables& W, const Asn& asn, const uint32_t* gkey, const uint32_t* gbeg,
-                          const WlRule* rules, const uint32_t* key, uint32_t pm, bool have_names) {
+                          const WlRule* rules, const uint32_t* key, uint32_t pm, bool have_names,
+                          const uint32_t* row = nullptr, uint32_t row_flags = 0u, bool* dom_overflow = nullptr) {
     const uint32_t dst[4] = {key[4], key[5], key[6], key[7]};
     const uint32_t port = key[8] >> 16, proto = key[9] & 0xFFu, fam = (key[9] >> 8) & 0xFFu;
     const bool v6 = fam == 10u;
     // protocol_matches / port_matches (src/whitelists.rs:711-732): None or equal
     const uint32_t keys[4] = {wl_key(0u, false, 0u), wl_key(0u, true, port), wl_key(proto, false, 0u),
                               wl_key(proto, true, port)};
-    bool ok = false, hc = false;
+    bool ok = false, hc = false, domid = false;
     // dst_asn, looked up when the first rule with an AS field is reached
     bool asn_done = false, asn_some = false;
     uint32_t as_number = 0u, owner = ~0u, country = ~0u;
@@ -217,6 +264,7 @@ FB_WL_HD uint32_t wl_eval(const WlTables& W, const Asn& asn, const uint32_t* gke
         if (g == ~0u) continue;
         hc |= (gkey[g] & kWlGroupHostCheck) != 0u;
         if (kProc) hc |= !have_names && (gkey[g] & kWlGroupProcCheck) != 0u;
+        if (kDom) domid |= (gkey[g] & kWlGroupDomId) != 0u;
         const uint32_t end = gbeg[g + 1u];
         for (uint32_t r = gbeg[g]; r < end && !ok; ++r) {
             // the whole rule first, so its three 16-B reads are in flight together (read behind the branch
@@ -248,7 +296,12 @@ FB_WL_HD uint32_t wl_eval(const WlTables& W, const Asn& asn, const uint32_t* gke
                  (!(want & FB_WL_HAS_COUNTRY) || (country != ~0u && a.z == country));
         }
     }
+    if (kDom && !ok && row && domid) ok = wl_domain_match(W, row, keys, pm);
     if (!ok) ok = v6 ? wl_exact_match<true, kProc>(W, dst, keys, pm) : wl_exact_match<false, kProc>(W, dst, keys, pm);
+    if (kDom && !ok && row && domid && (row_flags & 1u)) {  // the row is not all the name matches: the host's
+        if (dom_overflow) *dom_overflow = true;
+        hc = true;
+    }
     return ok ? FB_WL_CONFORMING : (FB_WL_NONCONFORMING | (hc ? FB_WL_HOST_CHECK : 0u));
 }
 
@@ -259,6 +312,8 @@ struct WlIndex {
     std::vector<WlU4> a6;
     std::vector<WlRule> rules;
     bool with_proc = false;  // some endpoint has a process with an id: the kProc instances run
+    std::vector<uint32_t> dpid;           // the domain endpoints with a pattern id: ordered by (pattern id, key,
+    std::vector<unsigned long long> dkp;  // process), deduplicated.  Non-empty: the kDom instances run
 };
 // What the device can decide about an endpoint (dst_domain = None; the process by its id):
 //   protocol "never"           nothing matches it, not even the host-check condition: dropped;
@@ -268,11 +323,16 @@ struct WlIndex {
 //   domain-only                never matches; its key is a host-check key;
 //   domain + ip                matches by the address alone (a matching ip returns true, a mismatch fails
 //                              the endpoint; src/whitelists.rs:503-531); its key is a host-check key too;
+//   domain with a pattern id   (ep_pattern[i] != 0) also matches the flows whose name matched the pattern --
+//                              protocol, port and process permitting --, and its key is no host-check key on
+//                              the domain's account (kWlGroupDomId instead);
 //   ip (unparsable)            never matches;
 //   ip (address or net)        matches by the address; the AS fields are never reached;
 //   neither domain nor ip      every specified AS field must match (none: matches everything).
-// false: an endpoint with a bad family / prefix / protocol, or more than FB_WL_MAX_EXACT / _OTHER.
-inline bool build_whitelist_index(const fb_wl_endpoint* eps, uint64_t n, WlIndex& ix) {
+// false: an endpoint with a bad family / prefix / protocol, more than FB_WL_MAX_EXACT / _OTHER, a pattern id
+// above n_patterns or on an endpoint without a domain.
+inline bool build_whitelist_index(const fb_wl_endpoint* eps, uint64_t n, WlIndex& ix, const uint32_t* ep_pattern = nullptr,
+                                  uint64_t n_patterns = 0u) {
     typedef unsigned __int128 u128;
     struct E6 {
         u128 a;
@@ -290,9 +350,12 @@ inline bool build_whitelist_index(const fb_wl_endpoint* eps, uint64_t n, WlIndex
     std::vector<E6> e6;
     std::vector<EP> p4, p6;
     std::vector<Keyed> rules;
-    std::vector<uint32_t> hck, pck;
+    std::vector<uint32_t> hck, pck, dck;
+    std::vector<std::pair<uint32_t, unsigned long long>> dom;
     for (uint64_t i = 0; i < n; ++i) {
         const fb_wl_endpoint& e = eps[i];
+        const uint32_t dp = ep_pattern ? ep_pattern[i] : 0u;
+        if (dp > n_patterns || (dp && !(e.flags & FB_WL_HAS_DOMAIN))) return false;
         const bool v4 = e.family == 2u, v6 = e.family == 10u;
         if (!(e.family == 0u || v4 || v6 || e.family == FB_WL_NEVER)) return false;
         if ((v4 && e.prefix > 32u) || (v6 && e.prefix > 128u)) return false;
@@ -302,9 +365,12 @@ inline bool build_whitelist_index(const fb_wl_endpoint* eps, uint64_t n, WlIndex
         const uint32_t key = wl_key(e.protocol, (e.flags & FB_WL_HAS_PORT) != 0u, e.port);
         const bool has_proc = (e.flags & FB_WL_HAS_PROCESS) != 0u;
         const uint32_t pm = has_proc ? e.process_match_id : 0u;
-        if ((e.flags & FB_WL_HAS_DOMAIN) || (has_proc && pm == 0u)) hck.push_back(key);
+        if (((e.flags & FB_WL_HAS_DOMAIN) && dp == 0u) || (has_proc && pm == 0u)) hck.push_back(key);
         if (pm != 0u && (pck.empty() || pck.back() != key)) pck.push_back(key);  // (a key, not an endpoint: not counted)
-        if ((has_proc && pm == 0u) || e.family == FB_WL_NEVER) continue;
+        if (dp && (dck.empty() || dck.back() != key)) dck.push_back(key);
+        if (has_proc && pm == 0u) continue;
+        if (dp) dom.push_back({dp, (unsigned long long)key << 32 | pm});
+        if (e.family == FB_WL_NEVER) continue;
         if (e.family == 0u) {
             if (e.flags & FB_WL_HAS_DOMAIN) continue;
             Keyed k = {};
@@ -358,7 +424,15 @@ inline bool build_whitelist_index(const fb_wl_endpoint* eps, uint64_t n, WlIndex
     hck.erase(std::unique(hck.begin(), hck.end()), hck.end());
     std::sort(pck.begin(), pck.end());
     pck.erase(std::unique(pck.begin(), pck.end()), pck.end());
+    std::sort(dck.begin(), dck.end());
+    dck.erase(std::unique(dck.begin(), dck.end()), dck.end());
+    std::sort(dom.begin(), dom.end());
+    dom.erase(std::unique(dom.begin(), dom.end()), dom.end());
     ix = WlIndex();
+    for (const auto& d : dom) {
+        ix.dpid.push_back(d.first);
+        ix.dkp.push_back(d.second);
+    }
     ix.with_proc = !pck.empty();
     if (ix.with_proc) {  // per family one array ordered by (address, key, process), deduplicated
         for (unsigned long long v : e4) p4.push_back(EP{(u128)(v >> 32), (v & 0xFFFFFFFFull) << 32});
@@ -389,6 +463,7 @@ inline bool build_whitelist_index(const fb_wl_endpoint* eps, uint64_t n, WlIndex
     // the group table: the distinct keys of the rules and of the two host-check lists, ascending
     std::vector<uint32_t> keys(hck);
     keys.insert(keys.end(), pck.begin(), pck.end());
+    keys.insert(keys.end(), dck.begin(), dck.end());
     for (const Keyed& k : rules) keys.push_back(k.key);
     std::sort(keys.begin(), keys.end());
     keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
@@ -397,6 +472,7 @@ inline bool build_whitelist_index(const fb_wl_endpoint* eps, uint64_t n, WlIndex
         uint32_t word = key;
         if (std::binary_search(hck.begin(), hck.end(), key)) word |= kWlGroupHostCheck;
         if (std::binary_search(pck.begin(), pck.end(), key)) word |= kWlGroupProcCheck;
+        if (std::binary_search(dck.begin(), dck.end(), key)) word |= kWlGroupDomId;
         ix.gkey.push_back(word);
         ix.gbeg.push_back((uint32_t)ix.rules.size());
         for (; r < rules.size() && rules[r].key == key; ++r) ix.rules.push_back(rules[r].r);

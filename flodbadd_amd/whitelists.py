@@ -140,6 +140,19 @@ def domain_matches(session_domain, pattern):
     return domain == pattern
 
 
+def classify_domain_pattern(pattern):
+    """The kind of a lower-cased pattern as domain_matches tells them apart, in its order: "exact" (no '*'),
+    "suffix" ("*.s"), "prefix" ("q.*"), "general" (one '*': a*b) or "never" -- what fb_set_whitelist_dom
+    classifies the pattern's bytes as."""
+    if "*" not in pattern:
+        return "exact"
+    if pattern.startswith("*."):
+        return "suffix"
+    if pattern.endswith(".*"):
+        return "prefix"
+    return "general" if pattern.count("*") == 1 else "never"
+
+
 def ip_matches(session_ip, pattern):
     """src/whitelists.rs:682-709."""
     if pattern is None:
@@ -222,6 +235,12 @@ class CompiledWhitelist:
     rec_owner_id: np.ndarray            # uint32 per ASN record
     rec_country_id: np.ndarray
     strings: dict                       # lower-cased string -> id
+    # compile(domain_patterns=True), the further fb_set_whitelist_dom arguments: the distinct lower-cased domain
+    # patterns (id = index + 1), their UTF-8 bytes and offsets, and the pattern id of every row (0: none)
+    patterns: Optional[List[str]] = None
+    ep_pattern: Optional[np.ndarray] = None
+    pattern_bytes: Optional[np.ndarray] = None
+    pattern_off: Optional[np.ndarray] = None
 
 
 def _ip_fields(row, text):
@@ -371,7 +390,7 @@ class Whitelists:
         out.whitelists = merged
         return out.to_json(compact=True)
 
-    def compile(self, name, asn_records=None, dns_resolutions=None, process_ids=None):
+    def compile(self, name, asn_records=None, dns_resolutions=None, process_ids=None, domain_patterns=False):
         """The flattened list `name` as fb_wl_endpoint rows.  asn_records: the (as_number, country,
         owner) of every fb_asn_range.record (asn_tables_from_tsv's third result), for the interned
         owner / country ids.  dns_resolutions {ip: domain}: every domain endpoint whose pattern matches
@@ -381,9 +400,15 @@ class Whitelists:
         l7.ProcessNameInterner -- every endpoint with a process then carries its process_match_id (the
         word `reserved2` of the rows, N.WL_ENDPOINT_PROC_DTYPE), expanded rows included, and the device
         matches it against the flows' processes (fb_set_l7_process_names); without it the word stays 0
-        and such an endpoint is the host's to decide."""
+        and such an endpoint is the host's to decide.  domain_patterns: no expansion (dns_resolutions must be
+        None) -- the result carries the distinct lower-cased patterns and every row's pattern id for
+        fb_set_whitelist_dom, which matches them against the names the device tracks; the general (a*b)
+        patterns past the FB_WL_MAX_GENERAL-th distinct one, in list order, get id 0 and stay the host's."""
+        if domain_patterns and dns_resolutions:
+            raise ValueError("domain_patterns compiles no resolutions into the list")
         eps = self.get_all_endpoints(name)
         strings = {}
+        pattern_ids, patterns, ep_pattern, generals = {}, [], [], 0
 
         def intern(s):
             return strings.setdefault(ascii_lower(s), len(strings))
@@ -421,6 +446,17 @@ class Whitelists:
                 r["country_id"] = intern(ep.as_country)
             if ep.domain is not None:
                 flags |= N.FB_WL_HAS_DOMAIN
+                if domain_patterns:
+                    pat = ep.domain.lower()
+                    if pat not in pattern_ids:
+                        general = classify_domain_pattern(pat) == "general"
+                        generals += general
+                        if general and generals > N.FB_WL_MAX_GENERAL:
+                            pattern_ids[pat] = 0
+                        else:
+                            patterns.append(pat)
+                            pattern_ids[pat] = len(patterns)
+                    ep_pattern.append(pattern_ids[pat])
                 for a, dom in resolved:
                     if domain_matches(dom, ep.domain):
                         x = base.copy()
@@ -429,11 +465,20 @@ class Whitelists:
                         rows.append(x)
             r["flags"] = flags
             rows.append(r)
+            if domain_patterns and ep.domain is None:
+                ep_pattern.append(0)
         recs = list(asn_records or [])
         owner = np.array([intern(o) for _, _, o in recs], dtype=np.uint32)
         country = np.array([intern(c) for _, c, _ in recs], dtype=np.uint32)
         arr = np.array(rows, dtype=N.WL_ENDPOINT_DTYPE) if rows else np.zeros(0, dtype=N.WL_ENDPOINT_DTYPE)
-        return CompiledWhitelist(name, eps, arr, owner, country, strings)
+        comp = CompiledWhitelist(name, eps, arr, owner, country, strings)
+        if domain_patterns:
+            blobs = [p.encode("utf-8") for p in patterns]
+            comp.patterns = patterns
+            comp.ep_pattern = np.array(ep_pattern, dtype=np.uint32)
+            comp.pattern_bytes = np.frombuffer(b"".join(blobs), dtype=np.uint8).copy()
+            comp.pattern_off = np.cumsum([0] + [len(b) for b in blobs], dtype=np.uint64)
+        return comp
 
 
 def rows_from_flows(flows):
@@ -454,4 +499,4 @@ def rows_from_flows(flows):
 
 
 __all__ = ["WhitelistEndpoint", "WhitelistInfo", "Whitelists", "CompiledWhitelist", "domain_matches", "ip_matches",
-           "endpoint_matches", "is_session_in_whitelist", "no_match_reason", "rows_from_flows", "dedup_endpoints", "ascii_lower", "rust_debug", "parse_ip", "parse_net"]
+           "classify_domain_pattern", "endpoint_matches", "is_session_in_whitelist", "no_match_reason", "rows_from_flows", "dedup_endpoints", "ascii_lower", "rust_debug", "parse_ip", "parse_net"]

@@ -351,14 +351,18 @@ int fb_set_frame_times(fb_ctx* ctx, const uint64_t* d_ts);
  * slots are launch numbers, and a tracker past launch 0xF0000000 restamps what it holds before its next
  * call: a week of capture, or this knob).  FB_ERR_INVAL without fb_dns_track_enable, for 0 or a value of
  * 2^32 and more, and for a value below the current number -- going backwards would leave published slots
- * reading "not yet". */
+ * reading "not yet".;
+ * FB_DEBUG_WL_NAME_HASH_MASK -- ANDed into the hash of a domain pattern and of every part of a name that is
+ * looked up among the patterns (fb_set_whitelist_dom); 0 restores all bits.  Setting it rebuilds the installed
+ * pattern tables and forgets the match state of every name; the rows never depend on it. */
 enum fb_debug_knob {
     FB_DEBUG_DENSE_STEAL_POLLS = 1,
     FB_DEBUG_DENSE_OFFSET_SKEW = 2,
     FB_DEBUG_VIEW_DIRECT = 3,
     FB_DEBUG_ZEEK_DIRECT = 4,
     FB_DEBUG_LEARN_HASH_MASK = 6, /* (5 stays unassigned: the refusal of an unknown knob is tested with it) */
-    FB_DEBUG_DNS_LAUNCH = 7
+    FB_DEBUG_DNS_LAUNCH = 7,
+    FB_DEBUG_WL_NAME_HASH_MASK = 8
 };
 int fb_debug_set(fb_ctx* ctx, uint32_t knob, uint64_t value);
 /* Whether the fused parse + upsert calls (fb_process_seg_dev, fb_process_seg_async_dev) store the
@@ -1050,7 +1054,11 @@ typedef struct fb_wl_stats {
     uint64_t host_check;    /* of the nonconforming: FB_WL_HOST_CHECK set                              */
     uint64_t changed;       /* flows whose state byte differs from before the call (the reference bumps
                                last_modified for those, src/whitelists.rs:975-982)                     */
-    uint64_t reserved[3];
+    union {                 /* 40: three words, the first under two names                             */
+        uint64_t reserved[3];
+        uint64_t dom_overflow; /* of the host_check: marked because their name matched more patterns than
+                                  FB_WL_NAME_MATCHES (fb_set_whitelist_dom); 0 for a list without patterns */
+    };
 } fb_wl_stats; /* 64 bytes */
 /* Evaluate every flow against the installed list (the reference's incremental selection is an
  * optimisation of a pure function of the session, so a full pass gives the same states).  Synchronous:
@@ -1067,6 +1075,43 @@ int fb_flow_whitelist_dev(fb_ctx* ctx, uint8_t* d_out, uint64_t cap, void* strea
  * the first `cap` are written).  DEVICE pointers, asynchronous. */
 int fb_flow_export_whitelist_dev(fb_ctx* ctx, uint32_t state_mask, fb_flow_rec* d_out, uint64_t cap, uint64_t* d_n,
                                  void* stream);
+
+/* ---- domain endpoints on the device (domain_matches, src/whitelists.rs:602-679) ---------------------
+ * fb_set_whitelist with the domain patterns of the list beside the endpoints: ep_pattern[i] is the 1-based
+ * id of endpoint i's pattern (only with FB_WL_HAS_DOMAIN), 0 when the device has none -- that endpoint is what
+ * it is under fb_set_whitelist: it never matches by domain and its key is a host-check key.  Pattern p is
+ * pattern_bytes[pattern_off[p - 1], pattern_off[p]) (pattern_off[0] = 0), lower-cased by the caller; the call
+ * classifies it (a name n of the DNS tracker, ASCII A-Z lower-cased, matches
+ *   no '*': n == pattern;  "*.s": some n[i] == '.' with n[i + 1:] == s;  else "q.*": n == q or some n[i] == '.'
+ *   with n[:i] == q;  else one '*', "a*b": n starts with a, ends with b and is longer than both;  else never).
+ * An endpoint with a pattern id matches a flow whose protocol, port and process match (the process as under
+ * fb_set_whitelist) and whose dst_name_id (the domain plane, as of the last fb_flow_domains) names a matching
+ * name; then its `ip`, if any, decides as before.  FB_ERR_INVAL, the installed list untouched, for what
+ * fb_set_whitelist refuses and for: an id above n_patterns, an id on an endpoint without FB_WL_HAS_DOMAIN, more
+ * than FB_WL_MAX_GENERAL patterns of the a*b kind, pattern bytes of 2^32 and more, more than 2^24 - 1 patterns,
+ * offsets that do not ascend from 0.  fb_set_whitelist is this call with no patterns.
+ * Every name keeps the ids of the patterns it matches: FB_WL_NAME_MATCHES per name, ascending, zero-padded; a
+ * name that matches more keeps the least and an overflow flag, and a NonConforming flow of such a name gets
+ * FB_WL_HOST_CHECK when one of its four keys has a domain endpoint with an id (fb_wl_stats.dom_overflow counts
+ * them).  Names are matched once, by the first fb_flow_whitelist / fb_wl_name_matches_dev after they appear;
+ * fb_set_whitelist*, fb_clear_whitelist, fb_dns_track_clear and FB_DEBUG_WL_NAME_HASH_MASK start over. */
+#define FB_WL_MAX_GENERAL 1024u
+#define FB_WL_NAME_MATCHES 8u
+int fb_set_whitelist_dom(fb_ctx* ctx, const fb_wl_endpoint* eps, uint64_t n, const uint32_t* ep_pattern,
+                         const uint8_t* pattern_bytes, const uint64_t* pattern_off, uint64_t n_patterns,
+                         const uint32_t* rec_owner_id, const uint32_t* rec_country_id, uint32_t n_records);
+/* Brings the match state up to date, then d_rows[i * FB_WL_NAME_MATCHES ..] / d_flags[i] (bit 0: overflow) of
+ * name id d_ids[i]; id 0, an id beyond the stored names, no installed patterns or no DNS tracking: zeros.
+ * DEVICE pointers.  FB_ERR_INVAL without an installed list. */
+int fb_wl_name_matches_dev(fb_ctx* ctx, const uint32_t* d_ids, uint64_t n, uint32_t* d_rows, uint8_t* d_flags,
+                           void* stream);
+typedef struct fb_wl_dom_info {
+    uint64_t patterns[5];      /*  0: installed patterns per kind: exact, suffix, prefix, general, never       */
+    uint64_t names_done;       /* 40: names whose row is up to date (ids 1 .. names_done)                      */
+    uint64_t names_matched;    /* 48: of them with a non-empty row                                             */
+    uint64_t names_overflowed; /* 56: of them with the overflow flag                                           */
+} fb_wl_dom_info; /* 64 bytes */
+int fb_wl_dom_info_get(fb_ctx* ctx, fb_wl_dom_info* out);
 
 /* ---- blacklist pass over the session table (src/blacklists.rs:456-731, src/capture.rs:1850-1871) ----
  * recompute_blacklist_for_sessions gives every session the names of the lists one of whose ranges
